@@ -15,6 +15,8 @@
     (18 layers, 20 Sinkhorn iterations); roofline objects for the Sinkhorn sweeps (HBM) and the attention kernel (MFMA).
 Every rank processes its own steps (weak scaling, epochs sharded round-robin); the timed region ends with the job's single
 collective, one all-gather of the per-rank match tables (RCCL). Prints ONE JSON line on rank 0.
+--steps K: the timed region is exactly K steps; `ms_per_step` is its time / K.
+--dump-outputs DIR: after the timed region, the last timed step's match-table records as DIR/<name>.npy (`dump_outputs`).
 --dry-run: no GPU work at all (fabricated records): exercises spawn, rendezvous (gloo), sharding, the table all-gather and the
     JSON contract on a CPU-only machine (tests/test_host_cpu.py).
 """
@@ -60,7 +62,6 @@ PEAK_HBM_GBS = 8000.0          # same guide: HBM3E spec peak (6.3 TB/s is what a
 # (round 3, three boxes: 2 -> 105.8, 4 -> 107.3, 5 -> 107.5, 8 -> 108.1, 10 -> 107.0-108, 16 -> 106.6, 25 -> 106.3: the same shape.)
 # 10 divides the default 50 steps and the driver's 20. tests/test_gpu_fullsize.py checks this very mode against one pair per launch.
 DEFAULT_PAIRS_PER_LAUNCH = 10
-VALUE_REPEATS = 5                # timed regions of `steps` steps each, back to back; `value` = the median region
 SIDE_CONFIG3_EPOCHS = 60         # distinct epochs of the default line's `side_measurements.config3_distinct_epochs`
 TRAFFIC_FILE = os.path.join(ROOT, "profiles", "traffic.json")   # PMC-derived HBM bytes per launch (latest round)
 
@@ -168,6 +169,9 @@ def main():
     ap.add_argument("--fail-epochs", default="", help="test hook for the failure isolation of the sharded driver: comma-separated epochs whose "
                     "input pair is replaced by an array of the wrong shape; their records come out as n_matches = -1, the rank goes on, "
                     "the all-gather happens and the line lists them in `failed_epochs`")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the match-table records of the last timed step (one per rank) as DIR/<name>.npy "
+                         "(see `dump_outputs`); the inputs are seeded, so two builds run with the same arguments can be compared array by array")
     args = ap.parse_args()
     if args.steps is None:
         args.steps = {2: 50, 3: 256, 4: max(1, 2048 // max(args.gpus, 1)), 5: 5}[args.config]
@@ -320,32 +324,29 @@ def main():
     # the gather / sort of the match tables is part of the timed region: run it once untimed as well, so that the lazy
     # loading of torch's indexing and sort kernels (100+ ms in a fresh process) is not billed to the timed steps
     all_gather_tables(scratch.cpu() if one_dev else scratch)
-    # The timed region: EXACTLY `steps` steps bracketed by barrier + synchronize, ending with the job's one collective. It is run
-    # VALUE_REPEATS times back to back (same steps, same inputs, records overwritten) and `value` is the median region - with the driver's
-    # 20 steps a region is two graph replays per launch group, 0.18 s, and a single hiccup would be 1-2 % of it; every region is listed.
-    regions = []
-    for rep in range(VALUE_REPEATS):
-        barrier()
-        t0 = time.perf_counter()
-        for i in range(args.steps):
-            ep = epochs[args.warmup + i]
-            sm.match_pair(bad_pair if ep in fail_epochs else pool[(args.warmup + i) % len(pool)], ep, table, i)
-        sm.flush()
-        t_enq = time.perf_counter() - t0            # host time to enqueue every step (graph launches are asynchronous)
-        sm.synchronize()
-        t_own = time.perf_counter() - t0            # this rank's own pairs done (before the collective)
-        t_g = time.perf_counter()
-        full = all_gather_tables(table.cpu() if one_dev else table)
-        torch.cuda.synchronize()
-        t_gather = time.perf_counter() - t_g
-        barrier()
-        dt = time.perf_counter() - t0
-        if world > 1 or force_dist:                 # the slowest rank's clock is the region's
-            t = torch.tensor([dt], dtype=torch.float64, device="cpu" if one_dev else "cuda")
-            dist.all_reduce(t, op=dist.ReduceOp.MAX)
-            dt = float(t.item())
-        regions.append((dt, t_enq, t_own, t_gather))
-    dt, t_enq, t_own, t_gather = sorted(regions)[len(regions) // 2]
+    # The timed region: EXACTLY `steps` steps bracketed by barrier + synchronize, ending with the job's one collective. `--steps` is the
+    # number of timed steps and `ms_per_step` this region's time over it: callers size later runs from it.
+    barrier()
+    t0 = time.perf_counter()
+    for i in range(args.steps):
+        ep = epochs[args.warmup + i]
+        sm.match_pair(bad_pair if ep in fail_epochs else pool[(args.warmup + i) % len(pool)], ep, table, i)
+    sm.flush()
+    t_enq = time.perf_counter() - t0            # host time to enqueue every step (graph launches are asynchronous)
+    sm.synchronize()
+    t_own = time.perf_counter() - t0            # this rank's own pairs done (before the collective)
+    t_g = time.perf_counter()
+    full = all_gather_tables(table.cpu() if one_dev else table)
+    torch.cuda.synchronize()
+    t_gather = time.perf_counter() - t_g
+    barrier()
+    dt = time.perf_counter() - t0
+    if world > 1 or force_dist:                 # the slowest rank's clock is the region's
+        t = torch.tensor([dt], dtype=torch.float64, device="cpu" if one_dev else "cuda")
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        dt = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, full, kpts, world)
     ranks = None
     if world > 1 or force_dist:
         dev_ = "cpu" if one_dev else "cuda"
@@ -385,9 +386,6 @@ def main():
                    "mean_keypoints": n0, "mean_matches": nm},
         "host_enqueue_ms_per_step": 1e3 * t_enq / args.steps, "untimed_pairs_before_timing": warm_pairs,
         "all_gather_ms": 1e3 * t_gather,
-        "value_repeats": {"pairs_per_s": [n_pairs / r[0] for r in regions], "ms_per_step": [1e3 * r[0] / args.steps for r in regions],
-                          "value_is": "the median of these back-to-back timed regions of `steps` steps each (barrier + synchronize on both "
-                                      "sides, the table all-gather inside, max over ranks per region)"},
         "failed_epochs": failed_epochs,
     }
     if failed_epochs:
@@ -850,6 +848,24 @@ def cpu_baseline(epochs):
                           "sample": f"weights rebuilt inside every call: median of 2 pairs, {med_a:.2f} s per pair"}}
 
 
+def dump_outputs(out_dir, full, kpts, world):
+    """`--dump-outputs DIR`: what the timed path handed its caller in its last step - the match-table record of that step on every rank,
+    i.e. the last `world` rows of the gathered table (sorted by epoch; layout in icepy4d_amd/sequence.py) - decoded into one .npy per
+    field. Integer fields as float64 (exact for int32), scores and keypoints as float32: under 0.25 MB per rank in every
+    configuration (12 bytes per keypoint, 28 with the keypoints of configs[3])."""
+    import numpy as np
+    from icepy4d_amd.sequence import HEADER
+    rec = full[-world:].cpu().numpy()
+    K = kpts
+    out = {"epoch": rec[:, 0], "n_keypoints": rec[:, 1:3], "n_matches": rec[:, 3], "stop_layer": rec[:, 4],
+           "matches0": rec[:, HEADER:HEADER + K], "matching_scores0": rec[:, HEADER + K:HEADER + 2 * K].view(np.float32)}
+    if rec.shape[1] == HEADER + 6 * K:          # configs[3]: the records carry the keypoints of both images
+        out["keypoints"] = rec[:, HEADER + 2 * K:].view(np.float32).reshape(-1, 2, K, 2)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32 if a.dtype == np.float32 else np.float64))
+
+
 def dry_run(args, rank, world, epochs, kpts, dist):
     """No GPU: every rank fabricates the records of its epochs (n_matches = epoch), the tables are all-gathered over gloo and
     rank 0 prints a JSON line with the contract's fields (value = records per second of this fake work: NOT a measurement)."""
@@ -885,6 +901,8 @@ def dry_run(args, rank, world, epochs, kpts, dist):
     assert full.shape[0] == n_pairs, (full.shape, n_pairs)
     want = sorted(e for r in range(world) for e in range(r, (args.warmup + args.steps) * world, world)[args.warmup:])
     assert full[:, 0].tolist() == want and full[:, 3].tolist() == [(-1 if e in fail_epochs else e) for e in want]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, full, kpts, world)
     ranks = rank_report(dist, rank, world, args, t_own, t_gather, -1, "cpu", table, full, True) if world > 1 else None
     if rank == 0:
         emit(json.dumps({"ranks": ranks, "metric": "matched stereo image-pairs/sec (4096 kpts, 1080p)", "value": n_pairs / dt, "unit": "pairs/s",

@@ -162,10 +162,11 @@ def test_config3_timed_launch_mode_equals_direct_launches_and_the_oracle():
 @pytest.mark.parametrize("flags", [["--steps", "5", "--warmup", "3"], ["--steps", "2", "--warmup", "0"],
                                    ["--steps", "4", "--warmup", "2", "--config", "4", "--pool", "2"],
                                    ["--steps", "10", "--warmup", "2", "SIDE"]])
-def test_bench_line_with_odd_step_counts(flags):
+def test_bench_line_with_odd_step_counts(flags, tmp_path):
     """`python bench.py --gpus 1 --steps K --warmup W` as the round driver types it, with counts that do not fill the launch
     groups (ten pairs each by default): one JSON line with the contract fields, every step recorded, a throughput in the range of the device
-    (an odd warm-up once left a parked pair behind and shifted every timed group: 93 instead of 102 pairs/s at K = 20, W = 5)."""
+    (an odd warm-up once left a parked pair behind and shifted every timed group: 93 instead of 102 pairs/s at K = 20, W = 5).
+    `--dump-outputs`: the record of the last timed step (epoch W + K - 1) as float .npy files, consistent in itself."""
     import json
     import os
     import subprocess
@@ -174,8 +175,10 @@ def test_bench_line_with_odd_step_counts(flags):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
     side = "SIDE" in flags                  # the default line's side measurements (configs[2] / configs[4] / one match() call) ride along
     flags = [f for f in flags if f != "SIDE"]
+    dump = tmp_path / "outputs"
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", *flags, "--no-cpu-baseline",
-                        *([] if side else ["--no-side-measurements"])], env=env, capture_output=True, text=True, timeout=900)
+                        *([] if side else ["--no-side-measurements"]), "--dump-outputs", str(dump)],
+                       env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout
@@ -194,3 +197,14 @@ def test_bench_line_with_odd_step_counts(flags):
         assert sm["other_launch_mode"]["pairs_per_s"] > 5.0 and sm["host_inputs_pairs_per_s"]["pairs_per_s"] > 5.0
     if "--config" in flags:                 # configs[3] on one rank: 98 KB records (keypoints of both images ride along)
         assert "98 KB records" in d["config"]["workload"] and "configs[3]" in d["config"]["workload"]
+    out = {p.stem: np.load(p) for p in dump.glob("*.npy")}
+    fields = {"epoch", "n_keypoints", "n_matches", "stop_layer", "matches0", "matching_scores0"}
+    assert set(out) == (fields | {"keypoints"} if "--config" in flags else fields)
+    assert all(a.dtype in (np.float32, np.float64) for a in out.values())
+    assert out["epoch"].tolist() == [d["warmup"] + d["steps"] - 1] and out["n_keypoints"].tolist() == [[4096, 4096]]
+    m0, s0 = out["matches0"][0], out["matching_scores0"][0]
+    assert m0.shape == (4096,) and out["n_matches"][0] == (m0 > -1).sum() and ((m0 >= -1) & (m0 < 4096)).all()
+    assert np.isfinite(s0).all() and (s0 >= 0).all() and (s0 <= 1 + 1e-5).all() and (s0[m0 > -1] > 0).all()
+    if "--config" in flags:
+        kp = out["keypoints"]
+        assert kp.shape == (1, 2, 4096, 2) and (kp >= 0).all() and (kp[..., 0] < 1920).all() and (kp[..., 1] < 1080).all()

@@ -351,20 +351,28 @@ def test_sfm_relative_orientation_and_triangulation():
     assert np.abs(Xt[:, :3] - X).max() < 1e-8 and np.abs(Xt[:, 3] - 1).max() == 0
 
 
-def test_bench_gpus2_as_typed_spawns_its_ranks_dry_run():
+def test_bench_gpus2_as_typed_spawns_its_ranks_dry_run(tmp_path):
     """`python bench.py --gpus 2 ...` with no launcher around it: the parent starts one process per rank through
     torch.distributed.run before anything touches a GPU and relays rank 0's JSON line. --dry-run fabricates the records, so
-    spawn, rendezvous (gloo), epoch sharding, the table all-gather and the JSON contract are exercised on a CPU-only machine."""
+    spawn, rendezvous (gloo), epoch sharding, the table all-gather and the JSON contract are exercised on a CPU-only machine.
+    `--dump-outputs` writes the records of the last timed step of both ranks (fabricated: n_matches = epoch) as float .npy files."""
     import json
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
     env["OMP_NUM_THREADS"] = "1"
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2", "--dry-run"],
-                       env=env, capture_output=True, text=True, timeout=300)
+    dump = tmp_path / "outputs"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2", "--dry-run",
+                        "--dump-outputs", str(dump)], env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout
     d = json.loads(lines[0])
     assert d["n_gpus"] == 2 and d["steps"] == 5 and d["warmup"] == 2 and d["dry_run"] is True and d["scaling"] == "weak"
+    out = {p.stem: np.load(p) for p in dump.glob("*.npy")}
+    assert set(out) == {"epoch", "n_keypoints", "n_matches", "stop_layer", "matches0", "matching_scores0"}
+    assert all(a.dtype in (np.float32, np.float64) for a in out.values())
+    # 7 epochs per rank (e = rank mod 2), the first 2 of each warm-up: the last timed step is epoch 12 on rank 0 and 13 on rank 1
+    assert out["epoch"].tolist() == [12, 13] and out["n_matches"].tolist() == [12, 13] and out["n_keypoints"].tolist() == [[4096] * 2] * 2
+    assert out["matches0"].shape == (2, 4096) and out["matching_scores0"].shape == (2, 4096) and out["matching_scores0"].dtype == np.float32
     for k in ("metric", "value", "unit", "ms_per_step", "higher_is_better", "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline"):
         assert k in d, k
     # the N > 1 line is self-verifying: who took part, with how many pairs each, and what the gathered table holds

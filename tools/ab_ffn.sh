@@ -1,7 +1,7 @@
 #!/bin/bash
 # A/B of the fused feed-forward kernel against the separate-launch form (one gpurun call):
 #   gpurun --timeout 1500 -- 'bash tools/ab_ffn.sh'
-root=${GRAFT_REPO_ROOT:-/root/repo}
+root=$(cd "$(dirname "$0")/.." && pwd)
 out=$root/gpurun_out/ab_ffn
 mkdir -p $out
 cd $root

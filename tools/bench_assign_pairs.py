@@ -6,7 +6,7 @@ scores (to compare builds bit for bit: ICEMATCH_LIB selects the library). Round 
     python tools/bench_assign_pairs.py
 """
 import ctypes, json, os, sys, numpy as np, torch
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from icepy4d_amd import synthetic
 from icepy4d_amd.engine import Engine
 eng = Engine(0)

@@ -6,7 +6,7 @@
 # report) and leaves the rehearsal / SuperGlue / per-phase files of the last full collection in place.
 tag=${1:-r05}
 mode=${2:-full}
-root=${GRAFT_REPO_ROOT:-/root/repo}
+root=$(cd "$(dirname "$0")/.." && pwd)
 out=$root/gpurun_out/$tag
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp
