@@ -80,6 +80,8 @@ SIGNATURES = {
     "im_ransac_fundamental": [_P, _P, _P, _I, _I, C.c_double, C.c_uint, _P, _P, _P, _P],
     "im_ransac_essential": [_P, _P, _P, _I, _I, C.c_double, C.c_uint, _P, _P, _P, _P],
     "im_triangulate_linear": [_P, _P, _P, _P, _P, _I, _P, _P],
+    "im_forient": [_P, _P, _I, _I, _I, _I, _P, _P],
+    "im_template_match_oc": [_P, _P, _I, _I, _P, _I, _I, _I, _P, _P, _I, _I, _I, _I, _P, _P],
 }
 
 

@@ -100,6 +100,7 @@ struct im_ctx {
     float* stage_attn_part = nullptr; int* stage_attn_cnt = nullptr; size_t stage_attn_floats = 0, stage_attn_ints = 0;  // im_flash_attn
     unsigned char* stage_attn_planes = nullptr; size_t stage_attn_plane_bytes = 0;                                       // im_flash_attn (attention_bx.hip)
     im::MergeScratch* merge = nullptr;   // scratch of im_merge_tile_matches (tile_merge.hip), grown on demand
+    float* tm_scratch = nullptr; size_t tm_scratch_floats = 0;   // C of a batch of pairs, im_template_match_oc (templatematch.hip), grown on demand
     unsigned long long* clock_buf[2] = {nullptr, nullptr};   // im_debug_clock_probe: per-block (cycles, 100 MHz ticks) of the attention / Winograd BX main loops
     bool clock_armed = false;
     unsigned long long* clock_of(int cls) const { return clock_armed ? clock_buf[cls] : nullptr; }

@@ -1,0 +1,366 @@
+// Feature tracking by template matching with orientation correlation (`src/icepy4d/matching/templatematch.py:160-340`, driven
+// by `utils/track_targets.py`). The reference correlates each template with its search window through complex64 FFTs
+// (`templatematch.py:234-255, 296-301`); what it keeps of the full correlation is the (S - T) x (S - T) block
+//   C[i][j] = sum_{ty, tx < T} Ar[ty][tx] Br[i + ty][j + tx] + Ai[ty][tx] Bi[i + ty][j + tx]
+// (A = template cut from forient(A), B = search window cut from conj(forient(B)) and conjugated again by the product), and
+// that is what is computed here, directly, in fp32 on the vector ALUs: one template per pair makes it a matrix-vector
+// contraction, so there is nothing for the matrix cores to take without multiplying the work.
+//
+//   forient_kernel   one thread per pixel: the 3 x 3 complex filter of `forient` (`:332-340`) and the division by the modulus
+//   tm_corr_kernel   C of a tile of one pair: B rows of the tile and a chunk of template rows / columns staged in LDS (both
+//                    channels in separate planes), each thread a 1 x 16 strip of C slid along the template columns from a
+//                    32-value register window; template rows of a chunk split over `ks` thread groups, summed in a fixed order
+//   tm_peak_kernel   one wave per pair: argmax (first maximum in row-major order), mean |C|, edge test and the sub-pixel
+//                    centroid of `:303-325` with numpy's own summation order for the float32 / float64 sums of the window
+#include <cmath>
+
+#include "common.h"
+#include "ctx.h"
+
+namespace im {
+namespace {
+
+constexpr int TM_DX = 16;                       // C columns per thread
+constexpr int TM_MAX_THREADS = 256;
+constexpr int TM_LDS_FLOATS = 16384;            // 64 KiB of LDS per block: two blocks of 256 threads per CU at least
+
+struct TmPlan {
+    int R;            // S - T: C is R x R
+    int gy, gx, ks;   // rows of C, 16-column strips of C and template-row groups per block
+    int ny, nx;       // tiles of C per pair
+    int kt, kx;       // template rows / columns staged per chunk (kt a multiple of ks, kx a multiple of 16)
+    int pitch;        // floats per staged B row (== 4 mod 16: the 16 lanes of a ds_read_b128 group hit 16 different bank quads)
+    int brows;        // gy + kt - 1
+    int threads;
+    int lds_floats;
+};
+
+int tm_stage_floats(const TmPlan& p) { return 2 * p.brows * p.pitch + 2 * p.kt * p.kx; }
+
+TmPlan tm_plan(int T, int S) {
+    TmPlan p;
+    p.R = S - T;
+    const int R = p.R;
+    auto up = [](int a, int b) { return (a + b - 1) / b * b; };
+    p.gy = R < 16 ? R : (up(R, 32) <= up(R, 16) ? 32 : 16);
+    const int mx = (R + TM_DX - 1) / TM_DX;
+    p.gx = std::min(mx, TM_MAX_THREADS / p.gy);
+    p.nx = (mx + p.gx - 1) / p.gx;
+    p.gx = (mx + p.nx - 1) / p.nx;
+    p.ny = (R + p.gy - 1) / p.gy;
+    p.ks = std::max(1, std::min(TM_MAX_THREADS / (p.gy * p.gx), T));
+    p.kx = std::min(up(T, 16), 128);
+    auto set_rows = [&](int kt) { p.kt = kt; p.brows = p.gy + kt - 1; p.pitch = TM_DX * p.gx + p.kx + 4; };
+    set_rows(p.ks);
+    while (tm_stage_floats(p) > TM_LDS_FLOATS && p.ks > 1) { p.ks /= 2; set_rows(p.ks); }
+    while (tm_stage_floats(p) > TM_LDS_FLOATS && p.kx > 16) { p.kx -= 16; set_rows(p.ks); }
+    // as many template rows per chunk as fit, in chunks of equal size
+    int kt_max = p.ks;
+    for (int kt = 2 * p.ks; kt <= up(T, p.ks); kt += p.ks) {
+        set_rows(kt);
+        if (tm_stage_floats(p) > TM_LDS_FLOATS) break;
+        kt_max = kt;
+    }
+    const int nchunks = (T + kt_max - 1) / kt_max;
+    set_rows(up((T + nchunks - 1) / nchunks, p.ks));
+    p.threads = up(p.gy * p.gx * p.ks, IM_WAVE);
+    p.lds_floats = std::max(tm_stage_floats(p), p.ks > 1 ? p.threads * TM_DX : 0);
+    return p;
+}
+
+// Window of one pair (`templatematch.py:268-294`). `valid` = the reference correlates this pair.
+struct PairWin {
+    bool valid;
+    long arow, acol, brow, bcol;
+    double pu, pv, initdu, initdv;
+};
+
+__device__ PairWin pair_window(const double* __restrict__ pairs, const int32_t* __restrict__ bidx, int n_b, long i, int T, int S, int ha,
+                               int wa, int hb, int wb) {
+    const double u = pairs[4 * i], v = pairs[4 * i + 1], idu = pairs[4 * i + 2], idv = pairs[4 * i + 3];
+    PairWin w;
+    w.valid = false;
+    w.arow = w.acol = w.brow = w.bcol = 0;
+    w.initdu = w.initdv = NAN;
+    w.pu = u;   // `:264-265`: a NaN u is skipped before anything is written back
+    w.pv = v;
+    if (isnan(u)) return w;
+    const double th = (T & 1) ? 0.5 : 0.0, sh = (S & 1) ? 0.5 : 0.0;   // T / 2 % 1, S / 2 % 1
+    const double acx = rint(u) - th, acy = rint(v) - th;                 // np.round: half to even, as rint
+    const double bcx = rint(u + idu) - sh, bcy = rint(v + idv) - sh;
+    w.pu = acx;
+    w.pv = acy;
+    w.initdu = bcx - acx;
+    w.initdv = bcy - acy;
+    if (isnan(u + v)) return w;
+    // `.astype(int)` truncates toward zero; the reference skips a lower bound < 0 or an upper bound >= the image size
+    const double b0 = trunc(bcy - S / 2.0), b1 = trunc(bcy + S / 2.0), c0 = trunc(bcx - S / 2.0), c1 = trunc(bcx + S / 2.0);
+    const double a0 = trunc(acy - T / 2.0), a1 = trunc(acy + T / 2.0), d0 = trunc(acx - T / 2.0), d1 = trunc(acx + T / 2.0);
+    if (!(b0 >= 0) || !(a0 >= 0) || !(c0 >= 0) || !(d0 >= 0)) return w;
+    if (!(b1 < hb) || !(a1 < ha) || !(c1 < wb) || !(d1 < wa)) return w;
+    w.valid = (unsigned)bidx[i] < (unsigned)n_b;      // a B-image index out of range leaves the pair's outputs NaN
+    w.brow = (long)b0; w.bcol = (long)c0; w.arow = (long)a0; w.acol = (long)d0;
+    return w;
+}
+
+// r = convolve2d(img, [[1, 0, i], [0, 0, 0], [-i, 0, -1]], "same"): Re = img[y+1][x+1] - img[y-1][x-1], Im = img[y+1][x-1] - img[y-1][x+1]
+__global__ __launch_bounds__(256) void forient_kernel(const void* __restrict__ img, int dtype, int h, int w, float2* __restrict__ out) {
+    const long n = blockIdx.y;
+    const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.z;
+    if (x >= w) return;
+    const long base = n * (long)h * w;
+    auto at = [&](int yy, int xx) -> float {
+        if (yy < 0 || yy >= h || xx < 0 || xx >= w) return 0.f;          // convolve2d(mode="same"): zero padding
+        const long k = base + (long)yy * w + xx;
+        return dtype == 0 ? (float)static_cast<const uint8_t*>(img)[k] : static_cast<const float*>(img)[k];
+    };
+    const float re = at(y + 1, x + 1) - at(y - 1, x - 1);
+    const float im = at(y + 1, x - 1) - at(y - 1, x + 1);
+    const double m = sqrt((double)re * re + (double)im * im);           // np.abs; a modulus of 0 is set to 1
+    out[base + (long)y * w + x] = m == 0.0 ? make_float2(re, im) : make_float2((float)(re / m), (float)(im / m));
+}
+
+__global__ __launch_bounds__(TM_MAX_THREADS) void tm_corr_kernel(const float2* __restrict__ A, int ha, int wa, const float2* __restrict__ B,
+                                                                int hb, int wb, const double* __restrict__ pairs,
+                                                                const int32_t* __restrict__ bidx, int n_b, long pair0, int T, int S, float isign,
+                                                                TmPlan p, float* __restrict__ C) {
+    extern __shared__ float lds[];
+    const int tiles = p.ny * p.nx;
+    const long pl = blockIdx.x / tiles;
+    const int tile = blockIdx.x - (int)(pl * tiles);
+    const PairWin w = pair_window(pairs, bidx, n_b, pair0 + pl, T, S, ha, wa, hb, wb);
+    if (!w.valid) return;
+    const int oy0 = (tile / p.nx) * p.gy, ox0 = (tile % p.nx) * p.gx * TM_DX;
+    const int tid = threadIdx.x;
+    const int y = tid % p.gy, x = (tid / p.gy) % p.gx, k = tid / (p.gy * p.gx);
+    const bool active = k < p.ks;
+    float* sBr = lds;
+    float* sBi = sBr + p.brows * p.pitch;
+    float* sAr = sBi + p.brows * p.pitch;
+    float* sAi = sAr + p.kt * p.kx;
+    const float2* Bimg = B + (long)bidx[pair0 + pl] * hb * wb;
+    float acc[TM_DX];
+#pragma unroll
+    for (int q = 0; q < TM_DX; ++q) acc[q] = 0.f;
+
+    for (int cy = 0; cy < T; cy += p.kt) {
+        for (int cx = 0; cx < T; cx += p.kx) {
+            __syncthreads();
+            // B rows oy0 + cy + r and columns ox0 + cx + c of the search window; zero outside it
+            for (int e = tid; e < p.brows * p.pitch; e += blockDim.x) {
+                const int r = e / p.pitch, c = e - r * p.pitch;
+                const int sy = oy0 + cy + r, sx = ox0 + cx + c;
+                float2 b = make_float2(0.f, 0.f);
+                if (sy < S && sx < S) b = Bimg[(w.brow + sy) * wb + w.bcol + sx];
+                sBr[e] = b.x;
+                sBi[e] = b.y;
+            }
+            // template rows cy + r, columns cx + c; zero outside T x T
+            for (int e = tid; e < p.kt * p.kx; e += blockDim.x) {
+                const int r = e / p.kx, c = e - r * p.kx;
+                float2 a = make_float2(0.f, 0.f);
+                if (cy + r < T && cx + c < T) a = A[(w.arow + cy + r) * wa + w.acol + cx + c];
+                sAr[e] = a.x;
+                sAi[e] = isign * a.y;
+            }
+            __syncthreads();
+            if (!active) continue;
+            for (int r = k; r < p.kt; r += p.ks) {
+#pragma unroll
+                for (int ch = 0; ch < 2; ++ch) {
+                    const float* brow = (ch ? sBi : sBr) + (y + r) * p.pitch + TM_DX * x;
+                    const float* arow = (ch ? sAi : sAr) + r * p.kx;
+                    f32x4 win[8];
+#pragma unroll
+                    for (int v = 0; v < 4; ++v) win[v] = *reinterpret_cast<const f32x4*>(brow + 4 * v);
+                    for (int t0 = 0; t0 < p.kx; t0 += 16) {
+#pragma unroll
+                        for (int v = 0; v < 4; ++v) win[4 + v] = *reinterpret_cast<const f32x4*>(brow + t0 + 16 + 4 * v);
+                        f32x4 a4[4];
+#pragma unroll
+                        for (int v = 0; v < 4; ++v) a4[v] = *reinterpret_cast<const f32x4*>(arow + t0 + 4 * v);
+#pragma unroll
+                        for (int tt = 0; tt < 16; ++tt) {
+                            const float a = a4[tt >> 2][tt & 3];
+#pragma unroll
+                            for (int q = 0; q < TM_DX; ++q) acc[q] = fmaf(a, win[(q + tt) >> 2][(q + tt) & 3], acc[q]);
+                        }
+#pragma unroll
+                        for (int v = 0; v < 4; ++v) win[v] = win[4 + v];
+                    }
+                }
+            }
+        }
+    }
+
+    float* Cp = C + pl * (long)p.R * p.R;
+    if (p.ks == 1) {
+        if (!active) return;
+        const int i = oy0 + y;
+#pragma unroll
+        for (int q = 0; q < TM_DX; ++q) {
+            const int j = ox0 + TM_DX * x + q;
+            if (i < p.R && j < p.R) Cp[i * p.R + j] = acc[q];
+        }
+        return;
+    }
+    // the ks partial sums of every output, added in group order
+    __syncthreads();
+    const int per = p.gy * p.gx * TM_DX;
+    if (active) {
+#pragma unroll
+        for (int q = 0; q < TM_DX; ++q) lds[k * per + (x * p.gy + y) * TM_DX + q] = acc[q];
+    }
+    __syncthreads();
+    for (int o = tid; o < per; o += blockDim.x) {
+        float s = lds[o];
+        for (int kk = 1; kk < p.ks; ++kk) s += lds[kk * per + o];
+        const int q = o % TM_DX, yx = o / TM_DX, yy = yx % p.gy, xx = yx / p.gy;
+        const int i = oy0 + yy, j = ox0 + TM_DX * xx + q;
+        if (i < p.R && j < p.R) Cp[i * p.R + j] = s;
+    }
+}
+
+// numpy's pairwise summation of n <= 128 values (`pairwise_sum` of umath loops), started from the reduction identity 0
+template <typename T, typename F>
+__device__ T np_sum_small(int n, F get) {
+    if (n < 8) {
+        T r = 0;
+        for (int i = 0; i < n; ++i) r += get(i);
+        return (T)0 + r;
+    }
+    T r[8];
+    for (int j = 0; j < 8; ++j) r[j] = get(j);
+    int i = 8;
+    for (; i < n - n % 8; i += 8)
+        for (int j = 0; j < 8; ++j) r[j] += get(i + j);
+    T res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
+    for (; i < n; ++i) res += get(i);
+    return (T)0 + res;
+}
+
+// one wave per pair: `templatematch.py:303-329`
+__global__ __launch_bounds__(256) void tm_peak_kernel(const double* __restrict__ pairs, const int32_t* __restrict__ bidx, int n_b, long pair0, long n_batch, int T, int S, int ha, int wa,
+                                                      int hb, int wb, const float* __restrict__ C, long n_pairs, double* __restrict__ out) {
+    const long pl = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (pl >= n_batch) return;
+    const long pi = pair0 + pl;
+    const PairWin w = pair_window(pairs, bidx, n_b, pi, T, S, ha, wa, hb, wb);
+    double* o_pu = out;
+    double* o_pv = out + n_pairs;
+    double* o_du = out + 2 * n_pairs;
+    double* o_dv = out + 3 * n_pairs;
+    double* o_pk = out + 4 * n_pairs;
+    double* o_mc = out + 5 * n_pairs;
+    if (lane == 0) {
+        o_pu[pi] = w.pu; o_pv[pi] = w.pv;
+        o_du[pi] = NAN; o_dv[pi] = NAN; o_pk[pi] = NAN; o_mc[pi] = NAN;
+    }
+    if (!w.valid) return;
+    const int R = S - T, n = R * R;
+    const float* Cp = C + pl * (long)n;
+    float best = -INFINITY;
+    int bi = n;
+    double sabs = 0.0;
+    for (int e = lane; e < n; e += 64) {
+        const float c = Cp[e];
+        if (c > best || bi == n) { best = c; bi = e; }
+        sabs += fabs((double)c);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float ob = __shfl_xor(best, o);
+        const int oi = __shfl_xor(bi, o);
+        if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
+        sabs += __shfl_xor(sabs, o);
+    }
+    if (lane != 0) return;
+    o_mc[pi] = (double)(float)(sabs / n);     // np.mean of a float32 array is a float32
+    const int mi = bi / R, mj = bi - mi * R;
+    const int edge = min(min(mi, mj), min(R - 1 - mi, R - 1 - mj));
+    if (edge == 0) return;                    // a peak on the border of C is not trusted
+    const int ww = min(edge, 4), side = 2 * ww + 1, m = side * side;
+    auto cw = [&](int e) { return Cp[(mi - ww + e / side) * R + mj - ww + e % side]; };
+    const float mean_abs = np_sum_small<float>(m, [&](int e) { return fabsf(cw(e)); }) / (float)m;
+    auto cpos = [&](int e) { const float c = cw(e) - mean_abs; return c < 0.f ? 0.f : c; };
+    const float tot = np_sum_small<float>(m, cpos);
+    const double wkeep = R / 2.0;             // C_uu = C_vv = arange(-wkeep, wkeep + 1)
+    const double cv = np_sum_small<double>(m, [&](int e) { return (-wkeep + (mi - ww + e / side)) * (double)(cpos(e) / tot); });
+    const double cu = np_sum_small<double>(m, [&](int e) { return (-wkeep + (mj - ww + e % side)) * (double)(cpos(e) / tot); });
+    o_du[pi] = cu + w.initdu;
+    o_dv[pi] = cv + w.initdv;
+    o_pk[pi] = (double)best;
+}
+
+hipError_t launch_forient(const void* img, int dtype, int n, int h, int w, float* out, hipStream_t s) {
+    hipLaunchKernelGGL(forient_kernel, dim3((w + 255) / 256, n, h), dim3(256), 0, s, img, dtype, h, w, reinterpret_cast<float2*>(out));
+    return hipGetLastError();
+}
+
+hipError_t launch_corr(const TmPlan& p, long blocks, const float2* A, int ha, int wa, const float2* B, int hb, int wb, const double* pairs,
+                       const int32_t* bidx, int n_b, long pair0, int T, int S, float isign, float* C, hipStream_t s) {
+    hipLaunchKernelGGL(tm_corr_kernel, dim3((unsigned)blocks), dim3(p.threads), p.lds_floats * sizeof(float), s, A, ha, wa, B, hb, wb, pairs,
+                       bidx, n_b, pair0, T, S, isign, p, C);
+    return hipGetLastError();
+}
+
+hipError_t launch_peak(const double* pairs, const int32_t* bidx, int n_b, long pair0, long nb, int T, int S, int ha, int wa, int hb, int wb,
+                       const float* C, long n_pairs, double* out, hipStream_t s) {
+    hipLaunchKernelGGL(tm_peak_kernel, dim3((unsigned)((nb + 3) / 4)), dim3(256), 0, s, pairs, bidx, n_b, pair0, nb, T, S, ha, wa, hb, wb, C,
+                       n_pairs, out);
+    return hipGetLastError();
+}
+
+}  // namespace
+}  // namespace im
+
+using namespace im;
+
+extern "C" int im_forient(im_ctx* ctx, const void* d_img, int dtype, int n_images, int h, int w, float* d_out, void* stream) {
+    IM_CHECK_CTX(ctx);
+    if (!d_img || !d_out || (dtype != 0 && dtype != 1) || n_images < 0 || h < 0 || w < 0 || n_images > 65535 || h > 65535)
+        return ctx->fail(-72, "im_forient: bad arguments");
+    if (!n_images || !h || !w) return 0;
+    hipStream_t s = (hipStream_t)stream;
+    IM_LAUNCH(ctx, "forient", s, launch_forient(d_img, dtype, n_images, h, w, d_out, s));
+    IM_GUARD_CHECK(ctx, s, "im_forient");
+    return 0;
+}
+
+extern "C" int im_template_match_oc(im_ctx* ctx, const float* d_a, int ha, int wa, const float* d_b, int n_b, int hb, int wb,
+                                    const double* d_pairs, const int32_t* d_bidx, int n_pairs, int T, int S, int conj_b,
+                                    double* d_out, void* stream) {
+    IM_CHECK_CTX(ctx);
+    if (!d_a || !d_b || !d_pairs || !d_bidx || !d_out || n_pairs < 0 || n_b < 1 || ha < 0 || wa < 0 || hb < 0 || wb < 0)
+        return ctx->fail(-72, "im_template_match_oc: bad arguments");
+    if (T < 1 || S <= T) return ctx->fail(-72, "im_template_match_oc: need 1 <= template width < search width (got %d, %d)", T, S);
+    if (!n_pairs) return 0;
+    hipStream_t s = (hipStream_t)stream;
+    const TmPlan p = tm_plan(T, S);
+    const long per_pair = (long)p.R * p.R;
+    // C of one batch of pairs lives in a scratch buffer of at most 64 Mi floats (grown on demand)
+    const long batch = std::max(1L, std::min((long)n_pairs, (64L << 20) / per_pair));
+    const size_t need = (size_t)(batch * per_pair);
+    if (ctx->tm_scratch_floats < need) {
+        if (ctx->tm_scratch) {
+            IM_HIP(ctx, hipStreamSynchronize(s));
+            ctx->dfree(ctx->tm_scratch);
+        }
+        ctx->tm_scratch = ctx->dalloc<float>(need, "templatematch.C");
+        ctx->tm_scratch_floats = ctx->tm_scratch ? need : 0;
+        if (!ctx->tm_scratch) return ctx->fail(-71, "im_template_match_oc: out of device memory (%zu floats)", need);
+    }
+    const float2* A = reinterpret_cast<const float2*>(d_a);
+    const float2* B = reinterpret_cast<const float2*>(d_b);
+    const float isign = conj_b ? 1.f : -1.f;
+    for (long p0 = 0; p0 < n_pairs; p0 += batch) {
+        const long nb = std::min(batch, (long)n_pairs - p0);
+        const long blocks = nb * p.ny * p.nx;
+        if (blocks > 0x7fffffffL) return ctx->fail(-72, "im_template_match_oc: too many pairs per launch");
+        IM_LAUNCH(ctx, "tm_corr", s, launch_corr(p, blocks, A, ha, wa, B, hb, wb, d_pairs, d_bidx, n_b, p0, T, S, isign, ctx->tm_scratch, s));
+        IM_LAUNCH(ctx, "tm_peak", s, launch_peak(d_pairs, d_bidx, n_b, p0, nb, T, S, ha, wa, hb, wb, ctx->tm_scratch, (long)n_pairs, d_out, s));
+    }
+    IM_GUARD_CHECK(ctx, s, "im_template_match_oc");
+    return 0;
+}

@@ -213,4 +213,6 @@ void im_ctx::free_all() {
     d_guard_blocks = nullptr; d_guard_flag = nullptr; guard_table_cap = 0;
     delete merge;
     merge = nullptr;
+    tm_scratch = nullptr;
+    tm_scratch_floats = 0;
 }

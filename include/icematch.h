@@ -234,6 +234,19 @@ int im_ransac_essential(im_ctx* ctx, const float* d_x0, const float* d_x1, int n
 int im_triangulate_linear(im_ctx* ctx, const double* h_P0, const double* h_P1, const double* d_x0, const double* d_x1, int n,
                           double* d_X, void* stream);
 
+/* ---- template matching: orientation correlation (`src/icepy4d/matching/templatematch.py`) ---------------------------------
+ * im_forient replaces `forient` (`templatematch.py:332-340`): d_img [n_images][h][w] of dtype 0 = uint8, 1 = float32; d_out
+ * [n_images][h][w] float2 (re, im) = the 3 x 3 complex gradient with zero padding, divided by its modulus (0 -> 1). Enqueue only. */
+int im_forient(im_ctx* ctx, const void* d_img, int dtype, int n_images, int h, int w, float* d_out, void* stream);
+/* Replaces the per-point loop of `OC` (`templatematch.py:258-329`) for many (point, B image) pairs against ONE A map in one call.
+ *   d_a [ha][wa] float2: orientation map of A;  d_b [n_b][hb][wb] float2: orientation maps of the B images
+ *   d_pairs [n_pairs][4] double: u, v, initialdu, initialdv;  d_bidx [n_pairs] int32: the B image of every pair
+ *   T, S: template / search width (1 <= T < S);  conj_b: the reference's `B = np.conj(B)` was applied (1) or not (0)
+ *   d_out [6][n_pairs] double: pu, pv (the centres used), du, dv, peakCorr, meanAbsCorr; NaN wherever the reference leaves NaN.
+ * C = Re(corr(A window, conj B window)) over the (S - T)^2 valid offsets is computed directly in fp32. Enqueue only. */
+int im_template_match_oc(im_ctx* ctx, const float* d_a, int ha, int wa, const float* d_b, int n_b, int hb, int wb, const double* d_pairs,
+                         const int32_t* d_bidx, int n_pairs, int T, int S, int conj_b, double* d_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
