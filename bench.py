@@ -12,11 +12,15 @@
     rank by default), 98 KB records that carry the keypoints of both images, one RCCL all-gather of the tables at the
     end. A pool of --pool distinct synthetic pairs per rank is cycled (host synthesis of 2048 pairs would take minutes).
 --config 5 (configs[4], not the headline): one step = one 3000x4000 pair, 16384 keypoints, SuperPoint (nms 3) + SuperGlue
-    (18 layers, 20 Sinkhorn iterations); roofline objects for the Sinkhorn sweeps (HBM) and the attention kernel (MFMA).
+    (18 layers, 20 Sinkhorn iterations); with --full, roofline objects for the Sinkhorn sweeps (HBM) and the attention kernel (MFMA).
 Every rank processes its own steps (weak scaling, epochs sharded round-robin); the timed region ends with the job's single
 collective, one all-gather of the per-rank match tables (RCCL). Prints ONE JSON line on rank 0.
 --steps K: the timed region is exactly K steps; `ms_per_step` is its time / K.
 --dump-outputs DIR: after the timed region, the last timed step's match-table records as DIR/<name>.npy (`dump_outputs`).
+--full: after the timed region, also what the headline does not need (rank 0): the per-launch roofline pass (`roofline*`,
+    `kernel_ms_per_pair`, the pair-level utilisation figures), the default line's `side_measurements` (other configurations, launch
+    modes and calls, each in runs of its own) and the oracle's `cpu_baseline` (over a minute of CPU work). Without it a run sets up,
+    warms up, times its steps, writes its outputs and prints the line: the same headline, the same timed steps.
 --dry-run: no GPU work at all (fabricated records): exercises spawn, rendezvous (gloo), sharding, the table all-gather and the
     JSON contract on a CPU-only machine (tests/test_host_cpu.py).
 """
@@ -155,7 +159,9 @@ def main():
     ap.add_argument("--steps", type=int, default=None)
     ap.add_argument("--warmup", type=int, default=None)
     ap.add_argument("--config", type=int, default=2, choices=(2, 3, 4, 5))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline does not need: roofline pass, side measurements, "
+                                                        "CPU baseline (see the module docstring)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--pool", type=int, default=None, help="configs 2 / 4: distinct synthetic pairs per rank (cycled; default 4 / 32)")
     ap.add_argument("--pairs", default="stereo", choices=("stereo", "translated"),
                     help="stereo = SURVEY §8d homography-warped pair (seeded weights find almost no matches on it: full-depth worst "
@@ -164,7 +170,7 @@ def main():
     ap.add_argument("--streams", type=int, default=2, help="launch groups in flight per GPU (independent contexts on separate HIP streams)")
     ap.add_argument("--batch", type=int, default=DEFAULT_PAIRS_PER_LAUNCH,
                     help="pairs per launch (batch dimension over pairs inside the kernels); see DEFAULT_PAIRS_PER_LAUNCH for the measured sweep")
-    ap.add_argument("--no-side-measurements", action="store_true", help="skip the short untimed-side runs (other launch mode, translated pairs)")
+    ap.add_argument("--no-side-measurements", action="store_true", help="with --full: skip the short untimed-side runs (other launch mode, translated pairs)")
     ap.add_argument("--dry-run", action="store_true", help="no GPU work: spawn / rendezvous / sharding / gather / JSON only")
     ap.add_argument("--fail-epochs", default="", help="test hook for the failure isolation of the sharded driver: comma-separated epochs whose "
                     "input pair is replaced by an array of the wrong shape; their records come out as n_matches = -1, the rank goes on, "
@@ -211,9 +217,9 @@ def main():
     epochs = shard_epochs(total * world, rank, world)           # this rank's epochs: e = rank (mod world)
     cfg5 = args.config == 5
     h, w, kpts = (H5, W5, KPTS5) if cfg5 else (H, W, KPTS)
-    # side measurements of the default line (rank 0 of a one-rank run, headline config only): their inputs are synthesised here too,
-    # BEFORE the GPU is initialised (forked workers)
-    side_on = world == 1 and args.config == 2 and not args.no_side_measurements and not args.dry_run
+    # side measurements of the default line (--full, rank 0 of a one-rank run, headline config only): their inputs are synthesised here
+    # too, BEFORE the GPU is initialised (forked workers)
+    side_on = args.full and world == 1 and args.config == 2 and not args.no_side_measurements and not args.dry_run
     side_inputs = {}
     if args.dry_run:
         host_pairs = []
@@ -386,7 +392,7 @@ def main():
                    "mean_keypoints": n0, "mean_matches": nm},
         "host_enqueue_ms_per_step": 1e3 * t_enq / args.steps, "untimed_pairs_before_timing": warm_pairs,
         "all_gather_ms": 1e3 * t_gather,
-        "failed_epochs": failed_epochs,
+        "failed_epochs": failed_epochs, "full": args.full,
     }
     if failed_epochs:
         result["failed_epochs_note"] = (f"{len(failed_epochs)} of the {n_pairs} timed pairs have a record with n_matches = -1 (this rank's own: "
@@ -453,7 +459,7 @@ def main():
         result["side_measurements"]["production_call_ms"] = production_call_side(local_rank, sp_sd, m_sd)
         result["side_measurements"]["seconds_spent"] = round(time.perf_counter() - t_side, 1)
 
-    if rank == 0:
+    if rank == 0 and args.full:
         # ---- roofline of the dominant kernel: HIP events around every launch (library-side, on the launch stream); during the same isolated pass the
         # two matrix-core kernel classes report the shader clock they hold inside their main loops (im_debug_clock_probe: cycles / 100 MHz reference ticks)
         prof_steps = 1 if cfg5 else 4
@@ -585,6 +591,7 @@ def main():
         # ---- CPU baseline: the oracle (torch-CPU fp32 restatement of the reference path) on this box's host cores
         if world == 1 and not args.no_cpu_baseline and not cfg5:
             result["cpu_baseline"] = cpu_baseline(epochs)
+    if rank == 0:
         emit(json.dumps(result))
     if world > 1 or force_dist:
         dist.barrier()

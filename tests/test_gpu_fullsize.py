@@ -159,30 +159,34 @@ def test_config3_timed_launch_mode_equals_direct_launches_and_the_oracle():
     e.close()
 
 
-@pytest.mark.parametrize("flags", [["--steps", "5", "--warmup", "3"], ["--steps", "2", "--warmup", "0"],
-                                   ["--steps", "4", "--warmup", "2", "--config", "4", "--pool", "2"],
-                                   ["--steps", "10", "--warmup", "2", "SIDE"]])
-def test_bench_line_with_odd_step_counts(flags, tmp_path):
-    """`python bench.py --gpus 1 --steps K --warmup W` as the round driver types it, with counts that do not fill the launch
-    groups (ten pairs each by default): one JSON line with the contract fields, every step recorded, a throughput in the range of the device
-    (an odd warm-up once left a parked pair behind and shifted every timed group: 93 instead of 102 pairs/s at K = 20, W = 5).
-    `--dump-outputs`: the record of the last timed step (epoch W + K - 1) as float .npy files, consistent in itself."""
+def run_bench(flags, dump):
+    """`python bench.py --gpus 1 *flags --dump-outputs dump` in a fresh process: exit 0 and ONE JSON line on stdout, returned parsed."""
     import json
     import os
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
-    side = "SIDE" in flags                  # the default line's side measurements (configs[2] / configs[4] / one match() call) ride along
-    flags = [f for f in flags if f != "SIDE"]
-    dump = tmp_path / "outputs"
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", *flags, "--no-cpu-baseline",
-                        *([] if side else ["--no-side-measurements"]), "--dump-outputs", str(dump)],
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", *flags, "--dump-outputs", str(dump)],
                        env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout
-    d = json.loads(lines[0])
+    return json.loads(lines[0])
+
+
+@pytest.mark.parametrize("flags", [["--steps", "5", "--warmup", "3"], ["--steps", "2", "--warmup", "0"],
+                                   ["--steps", "4", "--warmup", "2", "--config", "4", "--pool", "2"],
+                                   ["--steps", "10", "--warmup", "2", "SIDE"]])
+def test_bench_line_with_odd_step_counts(flags, tmp_path):
+    """`python bench.py --gpus 1 --steps K --warmup W --full`, with counts that do not fill the launch
+    groups (ten pairs each by default): one JSON line with the contract fields, every step recorded, a throughput in the range of the device
+    (an odd warm-up once left a parked pair behind and shifted every timed group: 93 instead of 102 pairs/s at K = 20, W = 5).
+    `--dump-outputs`: the record of the last timed step (epoch W + K - 1) as float .npy files, consistent in itself."""
+    side = "SIDE" in flags                  # the default line's side measurements (configs[2] / configs[4] / one match() call) ride along
+    flags = [f for f in flags if f != "SIDE"]
+    dump = tmp_path / "outputs"
+    d = run_bench([*flags, "--full", "--no-cpu-baseline", *([] if side else ["--no-side-measurements"])], dump)
     assert d["n_gpus"] == 1 and d["steps"] == int(flags[1]) and d["warmup"] == int(flags[3]) and d["unit"] == "pairs/s"
     assert d["config"]["mean_keypoints"] == 4096 and d["roofline"]["bound"] == "mfma" and 0.2 < d["roofline"]["frac"] < 1.0
     assert d["value"] > 5.0, d["value"]      # a sanity bound, not a performance threshold (a cold or shared device is slower)
@@ -208,3 +212,26 @@ def test_bench_line_with_odd_step_counts(flags, tmp_path):
     if "--config" in flags:
         kp = out["keypoints"]
         assert kp.shape == (1, 2, 4096, 2) and (kp >= 0).all() and (kp[..., 0] < 1920).all() and (kp[..., 1] < 1080).all()
+
+
+def test_bench_plain_line_is_lean_and_dumps_what_full_dumps(tmp_path):
+    """Without --full a run does only what its headline needs: the contract fields, the same timed steps, and none of the runs of
+    their own that --full adds (roofline pass, side measurements, CPU baseline). The records of its last timed step equal, bit for
+    bit, those of the same run with --full, and so does everything the two lines derive from the timed records."""
+    flags = ["--steps", "5", "--warmup", "3"]
+    plain = run_bench(flags, tmp_path / "plain")
+    full = run_bench([*flags, "--full", "--no-cpu-baseline", "--no-side-measurements"], tmp_path / "full")
+    assert plain["full"] is False and full["full"] is True
+    for k in ("metric", "unit", "higher_is_better", "dtype", "dtype_note", "n_gpus", "steps", "warmup", "config", "failed_epochs"):
+        assert plain[k] == full[k], k
+    assert plain["steps"] == 5 and plain["warmup"] == 3 and plain["unit"] == "pairs/s" and plain["dtype"] == "f32"
+    assert plain["value"] > 5.0 and abs(plain["value"] - 1e3 / plain["ms_per_step"]) < 1e-6 * plain["value"]
+    extras = {"roofline", "roofline_attention", "roofline_convolutions", "kernel_ms_per_pair", "pair_matrix_pipe_time_at_peak_frac",
+              "side_measurements", "cpu_baseline"}
+    assert not extras & set(plain), extras & set(plain)
+    assert full["roofline"]["bound"] == "mfma" and "kernel_ms_per_pair" in full
+    a = {p.stem: np.load(p) for p in (tmp_path / "plain").glob("*.npy")}
+    b = {p.stem: np.load(p) for p in (tmp_path / "full").glob("*.npy")}
+    assert set(a) == set(b) == {"epoch", "n_keypoints", "n_matches", "stop_layer", "matches0", "matching_scores0"}
+    for name in a:
+        assert a[name].dtype == b[name].dtype and np.array_equal(a[name], b[name]), name

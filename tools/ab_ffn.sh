@@ -9,7 +9,7 @@ python3 -m pytest tests -q -x -m gpu > $out/pytest.log 2>&1
 tail -3 $out/pytest.log
 for mode in fused unfused; do
   if [ $mode = unfused ]; then export IM_FFN_UNFUSED=1; else unset IM_FFN_UNFUSED; fi
-  python3 bench.py --config 5 --no-cpu-baseline > $out/bench5_$mode.json 2> $out/bench5_$mode.err
+  python3 bench.py --config 5 --full --no-cpu-baseline > $out/bench5_$mode.json 2> $out/bench5_$mode.err
   python3 - <<PY
 import json
 b = json.load(open("$out/bench5_$mode.json"))
