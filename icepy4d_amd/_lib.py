@@ -39,6 +39,8 @@ class SuperGlueConf(C.Structure):
 _P = C.c_void_p
 _I = C.c_int
 _F = C.c_float
+_D = C.c_double
+_L = C.c_longlong
 
 # name -> argtypes; every symbol declared in include/icematch.h
 SIGNATURES = {
@@ -82,6 +84,10 @@ SIGNATURES = {
     "im_triangulate_linear": [_P, _P, _P, _P, _P, _I, _P, _P],
     "im_forient": [_P, _P, _I, _I, _I, _I, _P, _P],
     "im_template_match_oc": [_P, _P, _I, _I, _P, _I, _I, _I, _P, _P, _I, _I, _I, _I, _P, _P],
+    "im_dsm_round": [_P, _P, _L, _F, _P, _P, _P, _P, _P, _P],
+    "im_dsm_group_mean": [_P, _P, _P, _P, _P, _P, _P, _L, _P, _P, _P, _P, _P],
+    "im_dsm_rasterize": [_P, _P, _P, _P, _P, _P, _L, _P, _P, _I, _P, _I, _D, _D, _D, _D, _D, _P, _P],
+    "im_project_colors": [_P, _P, _L, _L, _P, _L, _L, _P, _L, _L, _I, _I, _I, _P, _P, _I, _I, _I, _P, _I, _P, _P, _P, _P],
 }
 
 

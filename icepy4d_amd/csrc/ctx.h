@@ -101,6 +101,7 @@ struct im_ctx {
     unsigned char* stage_attn_planes = nullptr; size_t stage_attn_plane_bytes = 0;                                       // im_flash_attn (attention_bx.hip)
     im::MergeScratch* merge = nullptr;   // scratch of im_merge_tile_matches (tile_merge.hip), grown on demand
     float* tm_scratch = nullptr; size_t tm_scratch_floats = 0;   // C of a batch of pairs, im_template_match_oc (templatematch.hip), grown on demand
+    char* dsm_scratch = nullptr; size_t dsm_scratch_bytes = 0;    // scans, group starts, per-cell triangle of the DSM calls (dsm.hip), grown on demand
     unsigned long long* clock_buf[2] = {nullptr, nullptr};   // im_debug_clock_probe: per-block (cycles, 100 MHz ticks) of the attention / Winograd BX main loops
     bool clock_armed = false;
     unsigned long long* clock_of(int cls) const { return clock_armed ? clock_buf[cls] : nullptr; }

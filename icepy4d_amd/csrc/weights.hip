@@ -215,4 +215,6 @@ void im_ctx::free_all() {
     merge = nullptr;
     tm_scratch = nullptr;
     tm_scratch_floats = 0;
+    dsm_scratch = nullptr;
+    dsm_scratch_bytes = 0;
 }

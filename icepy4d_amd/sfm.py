@@ -254,3 +254,87 @@ def estimate_pose(kpts0: np.ndarray, kpts1: np.ndarray, K0: np.ndarray, K1: np.n
     inliers = mask.copy()
     inliers[np.flatnonzero(mask)[~front]] = False
     return R, t, inliers
+
+
+# ---- projection and point colours (`sfm/geometry.py:79-100`, `sfm/interpolate_colors.py:13-92`): csrc/dsm.hip `im_project_colors`
+def _engine(engine):
+    if engine is not None:
+        return engine
+    from .matching.matchers import get_engine
+    return get_engine(0)
+
+
+def _camera_params(camera) -> np.ndarray:
+    """[28] float64 for `im_project_colors`: fx, fy, cx, cy, R (row-major), t, k1 k2 p1 p2 k3 k4 k5 k6 s1..s4. Reads only `.K`, `.dist`,
+    `.R` and `.t`, as the reference does. Distortion vectors of length 0, 4, 5 or 8 (OpenCV's forms without thin prism / tilt terms)."""
+    K = np.asarray(camera.K, np.float64).reshape(3, 3)
+    R = np.asarray(camera.R, np.float64).reshape(9)
+    t = np.asarray(camera.t, np.float64).reshape(3)
+    dist = np.zeros(0) if camera.dist is None else np.asarray(camera.dist, np.float64).ravel()
+    if len(dist) not in (0, 4, 5, 8):
+        raise ValueError(f"project_points: distortion vectors of length 0, 4, 5 or 8 are supported (got {len(dist)})")
+    k = np.zeros(12)
+    k[:len(dist)] = dist
+    return np.ascontiguousarray(np.concatenate([[K[0, 0], K[1, 1], K[0, 2], K[1, 2]], R, t, k]))
+
+
+def _channel_map(image: np.ndarray, convert_BRG2RGB: bool) -> np.ndarray:
+    """Output channel -> image channel: cv2.cvtColor(BGR2RGB) keeps B, G, R reversed (and drops a fourth channel)."""
+    c = image.shape[2]
+    if convert_BRG2RGB:
+        if c not in (3, 4):
+            raise ValueError(f"interpolate_point_colors: BGR to RGB needs a 3- or 4-channel image (got {c})")
+        return np.array([2, 1, 0], np.int32)
+    if not 1 <= c <= 4:
+        raise ValueError(f"interpolate_point_colors: 1 to 4 channels are supported (got {c})")
+    return np.arange(c, dtype=np.int32)
+
+
+def _points(points3d) -> np.ndarray:
+    p = np.ascontiguousarray(points3d, dtype=np.float64)
+    if p.ndim != 2 or p.shape[1] != 3:
+        raise ValueError(f"expected an Nx3 array of points (got shape {p.shape})")
+    return p
+
+
+def _project_colors(engine, points: np.ndarray, cam: np.ndarray, image=None, chmap=None, want_proj=True):
+    import torch
+    from ._lib import ptr
+    dev = engine.device
+    n = len(points)
+    dp = torch.from_numpy(points).to(dev)
+    proj = torch.empty((n, 2), dtype=torch.float32, device=dev) if want_proj else None
+    col = img = None
+    h = w = cin = cout = 0
+    if image is not None:
+        h, w, cin = image.shape
+        cout = len(chmap)
+        img = torch.from_numpy(np.ascontiguousarray(image)).to(dev)
+        col = torch.empty((n, cout), dtype=torch.float64, device=dev)
+    base = ptr(dp)
+    engine.ctx.call("im_project_colors", base, 0, 3, base + 8, 0, 3, base + 16, 0, 3, 1 if n else 0, n, 0, cam.ctypes.data,
+                    ptr(img), h, w, cin, None if chmap is None else chmap.ctypes.data, cout, ptr(proj), ptr(col), None, engine.stream_ptr())
+    return (None if proj is None else proj.cpu().numpy()), (None if col is None else col.cpu().numpy())
+
+
+def project_points(points3d, camera, engine=None) -> np.ndarray:
+    """`project_points` of the reference (`sfm/geometry.py:79-100`): [n, 2] float32 image coordinates of [n, 3] world points. The
+    reference calls cv2.projectPoints; here it is restated elementwise in float64 on the device (R X + t, the perspective divide, Brown
+    k1 k2 p1 p2 [k3 [k4 k5 k6]] rational distortion, fx x + cx) and cast to float32. R is used as given (no Rodrigues round trip)."""
+    cam = _camera_params(camera)
+    p = _points(points3d)
+    return _project_colors(_engine(engine), p, cam)[0]
+
+
+def interpolate_point_colors(points3d, image, camera, convert_BRG2RGB=True, engine=None) -> np.ndarray:
+    """`interpolate_point_colors` of the reference (`sfm/interpolate_colors.py:13-51`): [n, channels] float64 colours in [0, 1] of
+    [n, 3] world points, sampled bilinearly (`bilinear_interpolate`: clipped corners, weights from the unclipped position) from a uint8
+    image after `float32(v) / 255`; BGR is reversed to RGB first unless `convert_BRG2RGB=False`. Projection and sampling in one launch."""
+    assert image.ndim == 3, "invalid input image. Image has not 3 channel"
+    image = np.asarray(image)
+    if image.dtype != np.uint8:
+        raise ValueError(f"interpolate_point_colors: a uint8 image is expected (got {image.dtype})")
+    chmap = _channel_map(image, convert_BRG2RGB)
+    cam = _camera_params(camera)
+    p = _points(points3d)
+    return _project_colors(_engine(engine), p, cam, image, chmap, want_proj=False)[1]

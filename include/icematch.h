@@ -247,6 +247,41 @@ int im_forient(im_ctx* ctx, const void* d_img, int dtype, int n_images, int h, i
 int im_template_match_oc(im_ctx* ctx, const float* d_a, int ha, int wa, const float* d_b, int n_b, int hb, int wb, const double* d_pairs,
                          const int32_t* d_bidx, int n_pairs, int T, int S, int conj_b, double* d_out, void* stream);
 
+/* ---- DSM and orthophoto rasters (`src/icepy4d/utils/dsm_orthophoto.py`, `sfm/interpolate_colors.py`, `sfm/geometry.py`) ------------
+ * The binning of `build_dsm` (`dsm_orthophoto.py:40-81`) in two calls around three stable sorts done by the caller:
+ * im_dsm_round replaces `round_to_val` (`:39-40`, `:64-66`): d_pts [n][3] float64; d_xr / d_yr [n] float32 = rint(x / step) * step in
+ * float32 (half to even); sort keys [n] int64 whose ascending order is the value order with -0.0 == 0.0: d_xykey of (x_r, y_r),
+ * d_ykey of y_r, d_zkey of z (NaN last, all NaN equal). Enqueue only.
+ * The caller forms the reference's `np.lexsort((y_r, z))` order (`:69-70`) as d_perm_b = stable sorts by d_ykey, then by d_zkey, and
+ * the group order as d_perm_c = d_perm_b stably sorted by d_xykey.
+ * im_dsm_group_mean replaces `df.groupby(["x_round", "y_round"]).mean()` (`:73-81`): d_bx / d_by / d_bz [n] float32 (capacity n) get
+ * the groups in ascending (x, y), z the Kahan mean of the group's non-NaN z in ascending-z order (pandas' group_mean; NaN when there
+ * is none); *d_n_groups the number of groups. A key of zero keeps the sign of its first row in d_perm_b order. Enqueue only. */
+int im_dsm_round(im_ctx* ctx, const double* d_pts, long long n, float step, float* d_xr, float* d_yr, long long* d_xykey,
+                 long long* d_ykey, long long* d_zkey, void* stream);
+int im_dsm_group_mean(im_ctx* ctx, const double* d_pts, const float* d_xr, const float* d_yr, const long long* d_xykey,
+                      const long long* d_perm_b, const long long* d_perm_c, long long n, float* d_bx, float* d_by, float* d_bz,
+                      long long* d_n_groups, void* stream);
+/* Replaces `LinearNDInterpolator(...)(grid_x, grid_y)` of `build_dsm` (`:85-96`) once qhull has triangulated the binned points on the
+ * host: d_simplices [T][3] int32 and d_transform [T][3][2] float64 are scipy's `Delaunay.simplices` / `.transform`, h_bounds its
+ * min_bound (x, y) and max_bound (x, y); d_xq [nx] / d_yq [ny] the grid axes (np.arange), xq[c] == x0 + c * dx. Every cell takes the
+ * lowest-index simplex that contains it (scipy's inside test, eps = 100 DBL_EPSILON) and z = ((0 + c0 v0) + c1 v1) + c2 v2 with
+ * v = float64 of d_bz; cells in none get `fill`. d_z [ny][nx] float64. Scratch from the context. Enqueue only. */
+int im_dsm_rasterize(im_ctx* ctx, const float* d_bx, const float* d_by, const float* d_bz, const int32_t* d_simplices,
+                     const double* d_transform, long long n_simplices, const double* h_bounds, const double* d_xq, int nx,
+                     const double* d_yq, int ny, double x0, double dx, double y0, double dy, double fill, double* d_z, void* stream);
+/* Replaces `project_points` (`sfm/geometry.py:79-100`: cv2.projectPoints, restated in float64) and `interpolate_point_colors` /
+ * `bilinear_interpolate` (`sfm/interpolate_colors.py:13-92`), and the colouring of `generate_ortophoto` (`dsm_orthophoto.py:176-211`).
+ * Items (r, c) of a rows x cols table; coordinate plane P has element (r, c) at d_P[r * sPr + c * sPc]. cells = 1: a NaN z is an
+ * invalid cell (black in d_ortho). h_cam [28] float64: fx, fy, cx, cy, R (9, row-major), t (3), k1 k2 p1 p2 k3 k4 k5 k6 s1..s4 (zeros
+ * where absent). d_img [h][w][cin] uint8; output channel ch samples image channel h_chmap[ch] (cout <= 4) as float32(v) / 255.
+ * Outputs, each optional: d_proj [n][2] float32 projections, d_col [n][cout] float64 colours (the float64 sum of the reference),
+ * d_ortho [n][3] uint8 = np.uint8(float32(colour) * 255). Enqueue only. */
+int im_project_colors(im_ctx* ctx, const double* d_x, long long sxr, long long sxc, const double* d_y, long long syr, long long syc,
+                      const double* d_z, long long szr, long long szc, int rows, int cols, int cells, const double* h_cam,
+                      const unsigned char* d_img, int h, int w, int cin, const int32_t* h_chmap, int cout, float* d_proj,
+                      double* d_col, unsigned char* d_ortho, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
