@@ -217,7 +217,8 @@ __global__ __launch_bounds__(64) void ransac_hypotheses_kernel(const float* __re
     for (int j = 0; j < 9; ++j) Fs[(long)h * 9 + j] = F[j];
 }
 
-// one block: arg-max of the inlier counts (ties: lowest hypothesis), then the inlier mask of the winner
+// one block: arg-max of the inlier counts (ties: lowest hypothesis), then the inlier mask of the winner. A winner without inliers
+// (no valid hypothesis in the launch: its F is 0, and the Sampson test of F = 0 holds for every point) gives F = 0 and an empty mask.
 __global__ __launch_bounds__(1024) void ransac_select_kernel(const float* __restrict__ p0, const float* __restrict__ p1, int n, int n_hyp,
                                                               double thr2, const int* __restrict__ counts, const double* __restrict__ Fs,
                                                               double* __restrict__ F_out, uint8_t* __restrict__ mask, int* __restrict__ info) {
@@ -236,13 +237,13 @@ __global__ __launch_bounds__(1024) void ransac_select_kernel(const float* __rest
     const int hbest = 0x7FFFFFFF - (int)(uint32_t)(best[0] & 0xFFFFFFFFu);
     const int cbest = (int)(best[0] >> 32);
     double F[9];
-    for (int j = 0; j < 9; ++j) F[j] = Fs[(long)hbest * 9 + j];
+    for (int j = 0; j < 9; ++j) F[j] = cbest > 0 ? Fs[(long)hbest * 9 + j] : 0.0;
     if (threadIdx.x == 0) {
         info[0] = cbest; info[1] = hbest;
         for (int j = 0; j < 9; ++j) F_out[j] = F[j];
     }
     for (int i = threadIdx.x; i < n; i += 1024)
-        mask[i] = sampson_inlier(F, p0[2 * i], p0[2 * i + 1], p1[2 * i], p1[2 * i + 1], thr2) ? 1 : 0;
+        mask[i] = cbest > 0 && sampson_inlier(F, p0[2 * i], p0[2 * i + 1], p1[2 * i], p1[2 * i + 1], thr2) ? 1 : 0;
 }
 
 static int ransac_entry(im_ctx* ctx, const char* who, int essential, const float* d_p0, const float* d_p1, int n, int n_hyp, double threshold,
@@ -340,8 +341,9 @@ extern "C" int im_ransac_essential(im_ctx* ctx, const float* d_x0, const float* 
 extern "C" int im_triangulate_linear(im_ctx* ctx, const double* h_P0, const double* h_P1, const double* d_x0, const double* d_x1, int n,
                                      double* d_X, void* stream) {
     IM_CHECK_CTX(ctx);
-    if (!h_P0 || !h_P1 || !d_x0 || !d_x1 || !d_X || n < 0) return ctx->fail(-71, "im_triangulate_linear: null argument");
-    if (n == 0) return 0;
+    if (!h_P0 || !h_P1 || n < 0) return ctx->fail(-71, "im_triangulate_linear: null argument");
+    if (n == 0) return 0;                     // empty device tensors may hand over null pointers
+    if (!d_x0 || !d_x1 || !d_X) return ctx->fail(-71, "im_triangulate_linear: null argument");
     hipStream_t s = (hipStream_t)stream;
     double hP[24];
     for (int j = 0; j < 12; ++j) { hP[j] = h_P0[j]; hP[12 + j] = h_P1[j]; }

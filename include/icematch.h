@@ -214,14 +214,17 @@ int im_gather_rows(im_ctx* ctx, const float* d_src, int row_floats, const int32_
 /* Fundamental-matrix RANSAC over matched keypoints (`src/icepy4d/matching/geometric_verification.py:11-102`, which
  * calls pydegensac / cv2 USAC_MAGSAC on the CPU): n_hyp seeded 8-point hypotheses scored by Sampson error in parallel.
  * d_p0, d_p1 [n][2] float (x, y); d_F [9] double = matrix of the best hypothesis (unit Frobenius norm); d_mask [n] uint8
- * its inliers; d_info {inlier count, hypothesis index}. The least-squares refit on the inliers is left to the caller. */
+ * its inliers; d_info {inlier count, hypothesis index}. When the best count is 0 (every sample degenerate, e.g. duplicated or
+ * collinear correspondences), d_info = {0, 0}, d_F = 0 and the mask is all false. The least-squares refit on the inliers is left
+ * to the caller. */
 int im_ransac_fundamental(im_ctx* ctx, const float* d_p0, const float* d_p1, int n, int n_hyp, double threshold,
                           unsigned int seed, double* d_F, uint8_t* d_mask, int32_t* d_info, void* stream);
 
 /* Relative orientation, device stage (replaces the RANSAC inside `cv2.findEssentialMat`, `src/icepy4d/sfm/geometry.py:64-66`):
  * like im_ransac_fundamental on NORMALISED image coordinates (d_x0, d_x1 [n][2] float), every 8-point hypothesis projected onto
  * the essential manifold (two equal singular values, one zero) before it is scored; d_E [9] double = the best hypothesis
- * (x1^T E x0 = 0, unit Frobenius norm), d_mask / d_info as above. The cheirality test (`cv2.recoverPose`, `geometry.py:70-75`)
+ * (x1^T E x0 = 0, unit Frobenius norm), d_mask / d_info as above (also when no hypothesis is valid, a failed projection
+ * included: d_info = {0, 0}, d_E = 0, no inlier). The cheirality test (`cv2.recoverPose`, `geometry.py:70-75`)
  * and the 5-7 correspondence case (five-point solver) stay on the host: one 3 x 3 matrix. */
 int im_ransac_essential(im_ctx* ctx, const float* d_x0, const float* d_x1, int n, int n_hyp, double threshold,
                         unsigned int seed, double* d_E, uint8_t* d_mask, int32_t* d_info, void* stream);
@@ -230,7 +233,8 @@ int im_ransac_essential(im_ctx* ctx, const float* d_x0, const float* d_x1, int n
  * `src/icepy4d/sfm/triangulation.py:153-186`): h_P0, h_P1 = the two 3 x 4 projection matrices (row-major doubles in HOST
  * memory), d_x0, d_x1 [n][3] double homogeneous image points, d_X [n][4] double = homogeneous points normalised to X[3] = 1.
  * The reference's formulation (unknowns X and one depth per view, 6 x 6 system per point, right singular vector of the smallest singular
- * value): equal to the reference's outputs within 1e-9 relative (tests/golden/g10_triangulation.npz). */
+ * value): equal to the reference's outputs within 1e-9 relative (tests/golden/g10_triangulation.npz). n = 0 enqueues nothing, and
+ * d_x0 / d_x1 / d_X may then be null. */
 int im_triangulate_linear(im_ctx* ctx, const double* h_P0, const double* h_P1, const double* d_x0, const double* d_x1, int n,
                           double* d_X, void* stream);
 
