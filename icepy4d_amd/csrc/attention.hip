@@ -38,17 +38,7 @@ static constexpr int ATTN_LDS_FLOATS = 2 * KT * KS + 2 * KT * VS;   // per key g
 // 16-byte column idx & 15). The loads are buffer loads: a wave-uniform descriptor sized to the live key rows, a
 // loop-invariant 32-bit lane offset and a scalar tile offset - no per-load address arithmetic on the VALU (which
 // would cost matrix-pipe time, see softmax_tile), and rows past the last key read as zero without any clamping.
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ float4 buf_load4(__amdgpu_buffer_rsrc_t rsrc, unsigned voff, unsigned soff) {
-    const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff, soff, 0);
-    return make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
-}
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const float* base, int rows) {
-    const unsigned long long b = reinterpret_cast<unsigned long long>(base);
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)b), hi = __builtin_amdgcn_readfirstlane((unsigned)(b >> 32));
-    void* p = reinterpret_cast<void*>(((unsigned long long)hi << 32) | lo);
-    return __builtin_amdgcn_make_buffer_rsrc(p, 0, __builtin_amdgcn_readfirstlane(rows) * 256, 0x00020000);
-}
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc_rows(const float* base, int rows) { return make_rsrc(base, (unsigned)rows * 256u); }
 #define IM_LOAD_TILE(r, rsrc, tile)                                                      \
     {                                                                                    \
         const unsigned so_ = (unsigned)(tile) * (G * KT * 256u);                         \
@@ -258,8 +248,8 @@ __global__ __launch_bounds__(256 * G, 2 / G) void flash_attn_f32_kernel(AttnArgs
     const int qrow = qb + wave * 32 + c;
 
     const float* Q = a.q + (long)z * a.bstride + (long)head * a.hstride;
-    const __amdgpu_buffer_rsrc_t K = make_rsrc(a.k + (long)y * a.bstride + (long)head * a.hstride + (long)k0 * 64, nk);
-    const __amdgpu_buffer_rsrc_t V = make_rsrc(a.v + (long)y * a.bstride + (long)head * a.hstride + (long)k0 * 64, nk);
+    const __amdgpu_buffer_rsrc_t K = make_rsrc_rows(a.k + (long)y * a.bstride + (long)head * a.hstride + (long)k0 * 64, nk);
+    const __amdgpu_buffer_rsrc_t V = make_rsrc_rows(a.v + (long)y * a.bstride + (long)head * a.hstride + (long)k0 * 64, nk);
     const unsigned voff = ((tid >> 4) * 64 + (tid & 15) * 4) * sizeof(float);
 
     // Q fragment: lane (c, hh) keeps Q[qrow][32*hh + s], s = 0..31

@@ -2,17 +2,8 @@
 // and output layout as attention.hip (the reference materialises the attention matrix on the CPU: `lightglue/lightglue.py:120-123`
 // via SDPA, `:200-210` explicit einsum / softmax, `SuperGlue/models/superglue.py:87-93`).
 //
-// Why: gfx950's f32-input MFMA runs at the VECTOR rate (157 TFLOP/s, 1 / 16 of the bf16 matrix cores) and holds the vector issue port
-// while it runs; the bf16 MFMA does neither. An fp32 value is the exact sum of three bf16 values (8 + 8 + 8 significant bits, each cut
-// rounded to nearest: x = x0 + x1 + x2 with |x1| <= 2^-8 |x|, |x2| <= 2^-17 |x|, nothing left), a bf16 product is exact in
-// the matrix core's fp32 accumulation, and of the nine products of two such triples the three that are dropped (i + j >= 3) are worth at
-// most 2^-24 |a b| - the rounding of ONE fp32 operation -, 2^-27.4 in the root mean square (tests/test_host_cpu.py pins this arithmetic
-// in numpy). `tools/bf16x_probe.hip` measured the accumulation on the part
-// (`profiles/r05_bf16x_probe.txt`): error against an f64 sum, in units of 2^-24 sum |a b|, rms 0.37-0.39 for six products against
-// 0.45-0.47 for the f32 MFMA chain at K = 64 .. 4096 (the matrix core adds 16 products before it rounds once), nine products no
-// better than six, three 4-30 x worse; and six `v_mfma_f32_32x32x16_bf16` per 16 k run at 2.2-2.35 PFLOP/s = 2.4-2.5 x the f32 MFMA,
-// 1.8-2.15 x with four to five vector instructions between the MFMAs - the vector instructions of the splits and of the softmax run
-// BESIDE the matrix cores instead of in front of them.
+// Every fp32 product is six bf16 products of the operands' three bf16 planes (bf16x3.h: the scheme, its error and its rate on the part);
+// the vector instructions of the cuts and of the softmax run BESIDE the matrix cores instead of in front of them.
 //
 // Both products keep the QUERY on the MFMA lane, as attention.hip does:
 //     S^T (32 keys x 32 queries) = K . Q^T     A = three bf16 planes of a K tile in LDS (16-byte row reads), B = Q planes in registers
@@ -25,6 +16,7 @@
 //                staging registers, no ds_write; unpadded 128-byte rows whose 16-byte pieces are permuted by the transfer, rings of three stages;
 //   <PRE, !DMA>  the same planes through registers (IM_ATTN_REG_STAGING=1, A/B): padded rows, rings of two stages;
 //   <!PRE>       no plane workspace: the fp32 tiles are cut while they are staged, once per block.
+#include "bf16x3.h"
 #include "common.h"
 #include "kernels.h"
 #include "sp_post.h"
@@ -32,12 +24,6 @@
 #include <cstdlib>
 
 namespace im {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 
 static constexpr int BKT = 32;                    // keys per step
 static constexpr int BKS = 144;                   // bytes per key row of a K plane: 64 bf16 + 16 (conflict-free 16-byte row reads)
@@ -51,67 +37,14 @@ static constexpr int B_LDS = 2 * B_STAGE;
 static constexpr int DPL = BKT * 128;                           // bytes per plane of a tile
 static constexpr int D_LDS = 3 * 3 * (DPL + DPL);
 
-typedef unsigned int du32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) void* dlds_ptr_t;
-__device__ __forceinline__ du32x4 dma_rsrc(const void* base, unsigned bytes) {
-    const unsigned long long b = reinterpret_cast<unsigned long long>(base);
-    du32x4 r;
-    r.x = __builtin_amdgcn_readfirstlane((unsigned)b);
-    r.y = __builtin_amdgcn_readfirstlane((unsigned)(b >> 32)) & 0xFFFFu;
-    r.z = __builtin_amdgcn_readfirstlane(bytes);
-    r.w = 0x00020000u;
-    return r;
-}
-// one LDS-DMA piece as inline asm (conv_wino.hip: the compiler's wait-count pass must not see it, or it orders every later LDS read behind it)
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Winline-asm"
-__device__ __forceinline__ void bx_dma16(du32x4 rsrc, unsigned lds_byte_addr, unsigned voff, unsigned soff) {
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds"
-                 :: "s"(lds_byte_addr), "v"(voff), "s"(rsrc), "s"(soff) : "memory", "m0");
-}
-#pragma clang diagnostic pop
-
-__device__ __forceinline__ f32x16 mfma_bf(u32x4 a, u32x4 b, f32x16 c) {
-#ifdef BX_ABL_NO_MFMA       // timing ablation (wrong results): one vector instruction in place of every MFMA
+// -DBX_ABL_*: timing-only ablations of the main loop (wrong results; tools/attn_ablate.sh)
+__device__ __forceinline__ f32x16 mfma_attn(u32x4 a, u32x4 b, f32x16 c) {
+#ifdef BX_ABL_NO_MFMA       // one vector instruction in place of every MFMA
     c[0] += __uint_as_float(a.x ^ b.x);
     return c;
 #else
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
+    return mfma_bf(a, b, c);
 #endif
-}
-__device__ __forceinline__ unsigned cvt_pk(float a, float b) {            // v_cvt_pk_bf16_f32: a in the low half, round to nearest even
-    const bf16x2 v = __builtin_convertvector(f32x2{a, b}, bf16x2);
-    return __builtin_bit_cast(unsigned, v);
-}
-// (a, b) -> three packed bf16 pairs with a = h.lo + m.lo + l.lo exactly: the subtractions are exact in fp32
-__device__ __forceinline__ void split2(float a, float b, unsigned& h, unsigned& m, unsigned& l) {
-    h = cvt_pk(a, b);
-    float ra = a - __uint_as_float(h << 16), rb = b - __uint_as_float(h & 0xffff0000u);
-    m = cvt_pk(ra, rb);
-    ra -= __uint_as_float(m << 16);
-    rb -= __uint_as_float(m & 0xffff0000u);
-    l = cvt_pk(ra, rb);
-}
-
-__device__ __forceinline__ float4 bx_load4(__amdgpu_buffer_rsrc_t rsrc, unsigned voff, unsigned soff) {
-    const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff, soff, 0);
-    return make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
-}
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t bx_rsrc_bytes(const void* base, int bytes) {     // reads past `bytes` return zero
-    const unsigned long long b = reinterpret_cast<unsigned long long>(base);
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)b), hi = __builtin_amdgcn_readfirstlane((unsigned)(b >> 32));
-    void* p = reinterpret_cast<void*>(((unsigned long long)hi << 32) | lo);
-    return __builtin_amdgcn_make_buffer_rsrc(p, 0, __builtin_amdgcn_readfirstlane(bytes), 0x00020000);
-}
-
-struct Planes { u32x4 h, m, l; };
-__device__ __forceinline__ Planes split8(float x0, float x1, float x2, float x3, float x4, float x5, float x6, float x7) {
-    unsigned h[4], m[4], l[4];
-    split2(x0, x1, h[0], m[0], l[0]);
-    split2(x2, x3, h[1], m[1], l[1]);
-    split2(x4, x5, h[2], m[2], l[2]);
-    split2(x6, x7, h[3], m[3], l[3]);
-    return Planes{u32x4{h[0], h[1], h[2], h[3]}, u32x4{m[0], m[1], m[2], m[3]}, u32x4{l[0], l[1], l[2], l[3]}};
 }
 
 // one float4 of a tile row -> 8 bytes in each of the three planes
@@ -245,16 +178,16 @@ __global__ __launch_bounds__(256, 2) void flash_attn_bx_kernel(AttnArgs a) {
 
     const float* Q = a.q + (long)z * a.bstride + (long)head * a.hstride;
     __amdgpu_buffer_rsrc_t K, V;
-    du32x4 Kd = {}, Vd = {};
+    u32x4 Kd = {}, Vd = {};
     if constexpr (PRE) {
         const long rows = (long)a.heads * a.n_max * a.batch;
         const unsigned char* kp = reinterpret_cast<const unsigned char*>(a.planes) + (((long)y * a.heads + head) * a.n_max + k0) * 384;
-        K = bx_rsrc_bytes(kp, nk * 384);
-        V = bx_rsrc_bytes(kp + rows * 384, nk * 384);
-        if constexpr (DMA) { Kd = dma_rsrc(kp, nk * 384); Vd = dma_rsrc(kp + rows * 384, nk * 384); }
+        K = make_rsrc(kp, nk * 384);
+        V = make_rsrc(kp + rows * 384, nk * 384);
+        if constexpr (DMA) { Kd = make_rsrc4(kp, nk * 384); Vd = make_rsrc4(kp + rows * 384, nk * 384); }
     } else {
-        K = bx_rsrc_bytes(a.k + (long)y * a.bstride + (long)head * a.hstride + (long)k0 * 64, nk * 256);
-        V = bx_rsrc_bytes(a.v + (long)y * a.bstride + (long)head * a.hstride + (long)k0 * 64, nk * 256);
+        K = make_rsrc(a.k + (long)y * a.bstride + (long)head * a.hstride + (long)k0 * 64, nk * 256);
+        V = make_rsrc(a.v + (long)y * a.bstride + (long)head * a.hstride + (long)k0 * 64, nk * 256);
     }
 
     // Q planes: lane (c, hh) keeps Q[qrow][16 s + 8 hh + j], j = 0..7, of d-chunk s; the softmax scale and log2 e folded in before the cut
@@ -316,7 +249,7 @@ __global__ __launch_bounds__(256, 2) void flash_attn_bx_kernel(AttnArgs a) {
             for (int i = 0; i < 3; ++i) pk[i] = __builtin_amdgcn_raw_buffer_load_b128(K, voff, so + 4096u * i, 0);
         } else {
             const unsigned so = (unsigned)tile * (BKT * 256u);
-            fk[0] = bx_load4(K, voff, so); fk[1] = bx_load4(K, voff, so + 16 * 256u);
+            fk[0] = buf_load4(K, voff, so); fk[1] = buf_load4(K, voff, so + 16 * 256u);
         }
     };
     auto load_v = [&](int tile) {
@@ -326,7 +259,7 @@ __global__ __launch_bounds__(256, 2) void flash_attn_bx_kernel(AttnArgs a) {
             for (int i = 0; i < 3; ++i) pv[i] = __builtin_amdgcn_raw_buffer_load_b128(V, voff, so + 4096u * i, 0);
         } else {
             const unsigned so = (unsigned)tile * (BKT * 256u);
-            fv[0] = bx_load4(V, voff, so); fv[1] = bx_load4(V, voff, so + 16 * 256u);
+            fv[0] = buf_load4(V, voff, so); fv[1] = buf_load4(V, voff, so + 16 * 256u);
         }
     };
     auto store_k = [&](int stage) {
@@ -352,15 +285,15 @@ __global__ __launch_bounds__(256, 2) void flash_attn_bx_kernel(AttnArgs a) {
     const int drow = 8 * wave + (lane >> 3), dpc = lane & 7;
     const unsigned dvoff_k = drow * 384u + ((dpc ^ ((drow >> 1) & 7)) << 4), dvoff_v = drow * 384u + ((dpc ^ (((drow >> 1) & 1) << 2)) << 4);
     const unsigned wave_u = __builtin_amdgcn_readfirstlane(tid >> 6);          // in an SGPR: the transfer's LDS address goes through M0
-    const unsigned lds_k = __builtin_amdgcn_readfirstlane((unsigned)(unsigned long)(dlds_ptr_t)kring) + wave_u * 1024u;
-    const unsigned lds_v = __builtin_amdgcn_readfirstlane((unsigned)(unsigned long)(dlds_ptr_t)vring) + wave_u * 1024u;
+    const unsigned lds_k = __builtin_amdgcn_readfirstlane((unsigned)(unsigned long)(lds_ptr_t)kring) + wave_u * 1024u;
+    const unsigned lds_v = __builtin_amdgcn_readfirstlane((unsigned)(unsigned long)(lds_ptr_t)vring) + wave_u * 1024u;
     auto dma_k = [&](int tile, int stage) {
 #pragma unroll
-        for (int i = 0; i < 3; ++i) bx_dma16(Kd, __builtin_amdgcn_readfirstlane(lds_k + (unsigned)stage * (3u * DPL) + i * DPL), dvoff_k, __builtin_amdgcn_readfirstlane((unsigned)tile * (BKT * 384u) + i * 128u));
+        for (int i = 0; i < 3; ++i) dma16(Kd, __builtin_amdgcn_readfirstlane(lds_k + (unsigned)stage * (3u * DPL) + i * DPL), dvoff_k, __builtin_amdgcn_readfirstlane((unsigned)tile * (BKT * 384u) + i * 128u));
     };
     auto dma_v = [&](int tile, int stage) {
 #pragma unroll
-        for (int i = 0; i < 3; ++i) bx_dma16(Vd, __builtin_amdgcn_readfirstlane(lds_v + (unsigned)stage * (3u * DPL) + i * DPL), dvoff_v, __builtin_amdgcn_readfirstlane((unsigned)tile * (BKT * 384u) + i * 128u));
+        for (int i = 0; i < 3; ++i) dma16(Vd, __builtin_amdgcn_readfirstlane(lds_v + (unsigned)stage * (3u * DPL) + i * DPL), dvoff_v, __builtin_amdgcn_readfirstlane((unsigned)tile * (BKT * 384u) + i * 128u));
     };
     // S^T = K . Q^T of one tile: two accumulators (even / odd d-chunks), the small products first
     auto qk = [&](int stage, f32x16& out) {
@@ -374,12 +307,12 @@ __global__ __launch_bounds__(256, 2) void flash_attn_bx_kernel(AttnArgs a) {
             const u32x4 km = *reinterpret_cast<const u32x4*>(kp + KPL + kq[s]);
             const u32x4 kl = *reinterpret_cast<const u32x4*>(kp + 2 * KPL + kq[s]);
             f32x16& x = (s & 1) ? xb : xa;
-            x = mfma_bf(kh, ql[s], x);
-            x = mfma_bf(kl, qh[s], x);
-            x = mfma_bf(km, qm[s], x);
-            x = mfma_bf(kh, qm[s], x);
-            x = mfma_bf(km, qh[s], x);
-            x = mfma_bf(kh, qh[s], x);
+            x = mfma_attn(kh, ql[s], x);
+            x = mfma_attn(kl, qh[s], x);
+            x = mfma_attn(km, qm[s], x);
+            x = mfma_attn(kh, qm[s], x);
+            x = mfma_attn(km, qh[s], x);
+            x = mfma_attn(kh, qh[s], x);
         }
         out = xa + xb;
     };
@@ -397,12 +330,12 @@ __global__ __launch_bounds__(256, 2) void flash_attn_bx_kernel(AttnArgs a) {
                 const u32x2 l0 = tr_read(vb + 2 * VPL), l1 = tr_read(vb + 2 * VPL + 8 * VS);
                 const u32x4 vh = {h0.x, h0.y, h1.x, h1.y}, vm = {m0.x, m0.y, m1.x, m1.y}, vl = {l0.x, l0.y, l1.x, l1.y};
                 f32x16& o = dt ? o1 : o0;
-                o = mfma_bf(vh, pp.l, o);
-                o = mfma_bf(vl, pp.h, o);
-                o = mfma_bf(vm, pp.m, o);
-                o = mfma_bf(vh, pp.m, o);
-                o = mfma_bf(vm, pp.h, o);
-                o = mfma_bf(vh, pp.h, o);
+                o = mfma_attn(vh, pp.l, o);
+                o = mfma_attn(vl, pp.h, o);
+                o = mfma_attn(vm, pp.m, o);
+                o = mfma_attn(vh, pp.m, o);
+                o = mfma_attn(vm, pp.h, o);
+                o = mfma_attn(vh, pp.h, o);
             }
         }
     };
@@ -527,8 +460,8 @@ __global__ __launch_bounds__(256, 2) void flash_attn_bx_kernel(AttnArgs a) {
             for (int j = 0; j < 6; ++j) {
                 const int slot = 6 * s4 + j;
                 const u32x4 qb = PB[j] == 0 ? qh[s4] : (PB[j] == 1 ? qm[s4] : ql[s4]);
-                if (j & 1) xb = mfma_bf(kf[s4 & 1][PA[j]], qb, xb);
-                else xa = mfma_bf(kf[s4 & 1][PA[j]], qb, xa);
+                if (j & 1) xb = mfma_attn(kf[s4 & 1][PA[j]], qb, xb);
+                else xa = mfma_attn(kf[s4 & 1][PA[j]], qb, xa);
                 if (slot < 8) expo(slot);
                 else if (slot < 16) { if (slot & 1) cut_b((slot - 8) >> 1); else cut_a((slot - 8) >> 1); }
                 else { expo(slot - 8); if (slot < 20) cut_l(slot - 16); }
@@ -550,8 +483,8 @@ __global__ __launch_bounds__(256, 2) void flash_attn_bx_kernel(AttnArgs a) {
 #pragma unroll
             for (int j = 0; j < 6; ++j) {
                 const int slot = 6 * g + j;
-                if (g & 1) o1 = mfma_bf(vf[PA[j]], pp[PB[j]], o1);
-                else o0 = mfma_bf(vf[PA[j]], pp[PB[j]], o0);
+                if (g & 1) o1 = mfma_attn(vf[PA[j]], pp[PB[j]], o1);
+                else o0 = mfma_attn(vf[PA[j]], pp[PB[j]], o0);
                 if (slot < 8) { if (slot & 1) cut_b(4 + (slot >> 1)); else cut_a(4 + (slot >> 1)); }
                 else if (slot < 12) cut_l(4 + slot - 8);
                 if (slot >= 8 && slot < 16) {                     // S(t+1) = the two accumulators, two registers per slot

@@ -64,15 +64,7 @@ int im_ffn_fused(im_ctx* ctx, int act, float* d_x, const float* d_att, const flo
         f.act = act; f.x = d_x; f.x_bstride = (long)n_rows * 256; f.att = d_att; f.att_bstride = (long)n_rows * 256;
         f.w0p = d[0]; f.b0 = d[1]; f.ln_g = d[2]; f.ln_b = d[3]; f.w3p = d[4]; f.b3 = d[5];
         f.m_max = n_rows; f.batch = n_images; f.m_ptr = d_n; f.pstride = 2;
-        if (ctx->prof_on) {
-            im_ctx::ProfEntry pe{"ffn_fused", ctx->prof_event(), ctx->prof_event()};
-            hipEventRecord(pe.e0, st);
-            e = launch_ffn_fused(f, st);
-            hipEventRecord(pe.e1, st);
-            ctx->prof.push_back(pe);
-        } else {
-            e = launch_ffn_fused(f, st);
-        }
+        e = ctx->timed("ffn_fused", st, [&] { return launch_ffn_fused(f, st); });
     }
     const hipError_t e2 = hipStreamSynchronize(st);
     for (int i = 0; i < 6; ++i) hipFree(d[i]);
@@ -100,32 +92,24 @@ static int conv3x3_entry(im_ctx* ctx, bool wino, const float* d_in, const float*
     if (cin % 16 || cout % 64) return ctx->fail(-10, "im_conv3x3: cin %% 16 and cout %% 64 must be 0");
     std::vector<float> packed = wino ? pack_conv3x3_wino(h_weight, cout, cin) : pack_conv3x3(h_weight, cout, cin);
     std::vector<float> planes = wino ? pack_conv3x3_wino_bx(h_weight, cout, cin) : std::vector<float>(1);   // the product form of the Winograd layer (IM_CONV_F32=1: the f32-input form)
-    float *dw = nullptr, *db = nullptr, *dx = nullptr;
-    IM_HIP(ctx, hipMalloc(&dw, packed.size() * sizeof(float)));
-    IM_HIP(ctx, hipMalloc(&db, cout * sizeof(float)));
-    IM_HIP(ctx, hipMalloc(&dx, planes.size() * sizeof(float)));
-    IM_HIP(ctx, hipMemcpy(dw, packed.data(), packed.size() * sizeof(float), hipMemcpyHostToDevice));
-    IM_HIP(ctx, hipMemcpy(db, h_bias, cout * sizeof(float), hipMemcpyHostToDevice));
-    IM_HIP(ctx, hipMemcpy(dx, planes.data(), planes.size() * sizeof(float), hipMemcpyHostToDevice));
-    ConvArgs a;
-    a.in = d_in; a.w = dw; a.bias = db; a.out = d_out; a.B = b; a.H = h; a.W = w; a.Cin = cin; a.Cout = cout;
-    a.relu = relu; a.pool = pool;
-    if (wino) a.wx = dx;
-    hipStream_t st = (hipStream_t)stream;
+    const size_t sizes[3] = {packed.size(), (size_t)cout, planes.size()};
+    const float* src[3] = {packed.data(), h_bias, planes.data()};
+    float* d[3] = {nullptr, nullptr, nullptr};
     hipError_t e = hipSuccess;
-    if (ctx->prof_on) {
-        im_ctx::ProfEntry pe{wino ? "conv_wino" : "conv_direct", ctx->prof_event(), ctx->prof_event()};
-        hipEventRecord(pe.e0, st);
-        e = wino ? launch_conv3x3_wino(a, st) : launch_conv3x3(a, st);
-        hipEventRecord(pe.e1, st);
-        ctx->prof.push_back(pe);
-    } else {
-        e = wino ? launch_conv3x3_wino(a, st) : launch_conv3x3(a, st);
+    for (int i = 0; i < 3 && e == hipSuccess; ++i) {
+        e = hipMalloc(&d[i], sizes[i] * sizeof(float));
+        if (e == hipSuccess) e = hipMemcpy(d[i], src[i], sizes[i] * sizeof(float), hipMemcpyHostToDevice);
     }
-    hipError_t e2 = hipStreamSynchronize(st);
-    hipFree(dw);
-    hipFree(db);
-    hipFree(dx);
+    hipStream_t st = (hipStream_t)stream;
+    if (e == hipSuccess) {
+        ConvArgs a;
+        a.in = d_in; a.w = d[0]; a.bias = d[1]; a.out = d_out; a.B = b; a.H = h; a.W = w; a.Cin = cin; a.Cout = cout;
+        a.relu = relu; a.pool = pool;
+        if (wino) a.wx = d[2];
+        e = ctx->timed(wino ? "conv_wino" : "conv_direct", st, [&] { return wino ? launch_conv3x3_wino(a, st) : launch_conv3x3(a, st); });
+    }
+    const hipError_t e2 = hipStreamSynchronize(st);
+    for (int i = 0; i < 3; ++i) hipFree(d[i]);
     IM_HIP(ctx, e);
     IM_HIP(ctx, e2);
     return 0;
@@ -138,35 +122,15 @@ int im_flash_attn(im_ctx* ctx, const float* d_q, const float* d_k, const float* 
     a.q = d_q; a.k = d_k; a.v = d_v; a.hstride = (long)n_max * 64; a.bstride = a.hstride * heads;
     a.out = d_out; a.ldo = heads * 64; a.out_bstride = (long)n_max * a.ldo;
     a.n_ptr = d_n; a.n_max = n_max; a.batch = batch; a.heads = heads; a.cross = cross & 1; a.f32_form = (cross >> 1) & 1; a.scale = scale;
-    // split-KV scratch of the stage entry point (the model paths use the reserved workspace): grown on demand
-    // each of the three grows on its own, to max(old, new) (growing both when either was short re-allocated on alternating shapes,
-    // a failed second allocation leaked the first, and the planes were grown for calls that do not use them)
-    const size_t nf = attn_part_floats(n_max, batch, heads), ni = attn_counter_ints(n_max, batch, heads);
-    if (nf > ctx->stage_attn_floats) {
-        IM_HIP(ctx, hipDeviceSynchronize());
-        float* p = ctx->dalloc<float>(nf, "stage_attn_part");
-        if (!p) return ctx->fail(-11, "im_flash_attn: out of device memory");
-        ctx->dfree(ctx->stage_attn_part);        // the smaller scratch it replaces (the device is idle: synchronised above)
-        ctx->stage_attn_part = p; ctx->stage_attn_floats = nf;
-    }
-    if (ni > ctx->stage_attn_ints) {
-        IM_HIP(ctx, hipDeviceSynchronize());
-        int* c = ctx->dalloc<int>(ni, "stage_attn_cnt");
-        if (!c) return ctx->fail(-11, "im_flash_attn: out of device memory");
-        IM_HIP(ctx, hipMemset(c, 0, ni * sizeof(int)));
-        ctx->dfree(ctx->stage_attn_cnt);
-        ctx->stage_attn_cnt = c; ctx->stage_attn_ints = ni;
-    }
+    // split-KV scratch of the stage entry point (the model paths use the reserved workspace). Each of the three grows on its own (ADVICE r05:
+    // growing both when either was short re-allocated on alternating shapes, and the planes were grown for calls that do not use them)
+    im_ctx::StageScratch& sc = ctx->scratch;
     const bool wants_planes = !(cross & 4) && !a.f32_form;      // bit 2: K / V cut inside the attention kernel; the f32 form has no planes
-    const size_t nb = attn_planes_bytes(n_max, batch, heads);
-    if (wants_planes && nb > ctx->stage_attn_plane_bytes) {
-        IM_HIP(ctx, hipDeviceSynchronize());
-        unsigned char* p = ctx->dalloc<unsigned char>(nb, "stage_attn_planes");
-        if (!p) return ctx->fail(-11, "im_flash_attn: out of device memory");
-        ctx->dfree(ctx->stage_attn_planes);
-        ctx->stage_attn_planes = p; ctx->stage_attn_plane_bytes = nb;
-    }
-    a.part = ctx->stage_attn_part; a.counters = ctx->stage_attn_cnt; a.planes = wants_planes ? ctx->stage_attn_planes : nullptr;
+    IM_GROW(ctx, ctx->grow(sc.attn_part, attn_part_floats(n_max, batch, heads) * sizeof(float), "stage_attn_part"), -11, "im_flash_attn: out of device memory");
+    // the counters reset themselves, so only a new buffer needs zeroing - before it becomes the context's
+    IM_GROW(ctx, ctx->grow(sc.attn_cnt, attn_counter_ints(n_max, batch, heads) * sizeof(int), "stage_attn_cnt", true), -11, "im_flash_attn: out of device memory");
+    if (wants_planes) IM_GROW(ctx, ctx->grow(sc.attn_planes, attn_planes_bytes(n_max, batch, heads), "stage_attn_planes"), -11, "im_flash_attn: out of device memory");
+    a.part = sc.attn_part.as<float>(); a.counters = sc.attn_cnt.as<int>(); a.planes = wants_planes ? sc.attn_planes.as<unsigned char>() : nullptr;
     IM_HIP(ctx, launch_attn_planes(a, (hipStream_t)stream));
     IM_HIP(ctx, launch_flash_attn(a, (hipStream_t)stream));
     IM_GUARD_CHECK(ctx, (hipStream_t)stream, "im_flash_attn");

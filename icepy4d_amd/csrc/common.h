@@ -7,6 +7,8 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x8 __attribute__((ext_vector_type(8)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 #define IM_WAVE 64
 #define IM_MAX_DEVICES 16
@@ -40,17 +42,48 @@ __device__ __forceinline__ int wave_sum_i(int v) {
 
 // Raw buffer access: a descriptor sized to the live bytes (reads past it return zero, stores past it are dropped), lane
 // offsets in a VGPR, the wave-uniform part of the address in an SGPR - no 64-bit address arithmetic on the VALU.
-typedef unsigned int gu32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ float4 gbuf_load4(__amdgpu_buffer_rsrc_t rsrc, unsigned voff, unsigned soff) {
-    const gu32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff, soff, 0);
+__device__ __forceinline__ float4 buf_load4(__amdgpu_buffer_rsrc_t rsrc, unsigned voff, unsigned soff) {
+    const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff, soff, 0);
     return make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
 }
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t gmake_rsrc(const void* base, unsigned bytes) {
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* base, unsigned bytes) {
     const unsigned long long b = reinterpret_cast<unsigned long long>(base);
     const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)b), hi = __builtin_amdgcn_readfirstlane((unsigned)(b >> 32));
     void* p = reinterpret_cast<void*>(((unsigned long long)hi << 32) | lo);
     return __builtin_amdgcn_make_buffer_rsrc(p, 0, __builtin_amdgcn_readfirstlane(bytes), 0x00020000);
 }
+
+typedef __attribute__((address_space(3))) void* lds_ptr_t;
+
+// One LDS-DMA piece (buffer_load_dwordx4 ... lds: 64 lanes x 16 bytes land at lds_byte_addr + 16 * lane) issued as INLINE ASM, so
+// that the compiler's wait-count pass does not know about it: with the `__builtin_amdgcn_raw_ptr_buffer_load_lds` form it orders
+// every later LDS read behind the transfer with `s_waitcnt vmcnt(0)` (it cannot tell which LDS bytes a transfer writes), i.e. each
+// slab step of the Winograd kernels first waited for the transfer of the NEXT slab that it had just started. Issued this way the
+// transfer of slab + 1 stays in flight under the reads, the transform and the 32 MFMAs of slab and is waited for by an explicit
+// s_waitcnt vmcnt(0) in front of the step's barrier (IM_DMA_WAIT). The descriptor is four SGPRs, the LDS address goes through M0.
+__device__ __forceinline__ u32x4 make_rsrc4(const void* base, unsigned bytes) {
+    const unsigned long long b = reinterpret_cast<unsigned long long>(base);
+    u32x4 r;
+    r.x = __builtin_amdgcn_readfirstlane((unsigned)b);
+    r.y = __builtin_amdgcn_readfirstlane((unsigned)(b >> 32)) & 0xFFFFu;
+    r.z = __builtin_amdgcn_readfirstlane(bytes);
+    r.w = 0x00020000u;
+    return r;
+}
+// M0 is named in the clobber list so that a compiler-generated M0 user (builtin LDS-DMA, readlane / movrel, sendmsg) placed in the
+// same kernel never relies on a value from before the statement; clang notes that M0 is a reserved register (-Winline-asm), which is
+// the point: silenced for this function only.
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Winline-asm"
+__device__ __forceinline__ void dma16(u32x4 rsrc, unsigned lds_byte_addr, unsigned voff, unsigned soff) {
+    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds"
+                 :: "s"(lds_byte_addr), "v"(voff), "s"(rsrc), "s"(soff) : "memory", "m0");
+}
+#pragma clang diagnostic pop
+#define IM_DMA_WAIT() asm volatile("s_waitcnt vmcnt(0)" ::: "memory")
+// the same when eight register loads (the next slab's U fragments) were issued BEHIND the transfers: loads return in order, so "at most
+// eight outstanding" means the transfers have landed while the U loads stay in flight across the barrier (round 5)
+#define IM_DMA_WAIT_BEFORE_8_LOADS() asm volatile("s_waitcnt vmcnt(8)" ::: "memory")
 
 // Image value fed to conv1a for pixel `pix` of a uint8 image with 1 or 3 interleaved channels.
 //   1 channel : x / 255 (`matchers.py:1212-1220`, `:263-274`; true fp32 division == float64 divide then round, for all 256 inputs)

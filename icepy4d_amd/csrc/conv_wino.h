@@ -1,9 +1,10 @@
 // Shared pieces of the Winograd F(2x2, 3x3) kernels (conv_wino.hip: four waves per block, two blocks per CU; conv_wino_bx2.hip: eight waves,
-// two tile groups that share every U fragment through LDS): vector helpers, LDS-DMA, the bf16 plane cut and the inverse-transform epilogue.
+// two tile groups that share every U fragment through LDS): vector helpers, the ablation wrappers of the bf16 plane arithmetic and the inverse-transform epilogue.
 #pragma once
 #include <cstdlib>
 #include <type_traits>
 
+#include "bf16x3.h"
 #include "common.h"
 #include "kernels.h"
 #include "sp_post.h"
@@ -13,12 +14,6 @@ namespace im {
 static constexpr int WCC = 8;                         // channels per slab
 static constexpr int W_SU = 16 * 64 * WCC;            // floats: one U block
 
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t wmake_rsrc(const void* base, unsigned bytes) {
-    const unsigned long long b = reinterpret_cast<unsigned long long>(base);
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)b), hi = __builtin_amdgcn_readfirstlane((unsigned)(b >> 32));
-    void* p = reinterpret_cast<void*>(((unsigned long long)hi << 32) | lo);
-    return __builtin_amdgcn_make_buffer_rsrc(p, 0, __builtin_amdgcn_readfirstlane(bytes), 0x00020000);
-}
 // packed fp32 on float4 halves: two-element vector arithmetic, which the compiler lowers to v_pk_add_f32 (plain float4 arithmetic
 // is scalarised). NOT inline asm: round 3 found that `asm("v_pk_add_f32 ...")` next to the MFMAs gives wrong results as soon as
 // the register allocation changes (any reordering of the slab step that keeps the U fragments live across the stage; the same
@@ -74,77 +69,24 @@ static constexpr int X_SP = XP_STAGE * 4;            // BX: floats per patch sta
 static constexpr int X_LDS_FLOATS = 16384;           // BX: two patch stages (6,400 floats); the 64 KB exchange image of the epilogue aliases them
 static_assert(2 * X_SP <= X_LDS_FLOATS, "the patch stages must fit under the exchange image");
 
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-
-// One LDS-DMA piece (buffer_load_dwordx4 ... lds: 64 lanes x 16 bytes land at lds_byte_addr + 16 * lane) issued as INLINE ASM, so
-// that the compiler's wait-count pass does not know about it: with the `__builtin_amdgcn_raw_ptr_buffer_load_lds` form it orders
-// every later LDS read behind the transfer with `s_waitcnt vmcnt(0)` (it cannot tell which LDS bytes a transfer writes), i.e. each
-// slab step first waited for the transfer of the NEXT slab that it had just started. Issued this way the transfer of slab + 1 stays
-// in flight under the reads, the transform and the 32 MFMAs of slab and is waited for by an explicit s_waitcnt vmcnt(0) in front
-// of the step's barrier (IM_DMA_WAIT). The descriptor is four SGPRs, the LDS address goes through M0.
-typedef unsigned int wu32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ wu32x4 wmake_rsrc4(const void* base, unsigned bytes) {
-    const unsigned long long b = reinterpret_cast<unsigned long long>(base);
-    wu32x4 r;
-    r.x = __builtin_amdgcn_readfirstlane((unsigned)b);
-    r.y = __builtin_amdgcn_readfirstlane((unsigned)(b >> 32)) & 0xFFFFu;
-    r.z = __builtin_amdgcn_readfirstlane(bytes);
-    r.w = 0x00020000u;
-    return r;
-}
-// M0 is named in the clobber list so that a compiler-generated M0 user (builtin LDS-DMA, readlane / movrel, sendmsg) placed in the
-// same kernel never relies on a value from before the statement; clang notes that M0 is a reserved register (-Winline-asm), which is
-// the point: silenced for this function only.
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Winline-asm"
-__device__ __forceinline__ void dma16(wu32x4 rsrc, unsigned lds_byte_addr, unsigned voff, unsigned soff) {
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds"
-                 :: "s"(lds_byte_addr), "v"(voff), "s"(rsrc), "s"(soff) : "memory", "m0");
-}
-#pragma clang diagnostic pop
-#define IM_DMA_WAIT() asm volatile("s_waitcnt vmcnt(0)" ::: "memory")
-// the same when eight register loads (the next slab's U fragments) were issued BEHIND the transfers: loads return in order, so "at most
-// eight outstanding" means the transfers have landed while the U loads stay in flight across the barrier (round 5)
-#define IM_DMA_WAIT_BEFORE_8_LOADS() asm volatile("s_waitcnt vmcnt(8)" ::: "memory")
-
-// ---- BX (round 6): the sixteen element-wise products on the bf16 matrix cores at fp32 accuracy, as gemm.hip BX / attention_bx.hip: every fp32
-// operand is the exact sum of three bf16 values (x = h + m + l, each rounded to nearest even from the residual), a product is the six bf16
-// products h l, l h, m m, h m, m h, h h accumulated in fp32 in that order (small terms first). U is cut on the host (weights.hip::
-// pack_conv3x3_wino_bx); V = B^T d B is computed in fp32 exactly as in the f32 form and cut AFTER the transform (the planes of a sum are not
-// the sums of the planes), in registers, just before it becomes the A operand of v_mfma_f32_32x32x16_bf16 (lane (c, hh): tile c, channels
-// 8 hh .. 8 hh + 7 of a 16-channel chunk).
-typedef __bf16 wbf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 wbf16x2 __attribute__((ext_vector_type(2)));
+// ---- BX (round 6): the sixteen element-wise products on the bf16 matrix cores at fp32 accuracy (bf16x3.h). U is cut on the host
+// (weights.hip::pack_conv3x3_wino_bx); V = B^T d B is computed in fp32 exactly as in the f32 form and cut AFTER the transform (the planes of a
+// sum are not the sums of the planes), in registers, just before it becomes the A operand of v_mfma_f32_32x32x16_bf16 (lane (c, hh): tile c,
+// channels 8 hh .. 8 hh + 7 of a 16-channel chunk).
 // -DIM_XABL_*: timing-only ablations of the BX main loop (WRONG results by construction; tools/build_conv_variant.sh builds them into build_abl/)
-__device__ __forceinline__ f32x16 mfma_bx(wu32x4 a, wu32x4 b, f32x16 c) {
+__device__ __forceinline__ f32x16 mfma_bx(u32x4 a, u32x4 b, f32x16 c) {
 #ifdef IM_XABL_NO_MFMA
     c[0] += __uint_as_float(a.x ^ b.x);      // keeps the operands alive: one vector instruction instead of the MFMA
     return c;
 #endif
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(wbf16x8, a), __builtin_bit_cast(wbf16x8, b), c, 0, 0, 0);
-}
-__device__ __forceinline__ unsigned wcvt_pk(float a, float b) {
-    const wbf16x2 v = __builtin_convertvector(f32x2{a, b}, wbf16x2);
-    return __builtin_bit_cast(unsigned, v);
+    return mfma_bf(a, b, c);
 }
 __device__ __forceinline__ void wsplit2(float a, float b, unsigned& h, unsigned& m, unsigned& l) {
 #ifdef IM_XABL_NO_CUT
     h = __float_as_uint(a); m = __float_as_uint(b); l = h ^ m;
     return;
 #endif
-    h = wcvt_pk(a, b);
-    float ra = a - __uint_as_float(h << 16), rb = b - __uint_as_float(h & 0xffff0000u);
-    m = wcvt_pk(ra, rb);
-    ra -= __uint_as_float(m << 16);
-    rb -= __uint_as_float(m & 0xffff0000u);
-    l = wcvt_pk(ra, rb);
-}
-struct WPlanes { wu32x4 h, m, l; };
-__device__ __forceinline__ WPlanes wsplit8(const float (&x)[8]) {
-    unsigned h[4], m[4], l[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) wsplit2(x[2 * i], x[2 * i + 1], h[i], m[i], l[i]);
-    return WPlanes{wu32x4{h[0], h[1], h[2], h[3]}, wu32x4{m[0], m[1], m[2], m[3]}, wu32x4{l[0], l[1], l[2], l[3]}};
+    split2(a, b, h, m, l);
 }
 #ifdef IM_XABL_ONE_U          // every step reads the same 3 KB fragment of its wave (L1-resident): what is the L2 stream of the U planes worth?
 #define IM_XABL_U_OFFSET(x) (ux_base + 0u * (x))
@@ -197,7 +139,7 @@ __device__ __forceinline__ void wino_epilogue(const ConvArgs& a, const f32x16 (&
     // does not wrap around 32 bits, and the scalar offset ALONE (up to ST * 4 - 1 rows) stays below the record count: the raw-buffer
     // check is `offset >= num_records - soffset`, whose right side must not wrap for a map lower than one region (small tiles)
     const bool cols_all = Wo - ox0 >= ST * 8 && Ho >= ST * 4 && (unsigned long)(Ho + 8) * (unsigned long)Wo * (unsigned long)a.Cout * 4ul < (1ul << 32);
-    const __amdgpu_buffer_rsrc_t rout = wmake_rsrc(a.out + (long)b * Ho * Wo * a.Cout, (unsigned)Ho * Wo * a.Cout * 4u);
+    const __amdgpu_buffer_rsrc_t rout = make_rsrc(a.out + (long)b * Ho * Wo * a.Cout, (unsigned)Ho * Wo * a.Cout * 4u);
     auto finish_row = [&](auto W_) {
         constexpr int w = decltype(W_)::value;                                 // this wave's tile row: registers 4 w .. 4 w + 3
 #pragma unroll
@@ -311,7 +253,7 @@ __device__ __forceinline__ bool wino_epilogue_rounds(const ConvArgs& a, const f3
     // does not wrap around 32 bits, and the scalar offset ALONE (up to ST * 4 - 1 rows) stays below the record count: the raw-buffer
     // check is `offset >= num_records - soffset`, whose right side must not wrap for a map lower than one region (small tiles)
     const bool cols_all = Wo - ox0 >= ST * 8 && Ho >= ST * 4 && (unsigned long)(Ho + 8) * (unsigned long)Wo * (unsigned long)a.Cout * 4ul < (1ul << 32);
-    const __amdgpu_buffer_rsrc_t rout = wmake_rsrc(a.out + (long)b * Ho * Wo * a.Cout, (unsigned)Ho * Wo * a.Cout * 4u);
+    const __amdgpu_buffer_rsrc_t rout = make_rsrc(a.out + (long)b * Ho * Wo * a.Cout, (unsigned)Ho * Wo * a.Cout * 4u);
     auto finish_row = [&](auto W_) {
         constexpr int w = decltype(W_)::value;                                 // this wave's tile row: registers 4 w .. 4 w + 3
 #pragma unroll

@@ -109,12 +109,12 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wino_kernel(ConvArgs a) {
             // the vector form in the same order (same bits). A = weights (lane: channel c of the row tile, k = 2 s + hh), B = the patch
             // slot's image taps; a lane ends with its slot's channels (r & 3) + 8 (r >> 2) + 4 hh = one channel quad per register group,
             // i.e. the float4 the patch image holds. Seven column tiles of 32 slots cover the 200 slots; wave w takes tiles w, w + 4.
-            const __amdgpu_buffer_rsrc_t rwq = wmake_rsrc(a.w1q, 64u * 2u * 8u * 4u);
+            const __amdgpu_buffer_rsrc_t rwq = make_rsrc(a.w1q, 64u * 2u * 8u * 4u);
             float wA[2][5];
 #pragma unroll
             for (int m = 0; m < 2; ++m) {
                 const unsigned off = (unsigned)(((m * 32 + c) * 2 + hh) * 8) * 4u;
-                const float4 w4 = gbuf_load4(rwq, off, 0u), w5 = gbuf_load4(rwq, off + 16u, 0u);
+                const float4 w4 = buf_load4(rwq, off, 0u), w5 = buf_load4(rwq, off + 16u, 0u);
                 wA[m][0] = w4.x; wA[m][1] = w4.y; wA[m][2] = w4.z; wA[m][3] = w4.w; wA[m][4] = w5.x;
             }
             float4* const sPq = reinterpret_cast<float4*>(smem);
@@ -158,14 +158,14 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wino_kernel(ConvArgs a) {
         }
     }
 
-    const wu32x4 rin = wmake_rsrc4(FUSE1A ? (const void*)a.w : (const void*)(a.in + (long)b * a.H * a.W * a.Cin),
+    const u32x4 rin = make_rsrc4(FUSE1A ? (const void*)a.w : (const void*)(a.in + (long)b * a.H * a.W * a.Cin),
                                    FUSE1A ? 0u : (unsigned)a.H * a.W * a.Cin * 4u);
-    const wu32x4 ruw = wmake_rsrc4(a.w, (unsigned)(a.Cin / WCC) * 16u * a.Cout * WCC * 4u);
+    const u32x4 ruw = make_rsrc4(a.w, (unsigned)(a.Cin / WCC) * 16u * a.Cout * WCC * 4u);
     const unsigned lds_sP = (unsigned)(unsigned long)(lds_ptr_t)sP, lds_sU = (unsigned)(unsigned long)(lds_ptr_t)sU;   // LDS byte addresses
     // The fused first layer keeps the builtin form of the U transfer (compiler-managed waits): its stage is dominated by the conv1a
     // arithmetic and the ds_writes of the patch, and with the asm form it measured 10 % SLOWER (1.67 vs 1.52 ms at 1080p); the
     // plain layers gain 3-5 % from the asm form.
-    const __amdgpu_buffer_rsrc_t ruw_b = wmake_rsrc(a.w, (unsigned)(a.Cin / WCC) * 16u * a.Cout * WCC * 4u);
+    const __amdgpu_buffer_rsrc_t ruw_b = make_rsrc(a.w, (unsigned)(a.Cin / WCC) * 16u * a.Cout * WCC * 4u);
     const unsigned pv = p_in ? (unsigned)(((unsigned)p_gy * a.W + p_gx) * a.Cin) * 4u : 0xFFFFF000u;
     // U image in LDS: [pos][channel quad][64 output channels] float4, so that the 16 lanes of a ds_read_b128 lane
     // group read 16 consecutive slots (with the quad innermost the even / odd slots of one quad gave a 2-way bank
@@ -230,11 +230,11 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wino_kernel(ConvArgs a) {
     // channels x 32 bytes = 1 KB per load and half wave), requested one slab ahead into the other of two register sets, instead of
     // 8 LDS-DMA pieces + 8 ds_read_b128. Measured -2..-3 % at 64 output channels and +1..+3 % at 128 / 256 (several slices per
     // region fetch from L2 at once), hence a template parameter chosen per layer.
-    const __amdgpu_buffer_rsrc_t ruq = wmake_rsrc(a.w, (unsigned)(a.Cin / WCC) * 16u * a.Cout * WCC * 4u);
+    const __amdgpu_buffer_rsrc_t ruq = make_rsrc(a.w, (unsigned)(a.Cin / WCC) * 16u * a.Cout * WCC * 4u);
     const unsigned uq_voff = (unsigned)((((ph * 4) * a.Cout + co0 + c) * WCC) + hh * 4) * 4u;
     const unsigned uq_j = (unsigned)a.Cout * WCC * 4u;
     float4 uA[8], uB[8];
-#define IM_ULOAD(dst, slab) _Pragma("unroll") for (int p_ = 0; p_ < 8; ++p_) dst[p_] = gbuf_load4(ruq, uq_voff + (p_ & 1) * 1024u, (unsigned)(slab) * u_slab_bytes + (p_ >> 1) * uq_j);
+#define IM_ULOAD(dst, slab) _Pragma("unroll") for (int p_ = 0; p_ < 8; ++p_) dst[p_] = buf_load4(ruq, uq_voff + (p_ & 1) * 1024u, (unsigned)(slab) * u_slab_bytes + (p_ >> 1) * uq_j);
 #define IM_SDA(j) pa[a_slotA + ((j) & 1) * S_PAR + ((j) >> 1)]
 #define IM_SDB(j) pa[a_slotB + ((j) & 1) * S_PAR + ((j) >> 1)]
 #define IM_SMMA(slab, FIRST) IM_SMMA_U(slab, FIRST, ul_)
@@ -266,7 +266,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wino_kernel(ConvArgs a) {
         // next chunk travels by LDS-DMA under this chunk's products (plain layers; the fused first layer reads its resident image).
         const int nchunk = a.Cin / 16;
         const unsigned ux_pos = (unsigned)(a.Cout / 32) * 3072u, ux_chunk = 16u * ux_pos;
-        const __amdgpu_buffer_rsrc_t rux = wmake_rsrc(a.wx, (unsigned)nchunk * ux_chunk);
+        const __amdgpu_buffer_rsrc_t rux = make_rsrc(a.wx, (unsigned)nchunk * ux_chunk);
 #ifdef IM_XABL_NO_U
         const unsigned ux_voff = 0x80000000u + (unsigned)lane * 16u;
 #else
@@ -277,7 +277,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wino_kernel(ConvArgs a) {
         const int x_slotA = 2 * hh * S_QUAD + (2 * t_ty + rowA) * S_ROW + t_tx, x_slotB = 2 * hh * S_QUAD + (2 * t_ty + rowB) * S_ROW + t_tx;
         const int xp_rowA = 2 * t_ty + rowA, xp_rowB = 2 * t_ty + rowB;
         const int xp_A = 2 * xp_rowA * XP_PITCH + ((xp_rowA >> 1) & 3) + t_tx * 4 + 2 * hh, xp_B = 2 * xp_rowB * XP_PITCH + ((xp_rowB >> 1) & 3) + t_tx * 4 + 2 * hh;
-        wu32x4 ur[X_RING][3];
+        u32x4 ur[X_RING][3];
 #define IM_XULOAD(slot, cbase, nbase, nvoff, s)   /* cbase / nbase: byte offsets of this chunk's and the next chunk's U planes; nvoff: the lane offset for the next chunk's */ \
         {                                                                                                \
             const unsigned so_ = IM_XABL_U_OFFSET((((s) >> 3) ? (nbase) : (cbase)) + ux_base + (unsigned)(((s) >> 1) & 3) * ux_pos + (unsigned)((s) & 1) * 3072u); \
@@ -356,9 +356,9 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wino_kernel(ConvArgs a) {
 #pragma unroll
             for (int s = 0; s < 8; ++s) {
                 const int j = s >> 1, n = s & 1, cur = j & 1;
-                const wu32x4 ah = {ph_[cur][0], ph_[cur][1], ph_[cur][2], ph_[cur][3]}, am = {pm_[cur][0], pm_[cur][1], pm_[cur][2], pm_[cur][3]},
+                const u32x4 ah = {ph_[cur][0], ph_[cur][1], ph_[cur][2], ph_[cur][3]}, am = {pm_[cur][0], pm_[cur][1], pm_[cur][2], pm_[cur][3]},
                              al = {pl_[cur][0], pl_[cur][1], pl_[cur][2], pl_[cur][3]};
-                const wu32x4 bh = ur[s % X_RING][0], bm = ur[s % X_RING][1], bl = ur[s % X_RING][2];
+                const u32x4 bh = ur[s % X_RING][0], bm = ur[s % X_RING][1], bl = ur[s % X_RING][2];
                 f32x16 x = mfma_bx(ah, bl, FIRST ? f32x16{} : acc[s]);
                 x = mfma_bx(al, bh, x);
                 x = mfma_bx(am, bm, x);

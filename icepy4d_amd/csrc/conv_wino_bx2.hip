@@ -88,7 +88,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_wino_bx2_kernel(ConvArgs a, in
     // past the nine used slots of a row stay out (EXEC): their 16 bytes would land in the next piece's image
     auto patch_dma = [&](const YItem& z, int chunk, bool live) __attribute__((always_inline)) {
         const unsigned so = (live ? (unsigned)chunk : 0u) * 64u;
-        const wu32x4 rs = wmake_rsrc4(a.in + (long)z.b * a.H * a.W * a.Cin, (unsigned)a.H * a.W * a.Cin * 4u);   // image b's input, formed where it is used
+        const u32x4 rs = make_rsrc4(a.in + (long)z.b * a.H * a.W * a.Cin, (unsigned)a.H * a.W * a.Cin * 4u);   // image b's input, formed where it is used
         const unsigned oobv = 0x80000000u;
         if (lane < 4 * (Y_PW / 2)) {
 #pragma unroll
@@ -111,7 +111,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_wino_bx2_kernel(ConvArgs a, in
     // ---- U: an endless stream of quarters (chunk uc, position step uj), the same for every item of this block; wave w moves V row w >> 1,
     // column tile w & 1, its three planes. uw = ring slot written next, ur_ = ring slot read next.
     const unsigned ux_pos = (unsigned)(a.Cout / 32) * 3072u, ux_chunk = 16u * ux_pos;
-    const wu32x4 rux = wmake_rsrc4(a.wx, (unsigned)nchunk * ux_chunk);
+    const u32x4 rux = make_rsrc4(a.wx, (unsigned)nchunk * ux_chunk);
     const unsigned ux_w = (unsigned)(4 * (wave >> 1)) * ux_pos + (unsigned)(co0 / 32 + (wave & 1)) * 3072u;
     const unsigned ux_lane = (unsigned)lane * 16u;
     int uc = 0, uj = 0, uw = 0, ur_ = 0;
@@ -143,13 +143,13 @@ __global__ __launch_bounds__(512, 2) void conv3x3_wino_bx2_kernel(ConvArgs a, in
     float* const sBias = reinterpret_cast<float*>(reinterpret_cast<char*>(smem) + Y_LDS_BYTES);     // the block's 64 biases (it keeps its output channels)
     if (tid < 64) sBias[tid] = a.bias[co0 + tid];
     const float4* const pa = reinterpret_cast<const float4*>(smem);
-    const wu32x4* const ring = reinterpret_cast<const wu32x4*>(reinterpret_cast<const char*>(smem) + Y_STAGE_BYTES) + (ph * 2) * 192 + lane;   // + slot * 1536 + (ct * 3 + plane) * 64
+    const u32x4* const ring = reinterpret_cast<const u32x4*>(reinterpret_cast<const char*>(smem) + Y_STAGE_BYTES) + (ph * 2) * 192 + lane;   // + slot * 1536 + (ct * 3 + plane) * 64
 
     f32x16 acc[8];
     float4 t[2][4];                 // row pass of the next chunk (quarter 2)
     float v[4][8];                  // V row of the chunk in flight
     unsigned ph_[2][4], pm_[2][4], pl_[2][4];
-    wu32x4 uf[2][3];
+    u32x4 uf[2][3];
 
     auto row_reads = [&](int q, int jj, float4& da, float4& db) __attribute__((always_inline)) {
         da = pa[xp_A + (jj & 1) * XP_PITCH + (jj >> 1) * 4 + q];
@@ -172,7 +172,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_wino_bx2_kernel(ConvArgs a, in
 #ifdef IM_XABL_NO_CUT
         ph_[buf][i] = __float_as_uint(x); ra[k] = y; rb[k] = x;
 #else
-        const unsigned h = wcvt_pk(x, y);
+        const unsigned h = cvt_pk(x, y);
         ph_[buf][i] = h;
         ra[k] = x - __uint_as_float(h << 16);
         rb[k] = y - __uint_as_float(h & 0xffff0000u);
@@ -184,7 +184,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_wino_bx2_kernel(ConvArgs a, in
 #ifdef IM_XABL_NO_CUT
         pm_[buf][i] = __float_as_uint(ra[k]);
 #else
-        const unsigned m = wcvt_pk(ra[k], rb[k]);
+        const unsigned m = cvt_pk(ra[k], rb[k]);
         pm_[buf][i] = m;
         ra[k] -= __uint_as_float(m << 16);
         rb[k] -= __uint_as_float(m & 0xffff0000u);
@@ -196,13 +196,13 @@ __global__ __launch_bounds__(512, 2) void conv3x3_wino_bx2_kernel(ConvArgs a, in
 #ifdef IM_XABL_NO_CUT
         unsigned l = __float_as_uint(rb[k]);
 #else
-        unsigned l = wcvt_pk(ra[k], rb[k]);
+        unsigned l = cvt_pk(ra[k], rb[k]);
 #endif
         Y_PIN(l);
         pl_[buf][i] = l;
     };
     auto uread = [&](int buf, int slot, int ct) __attribute__((always_inline)) {
-        const wu32x4* p = ring + slot * 1536 + ct * 192;
+        const u32x4* p = ring + slot * 1536 + ct * 192;
 #pragma unroll
         for (int pl = 0; pl < 3; ++pl) uf[buf][pl] = p[pl * 64];
     };
@@ -250,9 +250,9 @@ __global__ __launch_bounds__(512, 2) void conv3x3_wino_bx2_kernel(ConvArgs a, in
 #pragma unroll
         for (int n = 0; n < 2; ++n) {
             const int s = 2 * j + n;
-            const wu32x4 ah = {ph_[cur_][0], ph_[cur_][1], ph_[cur_][2], ph_[cur_][3]}, am = {pm_[cur_][0], pm_[cur_][1], pm_[cur_][2], pm_[cur_][3]},
+            const u32x4 ah = {ph_[cur_][0], ph_[cur_][1], ph_[cur_][2], ph_[cur_][3]}, am = {pm_[cur_][0], pm_[cur_][1], pm_[cur_][2], pm_[cur_][3]},
                          al = {pl_[cur_][0], pl_[cur_][1], pl_[cur_][2], pl_[cur_][3]};
-            const wu32x4 bh = uf[n][0], bm = uf[n][1], bl = uf[n][2];
+            const u32x4 bh = uf[n][0], bm = uf[n][1], bl = uf[n][2];
             float4 da[1], db[1];
             f32x16 x = FIRST ? f32x16{} : acc[s];
             // six MFMA slots (h l, l h, m m, h m, m h, h h); behind each its share of the vector work, fenced:

@@ -13,12 +13,11 @@
 
 namespace im {
 
-struct MergeScratch {                     // im_merge_tile_matches (tile_merge.hip); device memory owned by im_ctx::allocs
-    unsigned long long* key = nullptr;    // (ordered bits of x) << 32 | ordered bits of y, of mkpts0
-    unsigned long long* skey = nullptr;   // the same for first occurrences, ~0 for later duplicates
-    unsigned* seq = nullptr;              // p * K + i: the position in the reference's concatenation order
-    int* count = nullptr;                 // [0] entries collected, [1] unique rows
-    size_t cap = 0;
+// A device buffer that only ever grows (im_ctx::grow); the memory is owned by im_ctx::allocs.
+struct Scratch {
+    void* p = nullptr;
+    size_t bytes = 0;
+    template <typename T> T* as() const { return static_cast<T*>(p); }
 };
 std::vector<float> pack_conv3x3(const float* w, int cout, int cin);       // [cout][cin][3][3] -> [cin/16][9][cout][16]
 std::vector<float> pack_conv3x3_wino(const float* w, int cout, int cin);  // -> G g G^T as [cin/8][16][cout][8]
@@ -93,18 +92,50 @@ struct im_ctx {
         hipEventCreate(&e);
         return e;
     }
+    // f() between two events on `stream` when profiling is on, plain f() otherwise; yields what f returns (IM_LAUNCH returns on an error;
+    // call sites that have to clean up first use this directly)
+    template <typename F>
+    auto timed(const char* name, hipStream_t stream, F&& f) -> decltype(f()) {
+        if (!prof_on) return f();
+        ProfEntry pe{name, prof_event(), prof_event()};
+        prof_stream = stream;
+        hipEventRecord(pe.e0, stream);
+        auto r = f();
+        hipEventRecord(pe.e1, stream);
+        prof.push_back(pe);
+        return r;
+    }
 
     // reserved workspace
     int max_h = 0, max_w = 0, max_images = 0, max_kpts = 0;
     struct Workspace* ws = nullptr;
-    float* stage_attn_part = nullptr; int* stage_attn_cnt = nullptr; size_t stage_attn_floats = 0, stage_attn_ints = 0;  // im_flash_attn
-    unsigned char* stage_attn_planes = nullptr; size_t stage_attn_plane_bytes = 0;                                       // im_flash_attn (attention_bx.hip)
-    im::MergeScratch* merge = nullptr;   // scratch of im_merge_tile_matches (tile_merge.hip), grown on demand
-    float* tm_scratch = nullptr; size_t tm_scratch_floats = 0;   // C of a batch of pairs, im_template_match_oc (templatematch.hip), grown on demand
-    char* dsm_scratch = nullptr; size_t dsm_scratch_bytes = 0;    // scans, group starts, per-cell triangle of the DSM calls (dsm.hip), grown on demand
-    unsigned long long* clock_buf[2] = {nullptr, nullptr};   // im_debug_clock_probe: per-block (cycles, 100 MHz ticks) of the attention / Winograd BX main loops
+    // scratch of the stage entry points, grown on demand by grow() (the model forwards use the reserved workspace); free_all resets all of it
+    struct StageScratch {
+        im::Scratch attn_part, attn_cnt, attn_planes;   // im_flash_attn: split-KV partials, their self-resetting counters, K / V planes (attention_bx.hip)
+        // im_merge_tile_matches (tile_merge.hip): key = (ordered bits of x) << 32 | ordered bits of y of mkpts0; skey = the same for first occurrences,
+        // ~0 for later duplicates; seq = p * K + i, the position in the reference's concatenation order; count = 4 ints, [0] entries collected, [1] unique rows
+        im::Scratch merge_key, merge_skey, merge_seq, merge_count;
+        im::Scratch tm;          // C of a batch of pairs, im_template_match_oc (templatematch.hip)
+        im::Scratch dsm;         // scans, group starts, per-cell triangle of the DSM calls (dsm.hip)
+        im::Scratch clock[2];    // im_debug_clock_probe: per-block (cycles, 100 MHz ticks) of the attention / Winograd BX main loops
+    } scratch;
+    // hipSuccess: s holds at least `bytes`. A larger buffer is allocated (through dalloc: guards and `allocs` ownership as for every buffer; `name`
+    // appears in -90 messages) once the device is idle - queued work may still read the old one -, zeroed if asked, and only then is the old one
+    // freed: a failed growth (hipErrorOutOfMemory, or the error of the synchronise / memset) leaves s as it was. Entry points call it through IM_GROW.
+    hipError_t grow(im::Scratch& s, size_t bytes, const char* name, bool zeroed = false) {
+        if (bytes <= s.bytes) return hipSuccess;
+        if (s.p)
+            if (hipError_t e = hipDeviceSynchronize(); e != hipSuccess) return e;
+        void* q = dalloc<unsigned char>(bytes, name);
+        if (!q) return hipErrorOutOfMemory;
+        if (zeroed)
+            if (hipError_t e = hipMemset(q, 0, bytes); e != hipSuccess) { dfree(q); return e; }
+        dfree(s.p);
+        s.p = q; s.bytes = bytes;
+        return hipSuccess;
+    }
     bool clock_armed = false;
-    unsigned long long* clock_of(int cls) const { return clock_armed ? clock_buf[cls] : nullptr; }
+    unsigned long long* clock_of(int cls) const { return clock_armed ? scratch.clock[cls].as<unsigned long long>() : nullptr; }
     int dbg_cur = 0;  // which ping-pong descriptor buffer the last LightGlue forward ended in (im_debug_read)
 
     int fail(int code, const char* fmt, ...) {
@@ -159,16 +190,12 @@ struct im_ctx {
         if (hipSetDevice((ctx)->device) != hipSuccess) return (ctx)->fail(-3, "hipSetDevice failed"); \
     } while (0)
 
-// launch wrapper: when profiling is on, brackets the launch with two events on its stream
+// launch wrapper: when profiling is on, brackets the launch with two events on its stream (im_ctx::timed). The plain branch is kept apart on
+// purpose: the timed path of the model forwards stays the bare expression, and IM_HIP's message keeps naming it
 #define IM_LAUNCH(ctx, name, stream, expr)                                   \
     do {                                                                     \
         if ((ctx)->prof_on) {                                                \
-            im_ctx::ProfEntry _pe{name, (ctx)->prof_event(), (ctx)->prof_event()}; \
-            (ctx)->prof_stream = (stream);                                   \
-            hipEventRecord(_pe.e0, (stream));                                \
-            hipError_t _le = (expr);                                         \
-            hipEventRecord(_pe.e1, (stream));                                \
-            (ctx)->prof.push_back(_pe);                                      \
+            hipError_t _le = (ctx)->timed(name, (stream), [&] { return (expr); }); \
             IM_HIP(ctx, _le);                                                \
         } else {                                                             \
             IM_HIP(ctx, expr);                                               \
@@ -180,4 +207,12 @@ struct im_ctx {
         hipError_t _e = (expr);                                                                             \
         if (_e != hipSuccess)                                                                               \
             return (ctx)->fail(-100 - (int)_e, "%s:%d: %s -> %s", __FILE__, __LINE__, #expr, hipGetErrorString(_e)); \
+    } while (0)
+
+// `grow_call` = ctx->grow(...) inside an entry point: out of device memory fails with the caller's code and message, any other HIP error as IM_HIP
+#define IM_GROW(ctx, grow_call, code, ...)                                              \
+    do {                                                                                \
+        const hipError_t _g = (grow_call);                                              \
+        if (_g == hipErrorOutOfMemory) return (ctx)->fail((code), __VA_ARGS__);         \
+        IM_HIP(ctx, _g);                                                                \
     } while (0)

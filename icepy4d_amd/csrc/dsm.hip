@@ -341,17 +341,6 @@ hipError_t launch(K kernel, long long blocks, hipStream_t s, A... args) {
     return hipGetLastError();
 }
 
-// scratch of the DSM calls: one byte buffer, grown on demand (the previous one may still be read by queued work: sync first)
-char* dsm_scratch(im_ctx* ctx, size_t bytes, hipStream_t s) {
-    if (ctx->dsm_scratch_bytes >= bytes) return ctx->dsm_scratch;
-    if (ctx->dsm_scratch) {
-        if (hipStreamSynchronize(s) != hipSuccess) return nullptr;
-        ctx->dfree(ctx->dsm_scratch);
-    }
-    ctx->dsm_scratch = ctx->dalloc<char>(bytes, "dsm.scratch");
-    ctx->dsm_scratch_bytes = ctx->dsm_scratch ? bytes : 0;
-    return ctx->dsm_scratch;
-}
 size_t up256(size_t b) { return (b + 255) & ~size_t(255); }
 
 template <typename S>
@@ -394,8 +383,8 @@ extern "C" int im_dsm_group_mean(im_ctx* ctx, const double* d_pts, const float* 
     }
     const long long nb = blocks_of(n, SCAN_THREADS);
     const size_t o_sums = 0, o_starts = up256(nb * sizeof(long long)), o_first = o_starts + up256(n * sizeof(long long));
-    char* sc = dsm_scratch(ctx, o_first + 256, s);
-    if (!sc) return ctx->fail(-71, "im_dsm_group_mean: out of device memory");
+    IM_GROW(ctx, ctx->grow(ctx->scratch.dsm, o_first + 256, "dsm.scratch"), -71, "im_dsm_group_mean: out of device memory");
+    char* const sc = ctx->scratch.dsm.as<char>();
     long long* sums = reinterpret_cast<long long*>(sc + o_sums);
     long long* starts = reinterpret_cast<long long*>(sc + o_starts);
     int* first = reinterpret_cast<int*>(sc + o_first);
@@ -426,8 +415,8 @@ extern "C" int im_dsm_rasterize(im_ctx* ctx, const float* d_bx, const float* d_b
     const long long T = n_simplices, nb = blocks_of(std::max(T, 1LL), SCAN_THREADS);
     const size_t o_win = 0, o_offs = up256(cells * sizeof(int)), o_sums = o_offs + up256(std::max(T, 1LL) * sizeof(long long));
     const size_t o_total = o_sums + up256(nb * sizeof(long long));
-    char* sc = dsm_scratch(ctx, o_total + 256, s);
-    if (!sc) return ctx->fail(-71, "im_dsm_rasterize: out of device memory (%lld cells)", cells);
+    IM_GROW(ctx, ctx->grow(ctx->scratch.dsm, o_total + 256, "dsm.scratch"), -71, "im_dsm_rasterize: out of device memory (%lld cells)", cells);
+    char* const sc = ctx->scratch.dsm.as<char>();
     int* win = reinterpret_cast<int*>(sc + o_win);
     long long* offs = reinterpret_cast<long long*>(sc + o_offs);
     long long* sums = reinterpret_cast<long long*>(sc + o_sums);

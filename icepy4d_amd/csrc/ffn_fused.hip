@@ -5,9 +5,7 @@
 // It replaces three launches (ffn.0 GEMM, LayerNorm + GELU, ffn.3 GEMM + residual) and the two HBM round trips of the 512-wide
 // hidden rows (3 x 16.8 MB per launch at 2 x 4096 keypoints).
 //
-// Round 5: both products run on the bf16 matrix cores with fp32 accuracy, as the attention does (attention_bx.hip: an fp32 value is the
-// exact sum of three bf16 values, six bf16 products per fp32 product, fp32 accumulation; error at or below the f32-input MFMA chain's,
-// profiles/r05_bf16x_probe.txt). The weights are cut into their three planes on the host, once per weight set; the rows are cut when
+// Round 5: both products run on the bf16 matrix cores with fp32 accuracy, as the attention does (bf16x3.h). The weights are cut into their three planes on the host, once per weight set; the rows are cut when
 // they are written to LDS - the inputs by the staging pass, the hidden rows by the LayerNorm / GELU pass - so every value is cut once.
 //
 // A block owns 32 rows of one image and holds them in LDS for the whole kernel: first [x | att] as three bf16 planes (32 x 512 each),
@@ -18,6 +16,7 @@
 // straight into registers, double-buffered one 32-deep k chunk (24 / 12 MFMAs per wave) ahead.
 //
 // LayerNorm is the two-pass form of lg_misc.hip's layernorm_gelu_kernel (mean, then centred sum of squares, eps 1e-5, erf GELU).
+#include "bf16x3.h"
 #include "common.h"
 #include "kernels.h"
 #include "sp_post.h"
@@ -37,25 +36,7 @@ constexpr int PS = 1040;            // bytes per row of a bf16 plane: 512 x 2 + 
 constexpr int PLANE = BM * PS;      // 33,280 bytes
 constexpr int LDS_BYTES = 3 * PLANE;                    // 99,840 (>= BM * LD * 4 = 66,048)
 constexpr unsigned TILE_BYTES = (512 / 16) * 3 * 1024;  // one packed 32-column tile at K = 512: 32 k chunks x 3 planes x 1 KiB
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 }  // namespace ff
-
-// host: fp32 -> bf16, round to nearest even (what v_cvt_pk_bf16_f32 does); the weights are finite
-static inline uint16_t host_bf16(float x) {
-    uint32_t u;
-    memcpy(&u, &x, 4);
-    u += 0x7FFFu + ((u >> 16) & 1u);
-    return (uint16_t)(u >> 16);
-}
-static inline float host_bf16_to_float(uint16_t h) {
-    const uint32_t u = (uint32_t)h << 16;
-    float f;
-    memcpy(&f, &u, 4);
-    return f;
-}
 
 // Fragment-order packing of a row-major W[N][K] as three bf16 planes (host side, once per weight set):
 //   out[tile = n / 32][chunk = k / 16][plane][lane = hh * 32 + c][j] = plane of W[tile * 32 + c][16 chunk + 8 hh + j],  j = 0..7
@@ -70,11 +51,8 @@ std::vector<float> pack_frag_weights(const float* w, int n, int k) {
             for (int lane = 0; lane < 64; ++lane)
                 for (int j = 0; j < 8; ++j) {
                     const float x = w[(size_t)(t * 32 + (lane & 31)) * k + 16 * ch + 8 * (lane >> 5) + j];
-                    const uint16_t h = host_bf16(x);
-                    const float r1 = x - host_bf16_to_float(h);
-                    const uint16_t m = host_bf16(r1);
-                    const float r2 = r1 - host_bf16_to_float(m);
-                    const uint16_t l = host_bf16(r2);
+                    uint16_t h, m, l;
+                    cut3(x, h, m, l);
                     const size_t base = (((size_t)t * chunks + ch) * 3) * 512 + (size_t)lane * 8 + j;     // in bf16 elements; a plane block = 64 x 8
                     o[base] = h; o[base + 512] = m; o[base + 1024] = l;
                 }
@@ -82,21 +60,6 @@ std::vector<float> pack_frag_weights(const float* w, int n, int k) {
 }
 
 namespace ff {
-__device__ __forceinline__ f32x16 mfma_bf(u32x4 a, u32x4 b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
-__device__ __forceinline__ unsigned cvt_pk(float a, float b) {
-    const bf16x2 v = __builtin_convertvector(f32x2{a, b}, bf16x2);
-    return __builtin_bit_cast(unsigned, v);
-}
-__device__ __forceinline__ void split2(float a, float b, unsigned& h, unsigned& m, unsigned& l) {
-    h = cvt_pk(a, b);
-    float ra = a - __uint_as_float(h << 16), rb = b - __uint_as_float(h & 0xffff0000u);
-    m = cvt_pk(ra, rb);
-    ra -= __uint_as_float(m << 16);
-    rb -= __uint_as_float(m & 0xffff0000u);
-    l = cvt_pk(ra, rb);
-}
 // four consecutive row values -> 8 bytes in each plane
 template <int PLANE_BYTES = PLANE>
 __device__ __forceinline__ void put4(unsigned char* plane0, int off, float4 x) {
@@ -139,10 +102,10 @@ __global__ __launch_bounds__(ff::NT, 2) void ffn_fused_kernel(FfnArgs a) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // in an SGPR: everything derived from it is wave-uniform
     const int c = lane & 31, hh = lane >> 5;
 
-    const __amdgpu_buffer_rsrc_t rX = gmake_rsrc(a.x + (long)z * a.x_bstride, (unsigned)M * 1024u);
-    const __amdgpu_buffer_rsrc_t rAtt = gmake_rsrc(a.att + (long)z * a.att_bstride, (unsigned)M * 1024u);
-    const __amdgpu_buffer_rsrc_t rW0 = gmake_rsrc(a.w0p, 512u * 512u * 6u);
-    const __amdgpu_buffer_rsrc_t rW3 = gmake_rsrc(a.w3p, 256u * 512u * 6u);
+    const __amdgpu_buffer_rsrc_t rX = make_rsrc(a.x + (long)z * a.x_bstride, (unsigned)M * 1024u);
+    const __amdgpu_buffer_rsrc_t rAtt = make_rsrc(a.att + (long)z * a.att_bstride, (unsigned)M * 1024u);
+    const __amdgpu_buffer_rsrc_t rW0 = make_rsrc(a.w0p, 512u * 512u * 6u);
+    const __amdgpu_buffer_rsrc_t rW3 = make_rsrc(a.w3p, 256u * 512u * 6u);
 
     // a weight chunk = 32 k = two MFMA k chunks x three planes (x two column tiles in the first product): 16-byte loads, 1 KiB per wave each
     const unsigned vb0 = (unsigned)(2 * wave) * TILE_BYTES + lane * 16u;
@@ -177,7 +140,7 @@ __global__ __launch_bounds__(ff::NT, 2) void ffn_fused_kernel(FfnArgs a) {
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
             const int idx = tid + i * NT, row = idx >> 7, c4 = idx & 63;
-            v[i] = gbuf_load4(second ? rAtt : rX, (unsigned)((m0 + row) * 256 + c4 * 4) * 4u, 0);
+            v[i] = buf_load4(second ? rAtt : rX, (unsigned)((m0 + row) * 256 + c4 * 4) * 4u, 0);
         }
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
@@ -326,10 +289,10 @@ __global__ __launch_bounds__(ff::NT, 4) void ffn_fused_split_kernel(FfnArgs a) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // in an SGPR: everything derived from it is wave-uniform
     const int c = lane & 31, hh = lane >> 5;
 
-    const __amdgpu_buffer_rsrc_t rX = gmake_rsrc(a.x + (long)z * a.x_bstride, (unsigned)M * 1024u);
-    const __amdgpu_buffer_rsrc_t rAtt = gmake_rsrc(a.att + (long)z * a.att_bstride, (unsigned)M * 1024u);
-    const __amdgpu_buffer_rsrc_t rW0 = gmake_rsrc(a.w0p, 512u * 512u * 6u);
-    const __amdgpu_buffer_rsrc_t rW3 = gmake_rsrc(a.w3p, 256u * 512u * 6u);
+    const __amdgpu_buffer_rsrc_t rX = make_rsrc(a.x + (long)z * a.x_bstride, (unsigned)M * 1024u);
+    const __amdgpu_buffer_rsrc_t rAtt = make_rsrc(a.att + (long)z * a.att_bstride, (unsigned)M * 1024u);
+    const __amdgpu_buffer_rsrc_t rW0 = make_rsrc(a.w0p, 512u * 512u * 6u);
+    const __amdgpu_buffer_rsrc_t rW3 = make_rsrc(a.w3p, 256u * 512u * 6u);
 
     // a weight step = one MFMA k chunk (16 of the 512 k) x three planes (x two column tiles in the first product): 16-byte loads, 1 KiB per wave each,
     // double-buffered one step (12 / 6 MFMAs per wave) ahead
@@ -364,7 +327,7 @@ __global__ __launch_bounds__(ff::NT, 4) void ffn_fused_split_kernel(FfnArgs a) {
 #define FF_FETCH(rsrc_)                                                                                  \
     _Pragma("unroll") for (int i = 0; i < 4; ++i) {                                                      \
         const int idx = tid + i * NT;                                                                    \
-        v[i] = gbuf_load4(rsrc_, (unsigned)((m0 + (idx >> 6)) * 256 + (idx & 63) * 4) * 4u, 0);          \
+        v[i] = buf_load4(rsrc_, (unsigned)((m0 + (idx >> 6)) * 256 + (idx & 63) * 4) * 4u, 0);          \
     }
 #define FF_PUT_IN()                                                                                      \
     _Pragma("unroll") for (int i = 0; i < 4; ++i) {                                                      \

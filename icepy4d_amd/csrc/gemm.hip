@@ -13,33 +13,14 @@
 // permuted (lane-half h reads k = h BK/2 .. contiguously) so that one 16-byte LDS read feeds four
 // MFMAs; A and B use the same permutation, so the product is unchanged up to summation order.
 // Global loads of slab t+1 are issued before the MFMAs of slab t (register staging).
+#include "bf16x3.h"
 #include "common.h"
 #include "kernels.h"
 #include "sp_post.h"
 
 namespace im {
 
-typedef unsigned int gu32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int gu32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 gbf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 gbf16x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ f32x16 gmfma_bf(gu32x4 a, gu32x4 b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(gbf16x8, a), __builtin_bit_cast(gbf16x8, b), c, 0, 0, 0);
-}
-__device__ __forceinline__ unsigned gcvt_pk(float a, float b) {
-    const gbf16x2 v = __builtin_convertvector(f32x2{a, b}, gbf16x2);
-    return __builtin_bit_cast(unsigned, v);
-}
-__device__ __forceinline__ void gsplit2(float a, float b, unsigned& h, unsigned& m, unsigned& l) {
-    h = gcvt_pk(a, b);
-    float ra = a - __uint_as_float(h << 16), rb = b - __uint_as_float(h & 0xffff0000u);
-    m = gcvt_pk(ra, rb);
-    ra -= __uint_as_float(m << 16);
-    rb -= __uint_as_float(m & 0xffff0000u);
-    l = gcvt_pk(ra, rb);
-}
-
-// BX (round 5, GemmArgs::bx): the product on the bf16 matrix cores with fp32 accuracy, as attention_bx.hip - the fp32 tiles are cut into three
+// BX (round 5, GemmArgs::bx): the product on the bf16 matrix cores with fp32 accuracy (bf16x3.h) - the fp32 tiles are cut into three
 // bf16 planes as they are written to LDS (row stride 80 bytes: conflict-free 16-byte fragment reads), six v_mfma_f32_32x32x16_bf16 per 16 k
 // and tile pair, small products first; everything around the slab loop (block map, staging loads, epilogues) is shared with the f32 form.
 template <int BM, int BN, int BK, int EPI, bool BX>
@@ -92,9 +73,9 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel(GemmArgs a) {
     // stored), lane offsets fixed for the whole kernel, the slab is a scalar offset - no address arithmetic on the VALU,
     // which on gfx950 would cost matrix-pipe time (tools/mfma_peak.hip).
     static_assert((A_IT == 1 || A_IT == 2 || A_IT == 4) && (B_IT == 1 || B_IT == 2 || B_IT == 4), "staging registers");
-    const __amdgpu_buffer_rsrc_t rA0 = gmake_rsrc(A0, (unsigned)M * a.lda * 4u);
-    const __amdgpu_buffer_rsrc_t rA1 = gmake_rsrc(A1 ? A1 : A0, A1 ? (unsigned)M * a.lda1 * 4u : 0u);
-    const __amdgpu_buffer_rsrc_t rW = gmake_rsrc(Wp, (unsigned)Nlive * a.ldw * 4u);
+    const __amdgpu_buffer_rsrc_t rA0 = make_rsrc(A0, (unsigned)M * a.lda * 4u);
+    const __amdgpu_buffer_rsrc_t rA1 = make_rsrc(A1 ? A1 : A0, A1 ? (unsigned)M * a.lda1 * 4u : 0u);
+    const __amdgpu_buffer_rsrc_t rW = make_rsrc(Wp, (unsigned)Nlive * a.ldw * 4u);
     unsigned va0[A_IT], va1[A_IT], vb[B_IT];
 #pragma unroll
     for (int i = 0; i < A_IT; ++i) {
@@ -106,8 +87,8 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel(GemmArgs a) {
     for (int i = 0; i < B_IT; ++i) vb[i] = ((unsigned)(n0 + (tid + i * 256) / F4) * a.ldw + ((tid + i * 256) % F4) * 4) * 4u;
     float4 ra0, ra1, ra2, ra3, rb0, rb1, rb2, rb3;
     ra1 = ra2 = ra3 = rb1 = rb2 = rb3 = make_float4(0.f, 0.f, 0.f, 0.f);
-#define IM_LD_A(i) gbuf_load4(second_ ? rA1 : rA0, second_ ? va1[i] : va0[i], so_)
-#define IM_LD_B(i, k0_) gbuf_load4(rW, vb[i], (k0_) * 4u)
+#define IM_LD_A(i) buf_load4(second_ ? rA1 : rA0, second_ ? va1[i] : va0[i], so_)
+#define IM_LD_B(i, k0_) buf_load4(rW, vb[i], (k0_) * 4u)
 #define IM_LOAD_SLAB(k0_)                                                                  \
     {                                                                                      \
         const bool second_ = A1 && (k0_) >= a.ksplit;                                      \
@@ -128,17 +109,17 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel(GemmArgs a) {
 #else
         const bool skip_ = plane0 == xB;
 #endif
-        if (skip_) { h0 = gcvt_pk(x.x, x.y); h1 = gcvt_pk(x.z, x.w); m0 = l0 = m1 = l1 = 0u; }     // bf16-accurate values: the data-dependent flow stays
+        if (skip_) { h0 = cvt_pk(x.x, x.y); h1 = cvt_pk(x.z, x.w); m0 = l0 = m1 = l1 = 0u; }     // bf16-accurate values: the data-dependent flow stays
         else
 #endif
         {
-        gsplit2(x.x, x.y, h0, m0, l0);
-        gsplit2(x.z, x.w, h1, m1, l1);
+        split2(x.x, x.y, h0, m0, l0);
+        split2(x.z, x.w, h1, m1, l1);
         }
         unsigned char* d = plane0 + ((tid + i * 256) / F4) * XS + ((tid + i * 256) % F4) * 8;
-        *reinterpret_cast<gu32x2*>(d) = gu32x2{h0, h1};
-        *reinterpret_cast<gu32x2*>(d + plane_bytes) = gu32x2{m0, m1};
-        *reinterpret_cast<gu32x2*>(d + 2 * plane_bytes) = gu32x2{l0, l1};
+        *reinterpret_cast<u32x2*>(d) = u32x2{h0, h1};
+        *reinterpret_cast<u32x2*>(d + plane_bytes) = u32x2{m0, m1};
+        *reinterpret_cast<u32x2*>(d + 2 * plane_bytes) = u32x2{l0, l1};
     };
 #define IM_ST(buf, i, r)                                                              \
     {                                                                                 \
@@ -159,27 +140,27 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel(GemmArgs a) {
         if constexpr (BX) {
 #pragma unroll
             for (int kc = 0; kc < BK / 16; ++kc) {
-                gu32x4 fa[MB][3], fb[NB][3];
+                u32x4 fa[MB][3], fb[NB][3];
 #pragma unroll
                 for (int i = 0; i < MB; ++i)
 #pragma unroll
                     for (int pl = 0; pl < 3; ++pl)
-                        fa[i][pl] = *reinterpret_cast<const gu32x4*>(xA + pl * XPA + (wm0 + i * 32 + c) * XS + kc * 32 + hh * 16);
+                        fa[i][pl] = *reinterpret_cast<const u32x4*>(xA + pl * XPA + (wm0 + i * 32 + c) * XS + kc * 32 + hh * 16);
 #pragma unroll
                 for (int j = 0; j < NB; ++j)
 #pragma unroll
                     for (int pl = 0; pl < 3; ++pl)
-                        fb[j][pl] = *reinterpret_cast<const gu32x4*>(xB + pl * XPB + (wn0 + j * 32 + c) * XS + kc * 32 + hh * 16);
+                        fb[j][pl] = *reinterpret_cast<const u32x4*>(xB + pl * XPB + (wn0 + j * 32 + c) * XS + kc * 32 + hh * 16);
 #pragma unroll
                 for (int i = 0; i < MB; ++i)
 #pragma unroll
                     for (int j = 0; j < NB; ++j) {
-                        acc[i][j] = gmfma_bf(fa[i][0], fb[j][2], acc[i][j]);
-                        acc[i][j] = gmfma_bf(fa[i][2], fb[j][0], acc[i][j]);
-                        acc[i][j] = gmfma_bf(fa[i][1], fb[j][1], acc[i][j]);
-                        acc[i][j] = gmfma_bf(fa[i][0], fb[j][1], acc[i][j]);
-                        acc[i][j] = gmfma_bf(fa[i][1], fb[j][0], acc[i][j]);
-                        acc[i][j] = gmfma_bf(fa[i][0], fb[j][0], acc[i][j]);
+                        acc[i][j] = mfma_bf(fa[i][0], fb[j][2], acc[i][j]);
+                        acc[i][j] = mfma_bf(fa[i][2], fb[j][0], acc[i][j]);
+                        acc[i][j] = mfma_bf(fa[i][1], fb[j][1], acc[i][j]);
+                        acc[i][j] = mfma_bf(fa[i][0], fb[j][1], acc[i][j]);
+                        acc[i][j] = mfma_bf(fa[i][1], fb[j][0], acc[i][j]);
+                        acc[i][j] = mfma_bf(fa[i][0], fb[j][0], acc[i][j]);
                     }
             }
         } else
@@ -224,12 +205,12 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel(GemmArgs a) {
             const float bv = (bias && col_ok) ? bias[col] : 0.f;
             const unsigned rowl = m0 + wm0 + i * 32 + 4 * hh; // row of register 0 of this lane
             if constexpr (EPI == EPI_BIAS || EPI == EPI_BIAS_RELU || EPI == EPI_BIAS_RESID) {
-                const __amdgpu_buffer_rsrc_t rC = gmake_rsrc(a.C + (long)z * a.c_bstride, (unsigned)M * a.ldc * 4u);
+                const __amdgpu_buffer_rsrc_t rC = make_rsrc(a.C + (long)z * a.c_bstride, (unsigned)M * a.ldc * 4u);
                 const unsigned vo = col_ok ? (rowl * a.ldc + col) * 4u : OOB;
                 const unsigned rstep = (unsigned)a.ldc * 4u;
                 float rv[16];
                 if constexpr (EPI == EPI_BIAS_RESID) {
-                    const __amdgpu_buffer_rsrc_t rR = gmake_rsrc(a.R + (long)z * a.r_bstride, (unsigned)M * a.ldr * 4u);
+                    const __amdgpu_buffer_rsrc_t rR = make_rsrc(a.R + (long)z * a.r_bstride, (unsigned)M * a.ldr * 4u);
                     const unsigned vr = col_ok ? (rowl * a.ldr + col) * 4u : OOB;
 #pragma unroll
                     for (int r = 0; r < 16; ++r)
@@ -250,7 +231,7 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel(GemmArgs a) {
                 float* dst = a.q;
                 if constexpr (EPI == EPI_QKV_ROPE) dst = which == 0 ? a.q : (which == 1 ? a.k : a.v);
                 if constexpr (EPI == EPI_HEADS_QV) dst = which ? a.v : a.q;
-                const __amdgpu_buffer_rsrc_t rD = gmake_rsrc(dst + (long)z * a.head_bstride + (long)(hd >> 6) * a.head_stride, (unsigned)M * 256u);
+                const __amdgpu_buffer_rsrc_t rD = make_rsrc(dst + (long)z * a.head_bstride + (long)(hd >> 6) * a.head_stride, (unsigned)M * 256u);
                 const int d = (hd & 63) + c;
                 const unsigned vo = col_ok ? (rowl * 64 + d) * 4u : OOB;
                 float scale = a.alpha;
@@ -260,8 +241,8 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel(GemmArgs a) {
                 if (rope) {
                     // rotary (`lightglue/lightglue.py:49-57`): pairs (2i, 2i+1) share a frequency;
                     // out = t * cos + rotate_half(t) * sin, rotate_half: (x0, x1) -> (-x1, x0)
-                    const __amdgpu_buffer_rsrc_t rCs = gmake_rsrc(a.cs + (long)z * a.enc_bstride, (unsigned)M * 128u);
-                    const __amdgpu_buffer_rsrc_t rSn = gmake_rsrc(a.sn + (long)z * a.enc_bstride, (unsigned)M * 128u);
+                    const __amdgpu_buffer_rsrc_t rCs = make_rsrc(a.cs + (long)z * a.enc_bstride, (unsigned)M * 128u);
+                    const __amdgpu_buffer_rsrc_t rSn = make_rsrc(a.sn + (long)z * a.enc_bstride, (unsigned)M * 128u);
                     const unsigned ve = (rowl * 32 + (d >> 1)) * 4u;
 #pragma unroll
                     for (int r = 0; r < 16; ++r) {
@@ -323,13 +304,13 @@ __global__ __launch_bounds__(pr::NT, 4) void proj_rows_kernel(GemmArgs a) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int c = lane & 31, hh = lane >> 5;
-    const __amdgpu_buffer_rsrc_t rX = gmake_rsrc(a.A + (long)z * a.a_bstride, (unsigned)M * 1024u);
-    const __amdgpu_buffer_rsrc_t rW = gmake_rsrc(a.wp, (unsigned)a.N * 256u * 6u);
+    const __amdgpu_buffer_rsrc_t rX = make_rsrc(a.A + (long)z * a.a_bstride, (unsigned)M * 1024u);
+    const __amdgpu_buffer_rsrc_t rW = make_rsrc(a.wp, (unsigned)a.N * 256u * 6u);
 
     P_STAMP(0)
     // weight steps (one 16-deep k chunk of one column tile = three 1 KB loads) run THREE steps ahead through four register buffers: the step index s = 16 j + kc
     // walks this wave's tiles j * 8 + wave; steps past the last tile are out of the descriptor's range by their lane offset (zeros, no traffic, no branch)
-    gu32x4 b0[3], b1[3], b2[3], b3[3];
+    u32x4 b0[3], b1[3], b2[3], b3[3];
 #define PR_LOAD(b_, s_)                                                                                                          \
     {                                                                                                                            \
         const bool in_ = (s_) < TILES * 16;                                                                                      \
@@ -345,18 +326,18 @@ __global__ __launch_bounds__(pr::NT, 4) void proj_rows_kernel(GemmArgs a) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int idx = tid + i * NT;
-            v[i] = gbuf_load4(rX, (unsigned)((m0 + (idx >> 6)) * 256 + (idx & 63) * 4) * 4u, 0);
+            v[i] = buf_load4(rX, (unsigned)((m0 + (idx >> 6)) * 256 + (idx & 63) * 4) * 4u, 0);
         }
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int idx = tid + i * NT;
             unsigned h0, m0_, l0, h1, m1, l1;
-            gsplit2(v[i].x, v[i].y, h0, m0_, l0);
-            gsplit2(v[i].z, v[i].w, h1, m1, l1);
+            split2(v[i].x, v[i].y, h0, m0_, l0);
+            split2(v[i].z, v[i].w, h1, m1, l1);
             unsigned char* d = psm + (idx >> 6) * PS + (idx & 63) * 8;
-            *reinterpret_cast<gu32x2*>(d) = gu32x2{h0, h1};
-            *reinterpret_cast<gu32x2*>(d + PLANE) = gu32x2{m0_, m1};
-            *reinterpret_cast<gu32x2*>(d + 2 * PLANE) = gu32x2{l0, l1};
+            *reinterpret_cast<u32x2*>(d) = u32x2{h0, h1};
+            *reinterpret_cast<u32x2*>(d + PLANE) = u32x2{m0_, m1};
+            *reinterpret_cast<u32x2*>(d + 2 * PLANE) = u32x2{l0, l1};
         }
     }
     __syncthreads();
@@ -365,14 +346,14 @@ __global__ __launch_bounds__(pr::NT, 4) void proj_rows_kernel(GemmArgs a) {
 #define PR_SIX(b_, kc_)                                                                                              \
     {                                                                                                                \
         const unsigned char* ap = psm + c * PS + ((kc_) * 16 + hh * 8) * 2;                                          \
-        const gu32x4 ah = *reinterpret_cast<const gu32x4*>(ap), am = *reinterpret_cast<const gu32x4*>(ap + PLANE),   \
-                     al = *reinterpret_cast<const gu32x4*>(ap + 2 * PLANE);                                          \
-        acc = gmfma_bf(ah, b_[2], acc);                                                                              \
-        acc = gmfma_bf(al, b_[0], acc);                                                                              \
-        acc = gmfma_bf(am, b_[1], acc);                                                                              \
-        acc = gmfma_bf(ah, b_[1], acc);                                                                              \
-        acc = gmfma_bf(am, b_[0], acc);                                                                              \
-        acc = gmfma_bf(ah, b_[0], acc);                                                                              \
+        const u32x4 ah = *reinterpret_cast<const u32x4*>(ap), am = *reinterpret_cast<const u32x4*>(ap + PLANE),   \
+                     al = *reinterpret_cast<const u32x4*>(ap + 2 * PLANE);                                          \
+        acc = mfma_bf(ah, b_[2], acc);                                                                              \
+        acc = mfma_bf(al, b_[0], acc);                                                                              \
+        acc = mfma_bf(am, b_[1], acc);                                                                              \
+        acc = mfma_bf(ah, b_[1], acc);                                                                              \
+        acc = mfma_bf(am, b_[0], acc);                                                                              \
+        acc = mfma_bf(ah, b_[0], acc);                                                                              \
     }
 #pragma unroll 1
     for (int j = 0; j < TILES; ++j) {
@@ -411,7 +392,7 @@ __global__ __launch_bounds__(pr::NT, 4) void proj_rows_kernel(GemmArgs a) {
         float* dst = a.q;
         if constexpr (EPI == EPI_QKV_ROPE) dst = which == 0 ? a.q : (which == 1 ? a.k : a.v);
         if constexpr (EPI == EPI_HEADS_QV) dst = which ? a.v : a.q;
-        const __amdgpu_buffer_rsrc_t rD = gmake_rsrc(dst + (long)z * a.head_bstride + (long)(hd >> 6) * a.head_stride, (unsigned)M * 256u);
+        const __amdgpu_buffer_rsrc_t rD = make_rsrc(dst + (long)z * a.head_bstride + (long)(hd >> 6) * a.head_stride, (unsigned)M * 256u);
         const int d = (hd & 63) + c;
         const unsigned vo = (rowl * 64 + d) * 4u;
         float scale = a.alpha;
@@ -419,8 +400,8 @@ __global__ __launch_bounds__(pr::NT, 4) void proj_rows_kernel(GemmArgs a) {
         if constexpr (EPI == EPI_HEADS_QV) scale = which ? 1.f : a.alpha;
         const bool rope = EPI == EPI_QKV_ROPE && which < 2 && a.cs;
         if (rope) {
-            const __amdgpu_buffer_rsrc_t rCs = gmake_rsrc(a.cs + (long)z * a.enc_bstride, (unsigned)M * 128u);
-            const __amdgpu_buffer_rsrc_t rSn = gmake_rsrc(a.sn + (long)z * a.enc_bstride, (unsigned)M * 128u);
+            const __amdgpu_buffer_rsrc_t rCs = make_rsrc(a.cs + (long)z * a.enc_bstride, (unsigned)M * 128u);
+            const __amdgpu_buffer_rsrc_t rSn = make_rsrc(a.sn + (long)z * a.enc_bstride, (unsigned)M * 128u);
             const unsigned ve = (rowl * 32 + (d >> 1)) * 4u;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {

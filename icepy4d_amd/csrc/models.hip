@@ -706,20 +706,17 @@ int im_debug_clock_probe(im_ctx* ctx, int arm, double* h_out, void* stream) {
     hipStream_t s = (hipStream_t)stream;
     const size_t bytes = (size_t)CLOCK_PROBE_SLOTS * 2 * sizeof(unsigned long long);
     if (arm == 1) {
-        if (!ctx->clock_buf[0]) {
-            ctx->clock_buf[0] = ctx->dalloc<unsigned long long>((size_t)CLOCK_PROBE_SLOTS * 2, "clock_probe_attention");
-            ctx->clock_buf[1] = ctx->dalloc<unsigned long long>((size_t)CLOCK_PROBE_SLOTS * 2, "clock_probe_convolution");
-            if (!ctx->clock_buf[0] || !ctx->clock_buf[1]) return ctx->fail(-22, "im_debug_clock_probe: allocation failed");
-        }
-        IM_HIP(ctx, hipMemsetAsync(ctx->clock_buf[0], 0, bytes, s));
-        IM_HIP(ctx, hipMemsetAsync(ctx->clock_buf[1], 0, bytes, s));
+        IM_GROW(ctx, ctx->grow(ctx->scratch.clock[0], bytes, "clock_probe_attention"), -22, "im_debug_clock_probe: allocation failed");
+        IM_GROW(ctx, ctx->grow(ctx->scratch.clock[1], bytes, "clock_probe_convolution"), -22, "im_debug_clock_probe: allocation failed");
+        IM_HIP(ctx, hipMemsetAsync(ctx->scratch.clock[0].p, 0, bytes, s));
+        IM_HIP(ctx, hipMemsetAsync(ctx->scratch.clock[1].p, 0, bytes, s));
         IM_HIP(ctx, hipStreamSynchronize(s));
         ctx->clock_armed = true;
         return 0;
     }
-    if (!ctx->clock_buf[0] || !h_out) return ctx->fail(-51, "im_debug_clock_probe: not armed");
+    if (!ctx->scratch.clock[0].p || !h_out) return ctx->fail(-51, "im_debug_clock_probe: not armed");
     std::vector<unsigned long long> h((size_t)CLOCK_PROBE_SLOTS * 2);
-    unsigned long long* src[2] = {ctx->clock_buf[0], ctx->clock_buf[1]};
+    const void* src[2] = {ctx->scratch.clock[0].p, ctx->scratch.clock[1].p};
     for (int c = 0; c < 2; ++c) {
         IM_HIP(ctx, hipMemcpyAsync(h.data(), src[c], bytes, hipMemcpyDeviceToHost, s));
         IM_HIP(ctx, hipStreamSynchronize(s));

@@ -196,10 +196,10 @@ __global__ __launch_bounds__(SK4_T, 1) void sinkhorn_fused4_kernel(const float* 
     {
         // v -> LDS (times log2 e, masked columns very negative): eight range-checked 16-byte loads in flight per lane. As `j < n ? v[j] : ..`
         // per element this was 32 dword loads behind 32 exec-masked branches, each waited for on its own: ~9 us of every launch (round 5)
-        const __amdgpu_buffer_rsrc_t rv = gmake_rsrc(v, (unsigned)n * 4u);
+        const __amdgpu_buffer_rsrc_t rv = make_rsrc(v, (unsigned)n * 4u);
         float4 vq[SK4_Q];
 #pragma unroll
-        for (int q = 0; q < SK4_Q; ++q) vq[q] = gbuf_load4(rv, voff, (unsigned)q * (SK4_T * 16u));
+        for (int q = 0; q < SK4_Q; ++q) vq[q] = buf_load4(rv, voff, (unsigned)q * (SK4_T * 16u));
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int q = 0; q < SK4_Q; ++q) {
@@ -218,9 +218,9 @@ __global__ __launch_bounds__(SK4_T, 1) void sinkhorn_fused4_kernel(const float* 
     // the same and return zeros that nothing uses (weight 0 in `step`). No branch here: with the dustbin row filled in behind `if (row >= m)`
     // the two paths met in register copies right behind the loads, i.e. every prefetched row was waited for as soon as it had been requested.
     auto load_row = [&](int row, float4 (&buf)[SK4_Q]) {
-        const __amdgpu_buffer_rsrc_t rs = gmake_rsrc(sim + (long)min(row, m - 1) * ld, row < m ? (unsigned)n * 4u : 0u);
+        const __amdgpu_buffer_rsrc_t rs = make_rsrc(sim + (long)min(row, m - 1) * ld, row < m ? (unsigned)n * 4u : 0u);
 #pragma unroll
-        for (int q = 0; q < SK4_Q; ++q) buf[q] = gbuf_load4(rs, voff, (unsigned)q * (SK4_T * 16u));
+        for (int q = 0; q < SK4_Q; ++q) buf[q] = buf_load4(rs, voff, (unsigned)q * (SK4_T * 16u));
     };
     // rows iA and iB = iA + G (hasB false: absent); on return A and B hold the exponentials exp2(t - lane maximum)
     auto step = [&](int iA, float4 (&A)[SK4_Q], float4 (&B)[SK4_Q], int parity, bool hasB) {
@@ -700,17 +700,8 @@ int im_superglue_forward(im_ctx* ctx, const float* d_kpts, const float* d_scores
     float* u = ws->uv;
     float* v = ws->uv + voff;
     float* norm = ws->uv + 2 * voff;
-    if (ctx->prof_on) {
-        im_ctx::ProfEntry pe{"sinkhorn", ctx->prof_event(), ctx->prof_event()};
-        hipEventRecord(pe.e0, s);
-        int rc = sinkhorn(ctx, s, ws->sim, K, &st->n[0], &st->n[1], K, K, W.bin_score, conf->sinkhorn_iterations, u, v, norm);
-        hipEventRecord(pe.e1, s);
-        ctx->prof.push_back(pe);
-        if (rc) return rc;
-    } else {
-        int rc = sinkhorn(ctx, s, ws->sim, K, &st->n[0], &st->n[1], K, K, W.bin_score, conf->sinkhorn_iterations, u, v, norm);
-        if (rc) return rc;
-    }
+    if (int rc = ctx->timed("sinkhorn", s, [&] { return sinkhorn(ctx, s, ws->sim, K, &st->n[0], &st->n[1], K, K, W.bin_score, conf->sinkhorn_iterations, u, v, norm); }))
+        return rc;
     AssignArgs a;
     a.mode = 1;
     a.n_pairs = 1;

@@ -342,15 +342,8 @@ extern "C" int im_template_match_oc(im_ctx* ctx, const float* d_a, int ha, int w
     // C of one batch of pairs lives in a scratch buffer of at most 64 Mi floats (grown on demand)
     const long batch = std::max(1L, std::min((long)n_pairs, (64L << 20) / per_pair));
     const size_t need = (size_t)(batch * per_pair);
-    if (ctx->tm_scratch_floats < need) {
-        if (ctx->tm_scratch) {
-            IM_HIP(ctx, hipStreamSynchronize(s));
-            ctx->dfree(ctx->tm_scratch);
-        }
-        ctx->tm_scratch = ctx->dalloc<float>(need, "templatematch.C");
-        ctx->tm_scratch_floats = ctx->tm_scratch ? need : 0;
-        if (!ctx->tm_scratch) return ctx->fail(-71, "im_template_match_oc: out of device memory (%zu floats)", need);
-    }
+    IM_GROW(ctx, ctx->grow(ctx->scratch.tm, need * sizeof(float), "templatematch.C"), -71, "im_template_match_oc: out of device memory (%zu floats)", need);
+    float* const C = ctx->scratch.tm.as<float>();
     const float2* A = reinterpret_cast<const float2*>(d_a);
     const float2* B = reinterpret_cast<const float2*>(d_b);
     const float isign = conj_b ? 1.f : -1.f;
@@ -358,8 +351,8 @@ extern "C" int im_template_match_oc(im_ctx* ctx, const float* d_a, int ha, int w
         const long nb = std::min(batch, (long)n_pairs - p0);
         const long blocks = nb * p.ny * p.nx;
         if (blocks > 0x7fffffffL) return ctx->fail(-72, "im_template_match_oc: too many pairs per launch");
-        IM_LAUNCH(ctx, "tm_corr", s, launch_corr(p, blocks, A, ha, wa, B, hb, wb, d_pairs, d_bidx, n_b, p0, T, S, isign, ctx->tm_scratch, s));
-        IM_LAUNCH(ctx, "tm_peak", s, launch_peak(d_pairs, d_bidx, n_b, p0, nb, T, S, ha, wa, hb, wb, ctx->tm_scratch, (long)n_pairs, d_out, s));
+        IM_LAUNCH(ctx, "tm_corr", s, launch_corr(p, blocks, A, ha, wa, B, hb, wb, d_pairs, d_bidx, n_b, p0, T, S, isign, C, s));
+        IM_LAUNCH(ctx, "tm_peak", s, launch_peak(d_pairs, d_bidx, n_b, p0, nb, T, S, ha, wa, hb, wb, C, (long)n_pairs, d_out, s));
     }
     IM_GUARD_CHECK(ctx, s, "im_template_match_oc");
     return 0;

@@ -131,30 +131,25 @@ int im_merge_tile_matches(im_ctx* ctx, int n_pairs, int max_kpts, const int32_t*
     if (n_pairs < 1 || max_kpts < 1 || !d_matches || !d_slots || !d_off || !h_origin || !d_kp_bank || !d_n_bank || !d_count)
         return ctx->fail(-70, "im_merge_tile_matches: bad arguments");
     const size_t cap = (size_t)n_pairs * max_kpts;
-    if (!ctx->merge) ctx->merge = new MergeScratch();
-    MergeScratch& ms = *ctx->merge;
-    if (cap > ms.cap) {
-        IM_HIP(ctx, hipDeviceSynchronize());
-        ctx->dfree(ms.key); ctx->dfree(ms.skey); ctx->dfree(ms.seq);     // the smaller scratch this replaces
-        ms.key = ms.skey = nullptr; ms.seq = nullptr; ms.cap = 0;
-        ms.key = ctx->dalloc<unsigned long long>(cap, "merge.key");
-        ms.skey = ctx->dalloc<unsigned long long>(cap, "merge.skey");
-        ms.seq = ctx->dalloc<unsigned>(cap, "merge.seq");
-        if (!ms.count) ms.count = ctx->dalloc<int>(4, "merge.count");
-        if (!ms.key || !ms.skey || !ms.seq || !ms.count) return ctx->fail(-71, "im_merge_tile_matches: out of device memory");
-        ms.cap = cap;
-    }
+    im_ctx::StageScratch& sc = ctx->scratch;
+    IM_GROW(ctx, ctx->grow(sc.merge_key, cap * sizeof(unsigned long long), "merge.key"), -71, "im_merge_tile_matches: out of device memory");
+    IM_GROW(ctx, ctx->grow(sc.merge_skey, cap * sizeof(unsigned long long), "merge.skey"), -71, "im_merge_tile_matches: out of device memory");
+    IM_GROW(ctx, ctx->grow(sc.merge_seq, cap * sizeof(unsigned), "merge.seq"), -71, "im_merge_tile_matches: out of device memory");
+    IM_GROW(ctx, ctx->grow(sc.merge_count, 4 * sizeof(int), "merge.count"), -71, "im_merge_tile_matches: out of device memory");
+    unsigned long long* const key = sc.merge_key.as<unsigned long long>(), *const skey = sc.merge_skey.as<unsigned long long>();
+    unsigned* const seq = sc.merge_seq.as<unsigned>();
+    int* const count = sc.merge_count.as<int>();
     hipStream_t s = (hipStream_t)stream;
     const float4 org = make_float4(h_origin[0], h_origin[1], h_origin[2], h_origin[3]);
-    IM_HIP(ctx, launch_zero_words(ms.count, 4, s));
+    IM_HIP(ctx, launch_zero_words(count, 4, s));
     hipLaunchKernelGGL(tm_collect_kernel, dim3((max_kpts + 255) / 256, n_pairs), dim3(256), 0, s, max_kpts, d_matches, d_slots, d_off, org,
-                       d_kp_bank, d_n_bank, ms.key, ms.seq, ms.count);
+                       d_kp_bank, d_n_bank, key, seq, count);
     const unsigned nb = (unsigned)((cap + RK_T - 1) / RK_T);
-    hipLaunchKernelGGL(tm_first_kernel, dim3(nb), dim3(RK_N), 0, s, ms.key, ms.seq, ms.count, ms.skey);
-    hipLaunchKernelGGL(tm_rank_kernel, dim3(nb), dim3(RK_N), 0, s, ms.skey, ms.seq, ms.count, max_kpts, d_matches, d_slots, d_off, org, d_kp_bank,
+    hipLaunchKernelGGL(tm_first_kernel, dim3(nb), dim3(RK_N), 0, s, key, seq, count, skey);
+    hipLaunchKernelGGL(tm_rank_kernel, dim3(nb), dim3(RK_N), 0, s, skey, seq, count, max_kpts, d_matches, d_slots, d_off, org, d_kp_bank,
                        d_idx0, d_idx1, d_kp0, d_kp1);
     IM_HIP(ctx, hipGetLastError());
-    IM_HIP(ctx, hipMemcpyAsync(d_count, ms.count + 1, sizeof(int), hipMemcpyDeviceToDevice, s));
+    IM_HIP(ctx, hipMemcpyAsync(d_count, count + 1, sizeof(int), hipMemcpyDeviceToDevice, s));
     IM_GUARD_CHECK(ctx, s, "im_merge_tile_matches");
     return 0;
 }
