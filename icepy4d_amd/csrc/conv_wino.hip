@@ -485,11 +485,9 @@ hipError_t launch_conv3x3_wino(const ConvArgs& a, hipStream_t s) {
     if (a.Cin < WCC || a.Cin % WCC != 0 || a.Cout % 64 != 0) return hipErrorInvalidValue;
     // BX (round 6): the products on the bf16 matrix cores whenever the bf16 planes of U are there; IM_CONV_F32=1 (read per call: the parity tests
     // run both forms in one process) or a.f32_form keeps the f32-input form of rounds 2-5, which needs a.w
-    const char* const f32_env = getenv("IM_CONV_F32");
-    const bool bx = a.wx && a.Cin % 16 == 0 && !(a.f32_form || (f32_env && f32_env[0] == '1'));
+    const bool bx = a.wx && a.Cin % 16 == 0 && !(a.f32_form || env_is_1("IM_CONV_F32"));
     if (bx) {
-        const char* const bx2_env = getenv("IM_CONV_BX2");
-        if (!a.img && bx2_env && bx2_env[0] == '1') return launch_conv3x3_wino_bx2(a, s);
+        if (!a.img && env_is_1("IM_CONV_BX2")) return launch_conv3x3_wino_bx2(a, s);
         if (a.img) {
             if (a.Cin != 64 || !a.pool || !a.w1 || !a.b1 || !a.w1q) return hipErrorInvalidValue;     // the model's conv1b: fused first layer, pooled
             return launch_wino<true, true, true, true>(a, s);

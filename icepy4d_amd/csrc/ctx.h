@@ -22,6 +22,13 @@ struct Scratch {
 std::vector<float> pack_conv3x3(const float* w, int cout, int cin);       // [cout][cin][3][3] -> [cin/16][9][cout][16]
 std::vector<float> pack_conv3x3_wino(const float* w, int cout, int cin);  // -> G g G^T as [cin/8][16][cout][8]
 std::vector<float> pack_conv3x3_wino_bx(const float* w, int cout, int cin);  // -> the same values as three bf16 planes in MFMA-fragment order (bytes in floats)
+std::vector<float> pack_layers(const std::vector<float>& src, int n, int k);  // [layers][n][k] -> pack_frag_weights of every layer, one behind the other
+void fold_out_proj_into_ffn0(const float* Wo, const float* bo, float* w0, float* b0);   // weights.hip: one layer, in place
+
+// SuperPoint's nine 3x3 layers behind conv1a: state-dict and profile names, channels
+inline constexpr const char* SP_CONV3[10] = {"conv1b", "conv2a", "conv2b", "conv3a", "conv3b", "conv4a", "conv4b", "convPa", "convDa", nullptr};
+inline constexpr int SP_CIN[9] = {64, 64, 64, 64, 128, 128, 128, 128, 128};
+inline constexpr int SP_COUT[9] = {64, 64, 64, 128, 128, 128, 128, 256, 256};
 
 struct SuperPointW {
     bool ready = false;
@@ -39,16 +46,14 @@ struct LightGlueW {
     float* wr = nullptr;                    // posenc.Wr [32][2]
     // per layer (9): contiguous blocks so that a device-side layer index can select them
     float* qkv_w = nullptr; float* qkv_b = nullptr;      // [L][768][256] rows permuted to [q|k|v][head][d], [L][768]
-    float* sf0_w = nullptr; float* sf0_b = nullptr;      // self ffn.0 [L][512][512] with out_proj folded into columns 256..511
-    float* sln_g = nullptr; float* sln_b = nullptr;      // [L][512]
-    float* sf3_w = nullptr; float* sf3_b = nullptr;      // [L][256][512]
     float* cqv_w = nullptr; float* cqv_b = nullptr;      // cross [to_qk ; to_v] [L][512][256]
-    float* cf0_w = nullptr; float* cf0_b = nullptr;      // cross ffn.0 with to_out folded in
-    float* cln_g = nullptr; float* cln_b = nullptr;
-    float* cf3_w = nullptr; float* cf3_b = nullptr;
     float* qkv_wp = nullptr; float* cqv_wp = nullptr;    // the two projections again as bf16 planes in MFMA-fragment order, per layer (gemm.hip proj_rows_kernel)
-    float* sf0_wp = nullptr; float* sf3_wp = nullptr;    // the four FFN matrices again in MFMA-fragment order (ffn_fused.hip)
-    float* cf0_wp = nullptr; float* cf3_wp = nullptr;
+    struct Ffn {                                         // feed-forward of the self / cross blocks
+        float* w0 = nullptr; float* b0 = nullptr;        // ffn.0 [L][512][512] with out_proj / to_out folded into columns 256..511
+        float* ln_g = nullptr; float* ln_b = nullptr;    // [L][512]
+        float* w3 = nullptr; float* b3 = nullptr;        // [L][256][512]
+        float* w0p = nullptr; float* w3p = nullptr;      // the two matrices again in MFMA-fragment order (ffn_fused.hip)
+    } self_ffn, cross_ffn;
     float* fp_w = nullptr;  float* fp_b = nullptr;       // log_assignment.final_proj [L][256][256], [L][256]
     float* ma_w = nullptr;  float* ma_b = nullptr;       // matchability [L][256], [L]
     float* tc_w = nullptr;  float* tc_b = nullptr;       // token_confidence [L-1][256], [L-1]

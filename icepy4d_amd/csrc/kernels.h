@@ -5,9 +5,17 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <cstdlib>
 #include <vector>
 
 namespace im {
+
+// an A/B or debugging switch of the environment is on: NAME=1 (the IM_ATTN_* switches parse a number themselves). Reads the environment on every
+// call; a site that decides once per process keeps the answer in a function-local static (DESIGN.md section 4 lists which)
+inline bool env_is_1(const char* name) {
+    const char* e = getenv(name);
+    return e && e[0] == '1';
+}
 
 // ------------------------------------------------------------------ gemm.hip
 enum GemmEpi {

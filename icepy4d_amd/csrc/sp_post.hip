@@ -705,7 +705,7 @@ static hipError_t launch_nms_rounds(const float* s, float* out, uint8_t* keep_a,
 }
 
 static bool nms_fusable(int H, int W, int r) {
-    static const bool staged = getenv("IM_NMS_STAGED") && getenv("IM_NMS_STAGED")[0] == '1';   // A/B switch: the five-launch form
+    static const bool staged = env_is_1("IM_NMS_STAGED");   // A/B switch: the five-launch form
     return !staged && r >= 1 && r <= 4 && (W % 4) == 0;
 }
 

@@ -1,8 +1,7 @@
-// SuperGlue (`SuperGlue/models/superglue.py:250-305`): keypoint encoder, 18-layer attentional GNN, score GEMM,
-// log-domain Sinkhorn, mutual filter. The GNN reuses the fp32-MFMA GEMM and flash-attention kernels: SuperGlue's
-// head layout (channel c = d * 4 + head, `view(b, 64, 4, N)` `:111-114`) is absorbed into the packed weights
-// (projection rows and merge columns are permuted to head-major once at load), BatchNorm (eval) is folded into
-// the preceding 1x1 convolution. The Sinkhorn sweeps never materialise the (M+1) x (N+1) coupling matrix:
+// SuperGlue (`SuperGlue/models/superglue.py:250-305`): the Sinkhorn kernels, the forward pass (keypoint encoder, 18-layer
+// attentional GNN, score GEMM, log-domain Sinkhorn, mutual filter) and im_log_optimal_transport. The GNN reuses the GEMM
+// and flash-attention kernels through the block launches of block.h: SuperGlue's head layout and BatchNorm are absorbed
+// into the weights once at load (weights.hip). The Sinkhorn sweeps never materialise the (M+1) x (N+1) coupling matrix:
 // the similarity matrix stays read-only in HBM and the dustbin row / column are the scalar `bin_score`.
 #include <algorithm>
 #include <cmath>
@@ -10,7 +9,7 @@
 #include <cstring>
 
 #include "common.h"
-#include "ctx.h"
+#include "block.h"
 #include "lg_misc.h"
 #include "workspace.h"
 
@@ -431,7 +430,7 @@ static int sinkhorn(im_ctx* ctx, hipStream_t s, const float* sim, int ld, const 
     // single-read form: needs the row in the registers of one block (n <= 16384), 16-byte aligned rows, and as many partial
     // strips as blocks (the workspace holds (K + 15) / 16 + 1 of them). Otherwise (and with IM_SINKHORN_TWO_SWEEP=1, the A/B switch):
     // round 1's row sweep + column sweep, two reads of the couplings per iteration, any size.
-    static const bool two_sweep = getenv("IM_SINKHORN_TWO_SWEEP") && getenv("IM_SINKHORN_TWO_SWEEP")[0] == '1';
+    static const bool two_sweep = env_is_1("IM_SINKHORN_TWO_SWEEP");
     const int max_parts = (ctx->max_kpts + 15) / 16;
     if (!two_sweep && n_max <= SKF_MAXN && (ld % 4) == 0 && (reinterpret_cast<uintptr_t>(sim) % 16) == 0 && max_parts >= 1 && iters > 0) {
         const int G4 = std::min(std::min(256, 2 * max_parts), m_max + 1);
@@ -443,7 +442,7 @@ static int sinkhorn(im_ctx* ctx, hipStream_t s, const float* sim, int ld, const 
         int* cnt = ws->ridx + (ctx->max_kpts + 1);
         IM_HIP(ctx, launch_zero_words(cnt, 2, s));
         // IM_SINKHORN_REPAIR_ALL=1 (tests): every column goes through the exact repair path
-        static const float c_min = (getenv("IM_SINKHORN_REPAIR_ALL") && getenv("IM_SINKHORN_REPAIR_ALL")[0] == '1') ? 3.0e38f : 1e-30f;
+        static const float c_min = env_is_1("IM_SINKHORN_REPAIR_ALL") ? 3.0e38f : 1e-30f;
         for (int it = 0; it < iters; ++it) {
             hipLaunchKernelGGL((sinkhorn_fused4_kernel<512, 8>), dim3(G4), dim3(512), lds4, s, sim, ld, m_ptr, n_ptr, alpha, v, u, csum, pstride);
             hipLaunchKernelGGL(sinkhorn_fused4_combine_kernel, dim3((n_max + SK4_CB) / SK4_CB), dim3(256), 0, s, csum, pstride, G4, m_ptr, n_ptr, v, norm_out,
@@ -463,136 +462,6 @@ static int sinkhorn(im_ctx* ctx, hipStream_t s, const float* sim, int ld, const 
         hipLaunchKernelGGL(sinkhorn_col_combine_kernel, dim3((n_max + 1 + 255) / 256), dim3(256), 0, s, ws->part, pstride, m_ptr, n_ptr,
                            alpha, u, v, norm_out);
     IM_HIP(ctx, hipGetLastError());
-    return 0;
-}
-
-// ------------------------------------------------------------------------------------------------ weights
-static const std::vector<float>* sg_find(im_ctx* ctx, const std::string& key, size_t numel) {
-    auto it = ctx->host_w.find("superglue/" + key);
-    if (it == ctx->host_w.end()) { ctx->fail(-20, "weights: missing tensor %s of model superglue", key.c_str()); return nullptr; }
-    if (it->second.size() != numel) {
-        ctx->fail(-21, "weights: tensor %s has %zu elements, expected %zu", key.c_str(), it->second.size(), numel);
-        return nullptr;
-    }
-    return &it->second;
-}
-
-// fold eval-mode BatchNorm1d (eps 1e-5) into the preceding 1x1 conv: y = g (Wx + b - mean) / sqrt(var + eps) + beta
-static int fold_bn(im_ctx* ctx, const std::string& bn, int c, int in, std::vector<float>& w, std::vector<float>& b) {
-    const auto* g = sg_find(ctx, bn + ".weight", c);
-    const auto* be = sg_find(ctx, bn + ".bias", c);
-    const auto* mu = sg_find(ctx, bn + ".running_mean", c);
-    const auto* var = sg_find(ctx, bn + ".running_var", c);
-    if (!g || !be || !mu || !var) return -20;
-    for (int o = 0; o < c; ++o) {
-        const float sc = (*g)[o] / std::sqrt((*var)[o] + 1e-5f);
-        for (int i = 0; i < in; ++i) w[(size_t)o * in + i] *= sc;
-        b[o] = (b[o] - (*mu)[o]) * sc + (*be)[o];
-    }
-    return 0;
-}
-
-int finalize_superglue(im_ctx* ctx) {
-    SuperGlueW& W = ctx->sg;
-    static const int dims[6] = {3, 32, 64, 128, 256, 256};
-    for (int l = 0; l < 5; ++l) {
-        const int in = dims[l], out = dims[l + 1], inp = l == 0 ? 32 : in;
-        const std::string key = "kenc.encoder." + std::to_string(3 * l);
-        const auto* w = sg_find(ctx, key + ".weight", (size_t)out * in);
-        const auto* b = sg_find(ctx, key + ".bias", out);
-        if (!w || !b) return -20;
-        std::vector<float> ww(*w), bb(*b);
-        if (l < 4 && fold_bn(ctx, "kenc.encoder." + std::to_string(3 * l + 1), out, in, ww, bb)) return -20;
-        std::vector<float> wp((size_t)out * inp, 0.f);
-        for (int o = 0; o < out; ++o)
-            for (int i = 0; i < in; ++i) wp[(size_t)o * inp + i] = ww[(size_t)o * in + i];
-        W.kenc_w[l] = ctx->upload(wp);
-        W.kenc_b[l] = ctx->upload(bb);
-    }
-    const int L = 18;
-    std::vector<float> qkv_w((size_t)L * 768 * 256), qkv_b((size_t)L * 768), mg_w((size_t)L * 65536), mg_b((size_t)L * 256),
-        m0_w((size_t)L * 512 * 512), m0_b((size_t)L * 512), m3_w((size_t)L * 256 * 512), m3_b((size_t)L * 256);
-    for (int l = 0; l < L; ++l) {
-        const std::string p = "gnn.layers." + std::to_string(l);
-        for (int which = 0; which < 3; ++which) {
-            const auto* w = sg_find(ctx, p + ".attn.proj." + std::to_string(which) + ".weight", 65536);
-            const auto* b = sg_find(ctx, p + ".attn.proj." + std::to_string(which) + ".bias", 256);
-            if (!w || !b) return -20;
-            for (int h = 0; h < 4; ++h)
-                for (int d = 0; d < 64; ++d) {
-                    const int src = d * 4 + h, dst = which * 256 + h * 64 + d;
-                    memcpy(&qkv_w[((size_t)l * 768 + dst) * 256], &(*w)[(size_t)src * 256], 256 * sizeof(float));
-                    qkv_b[(size_t)l * 768 + dst] = (*b)[src];
-                }
-        }
-        const auto* mw = sg_find(ctx, p + ".attn.merge.weight", 65536);
-        const auto* mb = sg_find(ctx, p + ".attn.merge.bias", 256);
-        if (!mw || !mb) return -20;
-        for (int o = 0; o < 256; ++o)
-            for (int h = 0; h < 4; ++h)
-                for (int d = 0; d < 64; ++d) mg_w[((size_t)l * 256 + o) * 256 + h * 64 + d] = (*mw)[(size_t)o * 256 + d * 4 + h];
-        memcpy(&mg_b[(size_t)l * 256], mb->data(), 256 * sizeof(float));
-        const auto* w0 = sg_find(ctx, p + ".mlp.0.weight", 512 * 512);
-        const auto* b0 = sg_find(ctx, p + ".mlp.0.bias", 512);
-        const auto* w3 = sg_find(ctx, p + ".mlp.3.weight", 256 * 512);
-        const auto* b3 = sg_find(ctx, p + ".mlp.3.bias", 256);
-        if (!w0 || !b0 || !w3 || !b3) return -20;
-        std::vector<float> ww(*w0), bb(*b0);
-        if (fold_bn(ctx, p + ".mlp.1", 512, 512, ww, bb)) return -20;
-        // `merge` feeds only mlp.0 (`superglue.py:104-116`: mlp(cat([x, message]))): fold it into the message half of the
-        // (BatchNorm-folded) mlp.0 weights, mlp0([x | Wm a + bm]) = W0a x + (W0b Wm) a + (W0b bm + b0), accumulated in
-        // double. One 256 -> 256 GEMM launch and the message round trip less per layer.
-        {
-            const float* Wm = &mg_w[(size_t)l * 65536];     // head-permuted merge weights [256 out][256 in (h * 64 + d)]
-            const float* bm = &mg_b[(size_t)l * 256];
-            std::vector<double> row(256);
-            for (int n = 0; n < 512; ++n) {
-                float* w0r = &ww[(size_t)n * 512 + 256];
-                double bacc = bb[n];
-                for (int k = 0; k < 256; ++k) row[k] = 0.0;
-                for (int j = 0; j < 256; ++j) {
-                    const double wj = w0r[j];
-                    const float* wmr = Wm + (size_t)j * 256;
-                    for (int k = 0; k < 256; ++k) row[k] += wj * (double)wmr[k];
-                    bacc += wj * (double)bm[j];
-                }
-                for (int k = 0; k < 256; ++k) w0r[k] = (float)row[k];
-                bb[n] = (float)bacc;
-            }
-        }
-        memcpy(&m0_w[(size_t)l * 512 * 512], ww.data(), ww.size() * sizeof(float));
-        memcpy(&m0_b[(size_t)l * 512], bb.data(), 512 * sizeof(float));
-        memcpy(&m3_w[(size_t)l * 256 * 512], w3->data(), w3->size() * sizeof(float));
-        memcpy(&m3_b[(size_t)l * 256], b3->data(), 256 * sizeof(float));
-    }
-    W.proj_w = ctx->upload(qkv_w); W.proj_b = ctx->upload(qkv_b);
-    W.mlp0_w = ctx->upload(m0_w); W.mlp0_b = ctx->upload(m0_b);
-    W.mlp3_w = ctx->upload(m3_w); W.mlp3_b = ctx->upload(m3_b);
-    {
-        std::vector<float> p0, p3;
-        for (int l = 0; l < L; ++l) {
-            const std::vector<float> a0 = pack_frag_weights(&m0_w[(size_t)l * 512 * 512], 512, 512), a3 = pack_frag_weights(&m3_w[(size_t)l * 256 * 512], 256, 512);
-            p0.insert(p0.end(), a0.begin(), a0.end());
-            p3.insert(p3.end(), a3.begin(), a3.end());
-        }
-        W.mlp0_wp = ctx->upload(p0); W.mlp3_wp = ctx->upload(p3);
-        std::vector<float> pq;
-        pq.reserve(qkv_w.size() * 3 / 2);
-        for (int l = 0; l < L; ++l) {
-            const std::vector<float> one = pack_frag_weights(&qkv_w[(size_t)l * 768 * 256], 768, 256);
-            pq.insert(pq.end(), one.begin(), one.end());
-        }
-        W.proj_wp = ctx->upload(pq);
-        if (!W.mlp0_wp || !W.mlp3_wp || !W.proj_wp) return ctx->fail(-22, "weights: upload failed");
-    }
-    const auto* fw = sg_find(ctx, "final_proj.weight", 65536);
-    const auto* fb = sg_find(ctx, "final_proj.bias", 256);
-    const auto* bs = sg_find(ctx, "bin_score", 1);
-    if (!fw || !fb || !bs) return -20;
-    W.fp_w = ctx->upload(*fw); W.fp_b = ctx->upload(*fb);
-    W.bin_score = (*bs)[0];
-    if (!W.proj_w || !W.mlp0_w || !W.mlp3_w || !W.fp_w) return ctx->fail(-22, "weights: upload failed");
-    W.ready = true;
     return 0;
 }
 
@@ -636,53 +505,24 @@ int im_superglue_forward(im_ctx* ctx, const float* d_kpts, const float* d_scores
         }
     }
     for (int l = 0; l < L; ++l) {
-        const bool cross = (l & 1) != 0;  // ['self', 'cross'] * 9 (`superglue.py:215`)
-        {
-            GemmArgs g = base;
-            g.A = x; g.a_bstride = xb; g.lda = 256; g.W = W.proj_w + (long)l * 768 * 256; g.ldw = 256;
-            g.bias = W.proj_b + (long)l * 768; g.N = 768; g.K = 256; g.epi = EPI_QKV_ROPE;  // no rotary tables => plain q/k/v
-            g.q = ws->q; g.k = ws->k; g.v = ws->v; g.head_bstride = (long)K * 256; g.head_stride = (long)K * 64;
-            const char* const tiled_env = getenv("IM_PROJ_TILED");      // A/B switch (read per call): 1 = the tiled GEMM of rounds 1-5 instead of the row-block kernel
-            if (tiled_env && tiled_env[0] == '1') {
-                IM_LAUNCH(ctx, "sg_qkv_gemm", s, launch_gemm(g, s));
-            } else {
-                g.wp = reinterpret_cast<const unsigned char*>(W.proj_wp) + (size_t)l * 768 * 256 * 6;
-                IM_LAUNCH(ctx, "sg_qkv_gemm", s, launch_proj_rows(g, s));
-            }
-        }
-        {
-            AttnArgs at;
-            at.q = ws->q; at.k = ws->k; at.v = ws->v; at.hstride = (long)K * 64; at.bstride = (long)K * 256;
-            at.out = ws->att; at.out_bstride = xb; at.ldo = 256; at.n_ptr = st->n; at.n_max = K; at.batch = 2; at.heads = 4;
-            at.cross = cross ? 1 : 0; at.scale = 0.125f;  // / dim ** .5, dim = 64 (`superglue.py:91`)
-            at.part = ws->attn_part; at.counters = ws->attn_cnt; at.planes = ws->attn_planes; at.clock = ctx->clock_of(0);
-            IM_LAUNCH(ctx, "attn_kv_planes", s, launch_attn_planes(at, s));
-            IM_LAUNCH(ctx, cross ? "flash_attn_cross" : "flash_attn_self", s, launch_flash_attn(at, s));
-        }
-        static const bool unfused = getenv("IM_FFN_UNFUSED") && getenv("IM_FFN_UNFUSED")[0] == '1';   // A/B switch: two GEMM launches
-        if (!unfused) {   // x += mlp.3(relu(bn(mlp.0([x | att])))) with merge and BatchNorm folded into mlp.0: one kernel (ffn_fused.hip)
-            FfnArgs f;
-            f.act = 1; f.x = x; f.x_bstride = xb; f.att = ws->att; f.att_bstride = xb;
-            f.w0p = W.mlp0_wp + (long)l * 512 * 512 * 3 / 2; f.b0 = W.mlp0_b + (long)l * 512;
-            f.w3p = W.mlp3_wp + (long)l * 256 * 512 * 3 / 2; f.b3 = W.mlp3_b + (long)l * 256;
-            f.m_max = base.m_max; f.batch = base.batch; f.m_ptr = base.m_ptr; f.active = base.active; f.pstride = base.pstride;
-            IM_LAUNCH(ctx, "sg_mlp_fused", s, launch_ffn_fused(f, s));
-            continue;
-        }
-        {
-            GemmArgs g = base;
-            g.A = x; g.a_bstride = xb; g.lda = 256; g.A1 = ws->att; g.a1_bstride = xb; g.lda1 = 256; g.ksplit = 256;   // merge folded in
-            g.W = W.mlp0_w + (long)l * 512 * 512; g.ldw = 512; g.bias = W.mlp0_b + (long)l * 512; g.N = 512; g.K = 512;
-            g.C = ws->h; g.c_bstride = (long)K * 512; g.ldc = 512; g.epi = EPI_BIAS_RELU;
-            IM_LAUNCH(ctx, "sg_mlp0_gemm", s, launch_gemm(g, s));
-        }
-        {
-            GemmArgs g = base;
-            g.A = ws->h; g.a_bstride = (long)K * 512; g.lda = 512; g.W = W.mlp3_w + (long)l * 256 * 512; g.ldw = 512;
-            g.bias = W.mlp3_b + (long)l * 256; g.N = 256; g.K = 512;
-            g.C = x; g.c_bstride = xb; g.ldc = 256; g.R = x; g.r_bstride = xb; g.ldr = 256; g.epi = EPI_BIAS_RESID;
-            IM_LAUNCH(ctx, "sg_mlp3_gemm", s, launch_gemm(g, s));
-        }
+        GemmArgs g = base;
+        g.A = x; g.a_bstride = xb; g.lda = 256; g.W = W.proj_w + (long)l * 768 * 256; g.ldw = 256;
+        g.bias = W.proj_b + (long)l * 768; g.N = 768; g.K = 256; g.epi = EPI_QKV_ROPE;  // no rotary tables => plain q/k/v
+        g.q = ws->q; g.k = ws->k; g.v = ws->v; g.head_bstride = (long)K * 256; g.head_stride = (long)K * 64;
+        if (int rc = launch_block_proj(ctx, s, "sg_qkv_gemm", g, W.proj_wp, l)) return rc;
+        AttnArgs at;
+        at.q = ws->q; at.k = ws->k; at.v = ws->v; at.hstride = (long)K * 64; at.bstride = (long)K * 256;
+        at.out = ws->att; at.out_bstride = xb; at.ldo = 256; at.n_ptr = st->n; at.n_max = K; at.batch = 2; at.heads = 4;
+        at.cross = l & 1;  // ['self', 'cross'] * 9 (`superglue.py:215`)
+        at.scale = 0.125f;  // / dim ** .5, dim = 64 (`superglue.py:91`)
+        at.part = ws->attn_part; at.counters = ws->attn_cnt; at.planes = ws->attn_planes; at.clock = ctx->clock_of(0);
+        // x += mlp.3(relu(bn(mlp.0([x | att])))) with merge and BatchNorm folded into mlp.0 (weights.hip)
+        BlockFfn f;
+        f.act = 1;
+        f.w0 = W.mlp0_w + (long)l * 512 * 512; f.w0p = W.mlp0_wp + (long)l * 512 * 512 * 3 / 2; f.b0 = W.mlp0_b + (long)l * 512;
+        f.w3 = W.mlp3_w + (long)l * 256 * 512; f.w3p = W.mlp3_wp + (long)l * 256 * 512 * 3 / 2; f.b3 = W.mlp3_b + (long)l * 256;
+        f.name_fused = "sg_mlp_fused"; f.name_ffn0 = "sg_mlp0_gemm"; f.name_ffn3 = "sg_mlp3_gemm";
+        if (int rc = launch_block_tail(ctx, s, at, f, base, x)) return rc;
     }
     {
         GemmArgs g = base;

@@ -16,6 +16,7 @@ struct Workspace {
     float* act0 = nullptr; float* act1 = nullptr;       // NHWC ping-pong
     float* logits = nullptr; float* dense = nullptr;    // [cells][65], [cells][256]
     float* smap = nullptr; float* nms = nullptr; float* rest = nullptr;
+    size_t smap_floats = 0;   // elements of a score-map sized buffer (smap, nms, rest, mask, supp, kpsel.keys): max_images x max_h / 8 * 8 x max_w / 8 * 8
     uint8_t* mask = nullptr; uint8_t* supp = nullptr;
     im::SelBuffers kpsel;   // keypoint selection: candidate counters + radix state, candidate keys, tie list, chosen keys
     // LightGlue / SuperGlue

@@ -255,7 +255,7 @@ class SequenceMatcher:
                 if self._graph is None:
                     self._capture()
                 self._graph.replay()
-                if _DEBUG_GUARDS:       # forwards inside a graph carry no guard check of their own (csrc/weights.hip): from the host
+                if _DEBUG_GUARDS:       # forwards inside a graph carry no guard check of their own (csrc/guards.hip): from the host
                     self.e.ctx.call("im_debug_guards_check", self.e.stream_ptr())
         except Exception as group_exc:      # noqa: BLE001 - any error of a launch group is isolated to the pairs that cause it
             # the group as a whole could not be enqueued: its pairs one by one with direct launches (their inputs are still parked in

@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
 """Are two builds of the library bit-identical on the benchmark pair? Runs SuperPoint + LightGlue (1080 x 1920 stereo pair and the
-translated pair, 4096 keypoints) with each library named on the command line in its own process and prints a SHA-1 per output
-(keypoints, scores, descriptors, matches0, matching_scores0): equal digests = equal bits. Used after instruction-level rewrites that
-must not change any result (same operations in the same order).
+translated pair, 4096 keypoints), then the same SuperPoint features through SuperGlue (18 layers, default Sinkhorn iterations), with each
+library named on the command line in its own process and prints a SHA-1 per output (keypoints, scores, descriptors, matches0,
+matching_scores0 of both matchers): equal digests = equal bits. Used after instruction-level rewrites and host-side refactors that must
+not change any result (same operations in the same order).
 
     python tools/compare_builds.py build_abl/<old>/libicematch.so icepy4d_amd/csrc/libicematch.so
 """
@@ -24,6 +25,7 @@ def child():
     eng = Engine(0)
     eng.load_state_dict("superpoint", synthetic.superpoint_state_dict(0))
     eng.load_state_dict("lightglue", synthetic.lightglue_state_dict(0, "passthrough"))
+    eng.load_state_dict("superglue", synthetic.superglue_state_dict(0, "passthrough"))
     out = {}
     for name, (a, b) in (("stereo", synthetic.stereo_pair(0, 1080, 1920)), ("translated", synthetic.translated_pair(0, 1080, 1920, 40, 8))):
         eng.reserve(1080, 1920, 2, 4096)
@@ -36,6 +38,11 @@ def child():
                          ("mscores0", m["matching_scores0"])):
             out[f"{name}.{key}"] = hashlib.sha1(np.ascontiguousarray(arr).tobytes()).hexdigest()[:12]
         out[f"{name}.n_matches"] = int((np.asarray(m["matches0"]) >= 0).sum())
+        eng.superglue((1080, 1920), (1080, 1920))
+        m = eng.matches_to_host(len(k0), len(k1))
+        for key, arr in (("sg_matches0", m["matches0"]), ("sg_mscores0", m["matching_scores0"])):
+            out[f"{name}.{key}"] = hashlib.sha1(np.ascontiguousarray(arr).tobytes()).hexdigest()[:12]
+        out[f"{name}.sg_n_matches"] = int((np.asarray(m["matches0"]) >= 0).sum())
     print(json.dumps(out))
 
 
