@@ -23,9 +23,6 @@
 // (tools/mfma_peak.hip), so everything next to the MFMAs is written for instruction count - see softmax_tile.
 #include "common.h"
 #include "kernels.h"
-#include "sp_post.h"
-
-#include <cstdlib>
 
 namespace im {
 
@@ -432,18 +429,18 @@ __global__ __launch_bounds__(256 * G, 2 / G) void flash_attn_f32_kernel(AttnArgs
 template <int G>
 static hipError_t launch_g(const AttnArgs& a, hipStream_t s) {
     const size_t lds = G * ATTN_LDS_FLOATS * sizeof(float);
-    static size_t lds_optin[IM_MAX_DEVICES] = {0};   // per device: a process may hold contexts on several GPUs
-    if (hipError_t e = ensure_dyn_lds(reinterpret_cast<const void*>(&flash_attn_f32_kernel<G>), lds, lds_optin); e != hipSuccess) return e;
-    dim3 grid(((a.n_max + 127) / 128) * a.heads * a.batch * (a.part ? ATTN_MAX_SPLIT : 1)), block(256 * G);
-    hipLaunchKernelGGL(flash_attn_f32_kernel<G>, grid, block, lds, s, a);
-    return hipGetLastError();
+    return launch_dyn_lds<flash_attn_f32_kernel<G>>(dim3(((a.n_max + 127) / 128) * a.heads * a.batch * (a.part ? ATTN_MAX_SPLIT : 1)), dim3(256 * G), lds, s, a);
+}
+
+bool attn_f32_form(const AttnArgs& a) {
+    static const bool env = env_int("IM_ATTN_F32") != 0;
+    return env || a.f32_form;
 }
 
 hipError_t launch_flash_attn(const AttnArgs& a, hipStream_t s) {
     if (a.n_max <= 0) return hipSuccess;
-    static const bool f32_form = [] { const char* e = getenv("IM_ATTN_F32"); return e && atoi(e) != 0; }();
-    if (!f32_form && !a.f32_form) return launch_flash_attn_bx(a, s);
-    static const int force = [] { const char* e = getenv("IM_ATTN_GROUPS"); return e ? atoi(e) : 0; }();
+    if (!attn_f32_form(a)) return launch_flash_attn_bx(a, s);
+    static const int force = env_int("IM_ATTN_GROUPS");
     const int g = force ? force : 2;
     return g == 2 ? launch_g<2>(a, s) : launch_g<1>(a, s);
 }

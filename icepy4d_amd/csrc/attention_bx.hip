@@ -19,9 +19,6 @@
 #include "bf16x3.h"
 #include "common.h"
 #include "kernels.h"
-#include "sp_post.h"
-
-#include <cstdlib>
 
 namespace im {
 
@@ -45,16 +42,6 @@ __device__ __forceinline__ f32x16 mfma_attn(u32x4 a, u32x4 b, f32x16 c) {
 #else
     return mfma_bf(a, b, c);
 #endif
-}
-
-// one float4 of a tile row -> 8 bytes in each of the three planes
-__device__ __forceinline__ void stage4(unsigned char* plane0, int plane_bytes, int off, float4 x) {
-    unsigned h0, m0, l0, h1, m1, l1;
-    split2(x.x, x.y, h0, m0, l0);
-    split2(x.z, x.w, h1, m1, l1);
-    *reinterpret_cast<u32x2*>(plane0 + off) = u32x2{h0, h1};
-    *reinterpret_cast<u32x2*>(plane0 + plane_bytes + off) = u32x2{m0, m1};
-    *reinterpret_cast<u32x2*>(plane0 + 2 * plane_bytes + off) = u32x2{l0, l1};
 }
 
 typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4;
@@ -268,7 +255,7 @@ __global__ __launch_bounds__(256, 2) void flash_attn_bx_kernel(AttnArgs a) {
 #pragma unroll
             for (int i = 0; i < 3; ++i) *reinterpret_cast<u32x4*>(kp + lk[i]) = pk[i];
         } else {
-            stage4(kp, BK_PLANE, st_k, fk[0]); stage4(kp, BK_PLANE, st_k + 16 * BKS, fk[1]);
+            put4<BK_PLANE>(kp, st_k, fk[0]); put4<BK_PLANE>(kp, st_k + 16 * BKS, fk[1]);
         }
     };
     auto store_v = [&](int stage) {
@@ -277,7 +264,7 @@ __global__ __launch_bounds__(256, 2) void flash_attn_bx_kernel(AttnArgs a) {
 #pragma unroll
             for (int i = 0; i < 3; ++i) *reinterpret_cast<u32x4*>(vp + lv[i]) = pv[i];
         } else {
-            stage4(vp, BV_PLANE, st_v, fv[0]); stage4(vp, BV_PLANE, st_v + 16 * BVS, fv[1]);
+            put4<BV_PLANE>(vp, st_v, fv[0]); put4<BV_PLANE>(vp, st_v + 16 * BVS, fv[1]);
         }
     };
     // DMA form: wave w transfers rows 8 w .. 8 w + 7 of the three planes of a tile (three 1 KB pieces per tensor), lane (row, place pc) fetching piece
@@ -619,29 +606,19 @@ __global__ __launch_bounds__(256, 2) void flash_attn_bx_kernel(AttnArgs a) {
 
 // K / V of the launch as bf16 triples (a.planes); a launch of its own so that event profiles and rocprofv3 name the two kernels apart
 hipError_t launch_attn_planes(const AttnArgs& a, hipStream_t s) {
-    static const bool f32_form = [] { const char* e = getenv("IM_ATTN_F32"); return e && atoi(e) != 0; }();
-    if (!a.planes || a.n_max <= 0 || f32_form || a.f32_form) return hipSuccess;
+    if (!a.planes || a.n_max <= 0 || attn_f32_form(a)) return hipSuccess;
     const long rows = (long)a.batch * a.heads * a.n_max;
     hipLaunchKernelGGL(kv_planes_kernel, dim3((unsigned)((rows + 31) / 32), 2), dim3(256), 0, s, a);
     return hipGetLastError();
 }
 
 hipError_t launch_flash_attn_bx(const AttnArgs& a, hipStream_t s) {
-    static size_t lds_pre[IM_MAX_DEVICES] = {0}, lds_cut[IM_MAX_DEVICES] = {0};
-    dim3 grid(((a.n_max + 127) / 128) * a.heads * a.batch * (a.part ? ATTN_MAX_SPLIT : 1)), block(256);
-    static size_t lds_dma[IM_MAX_DEVICES] = {0};
-    static const bool reg_staging = [] { const char* e = getenv("IM_ATTN_REG_STAGING"); return e && atoi(e) != 0; }();
-    if (a.planes && !reg_staging) {     // planes filled by launch_attn_planes on the same stream; tiles into LDS by LDS-DMA
-        if (hipError_t e = ensure_dyn_lds(reinterpret_cast<const void*>(&flash_attn_bx_kernel<true, true>), D_LDS, lds_dma); e != hipSuccess) return e;
-        hipLaunchKernelGGL((flash_attn_bx_kernel<true, true>), grid, block, D_LDS, s, a);
-    } else if (a.planes) {              // tiles through registers (A/B)
-        if (hipError_t e = ensure_dyn_lds(reinterpret_cast<const void*>(&flash_attn_bx_kernel<true, false>), B_LDS, lds_pre); e != hipSuccess) return e;
-        hipLaunchKernelGGL((flash_attn_bx_kernel<true, false>), grid, block, B_LDS, s, a);
-    } else {
-        if (hipError_t e = ensure_dyn_lds(reinterpret_cast<const void*>(&flash_attn_bx_kernel<false, false>), B_LDS, lds_cut); e != hipSuccess) return e;
-        hipLaunchKernelGGL((flash_attn_bx_kernel<false, false>), grid, block, B_LDS, s, a);
-    }
-    return hipGetLastError();
+    const dim3 grid(((a.n_max + 127) / 128) * a.heads * a.batch * (a.part ? ATTN_MAX_SPLIT : 1)), block(256);
+    static const bool reg_staging = env_int("IM_ATTN_REG_STAGING") != 0;
+    // planes filled by launch_attn_planes on the same stream: tiles into LDS by LDS-DMA, or through registers (A/B); no planes: cut in the kernel
+    if (a.planes && !reg_staging) return launch_dyn_lds<flash_attn_bx_kernel<true, true>>(grid, block, D_LDS, s, a);
+    if (a.planes) return launch_dyn_lds<flash_attn_bx_kernel<true, false>>(grid, block, B_LDS, s, a);
+    return launch_dyn_lds<flash_attn_bx_kernel<false, false>>(grid, block, B_LDS, s, a);
 }
 
 }  // namespace im

@@ -55,6 +55,26 @@ __device__ __forceinline__ Planes split8(float x0, float x1, float x2, float x3,
     split2(x6, x7, h[3], m[3], l[3]);
     return Planes{u32x4{h[0], h[1], h[2], h[3]}, u32x4{m[0], m[1], m[2], m[3]}, u32x4{l[0], l[1], l[2], l[3]}};
 }
+// four consecutive values of a row -> their 8 bytes in each of the three planes (plane p of the image starts at plane0 + p * PLANE_BYTES)
+template <int PLANE_BYTES>
+__device__ __forceinline__ void put4(unsigned char* plane0, int off, float4 x) {
+    unsigned h0, m0, l0, h1, m1, l1;
+    split2(x.x, x.y, h0, m0, l0);
+    split2(x.z, x.w, h1, m1, l1);
+    *reinterpret_cast<u32x2*>(plane0 + off) = u32x2{h0, h1};
+    *reinterpret_cast<u32x2*>(plane0 + PLANE_BYTES + off) = u32x2{m0, m1};
+    *reinterpret_cast<u32x2*>(plane0 + 2 * PLANE_BYTES + off) = u32x2{l0, l1};
+}
+// the six products of one 16-deep k chunk, small ones first: h l, l h, m m, h m, m h, h h
+__device__ __forceinline__ f32x16 six(u32x4 ah, u32x4 am, u32x4 al, u32x4 bh, u32x4 bm, u32x4 bl, f32x16 acc) {
+    acc = mfma_bf(ah, bl, acc);
+    acc = mfma_bf(al, bh, acc);
+    acc = mfma_bf(am, bm, acc);
+    acc = mfma_bf(ah, bm, acc);
+    acc = mfma_bf(am, bh, acc);
+    acc = mfma_bf(ah, bh, acc);
+    return acc;
+}
 
 // host: fp32 -> bf16, round to nearest even (what v_cvt_pk_bf16_f32 does; the weights are finite), and back
 inline uint16_t bf16_rne(float x) {

@@ -7,7 +7,6 @@
 #include "bf16x3.h"
 #include "common.h"
 #include "kernels.h"
-#include "sp_post.h"
 
 namespace im {
 

@@ -346,22 +346,14 @@ static hipError_t launch_bx2(const ConvArgs& a, hipStream_t s) {
     const int ntile = ((a.W + Y_TW - 1) / Y_TW) * ((a.H + Y_TH - 1) / Y_TH) * a.B;
     const int nslices = a.Cout / 64;
     const int nitems = ((ntile + 7) / 8) * 8 * nslices;
-    static int n_cu[IM_MAX_DEVICES] = {0};
-    int dev = 0;
-    if (hipError_t e = hipGetDevice(&dev); e != hipSuccess) return e;
-    if (dev < 0 || dev >= IM_MAX_DEVICES) return hipErrorInvalidDevice;
-    if (!n_cu[dev]) {
-        if (hipError_t e = hipDeviceGetAttribute(&n_cu[dev], hipDeviceAttributeMultiprocessorCount, dev); e != hipSuccess) return e;
-    }
+    int n_cu = 0;
+    if (hipError_t e = device_cu_count(&n_cu); e != hipSuccess) return e;
     // one block per CU; a multiple of 8 nslices so that a block keeps its output-channel slice and its residue mod 8 over all its items
     const int unit = 8 * nslices;
-    int grid = (n_cu[dev] / unit) * unit;
+    int grid = (n_cu / unit) * unit;
     if (grid < unit) grid = unit;
     if (grid > nitems) grid = nitems;
-    static size_t lds_optin[IM_MAX_DEVICES] = {0};
-    if (hipError_t e = ensure_dyn_lds(reinterpret_cast<const void*>(&conv3x3_wino_bx2_kernel<POOL>), Y_LDS_BYTES + 256, lds_optin); e != hipSuccess) return e;
-    hipLaunchKernelGGL((conv3x3_wino_bx2_kernel<POOL>), dim3(grid), dim3(512), Y_LDS_BYTES + 256, s, a, nitems);
-    return hipGetLastError();
+    return launch_dyn_lds<conv3x3_wino_bx2_kernel<POOL>>(dim3(grid), dim3(512), Y_LDS_BYTES + 256, s, a, nitems);
 }
 
 // plain layers (no fused first layer) with the bf16 planes of U

@@ -19,7 +19,6 @@
 #include "bf16x3.h"
 #include "common.h"
 #include "kernels.h"
-#include "sp_post.h"
 
 #include <cstdint>
 #include <cstdlib>
@@ -60,16 +59,6 @@ std::vector<float> pack_frag_weights(const float* w, int n, int k) {
 }
 
 namespace ff {
-// four consecutive row values -> 8 bytes in each plane
-template <int PLANE_BYTES = PLANE>
-__device__ __forceinline__ void put4(unsigned char* plane0, int off, float4 x) {
-    unsigned h0, m0, l0, h1, m1, l1;
-    split2(x.x, x.y, h0, m0, l0);
-    split2(x.z, x.w, h1, m1, l1);
-    *reinterpret_cast<u32x2*>(plane0 + off) = u32x2{h0, h1};
-    *reinterpret_cast<u32x2*>(plane0 + PLANE_BYTES + off) = u32x2{m0, m1};
-    *reinterpret_cast<u32x2*>(plane0 + 2 * PLANE_BYTES + off) = u32x2{l0, l1};
-}
 // the two-blocks-per-CU form (ffn_fused_split_kernel): planes of HALF the contraction (256 of 512) at a time
 constexpr int PS2 = 528;             // bytes per row of a half-K plane: 256 x 2 + 16 (132 dwords = 4 mod 64, as PS: conflict-free 16-byte row reads)
 constexpr int PLANE2 = BM * PS2;     // 16,896 bytes; three of them (50,688) lie over the fp32 hidden rows
@@ -115,21 +104,14 @@ __global__ __launch_bounds__(ff::NT, 2) void ffn_fused_kernel(FfnArgs a) {
         b0_[g] = __builtin_amdgcn_raw_buffer_load_b128(rW0, vb0, (unsigned)((ch_) * 6 + g) * 1024u, 0);              \
         b1_[g] = __builtin_amdgcn_raw_buffer_load_b128(rW0, vb0 + TILE_BYTES, (unsigned)((ch_) * 6 + g) * 1024u, 0); \
     }
-    // the six products of one 16-deep k chunk, small ones first: A planes (h, m, l) from LDS, B planes b[3 kc + (0, 1, 2)]
-#define FF_SIX(acc_, ah_, am_, al_, b_, kc_)              \
-    acc_ = mfma_bf(ah_, b_[3 * (kc_) + 2], acc_);         \
-    acc_ = mfma_bf(al_, b_[3 * (kc_) + 0], acc_);         \
-    acc_ = mfma_bf(am_, b_[3 * (kc_) + 1], acc_);         \
-    acc_ = mfma_bf(ah_, b_[3 * (kc_) + 1], acc_);         \
-    acc_ = mfma_bf(am_, b_[3 * (kc_) + 0], acc_);         \
-    acc_ = mfma_bf(ah_, b_[3 * (kc_) + 0], acc_);
+    // a 16-deep k chunk: A planes (h, m, l) from LDS, B planes b[3 kc + (0, 1, 2)]
 #define FF_MMA2(b0_, b1_, ch_)                                                                                   \
     _Pragma("unroll") for (int kc = 0; kc < 2; ++kc) {                                                           \
         const unsigned char* ap = sB + c * PS + ((ch_) * 32 + kc * 16 + hh * 8) * 2;                             \
         const u32x4 ah = *reinterpret_cast<const u32x4*>(ap), am = *reinterpret_cast<const u32x4*>(ap + PLANE),  \
                     al = *reinterpret_cast<const u32x4*>(ap + 2 * PLANE);                                        \
-        FF_SIX(acc0, ah, am, al, b0_, kc)                                                                        \
-        FF_SIX(acc1, ah, am, al, b1_, kc)                                                                        \
+        acc0 = six(ah, am, al, b0_[3 * kc], b0_[3 * kc + 1], b0_[3 * kc + 2], acc0);                                    \
+        acc1 = six(ah, am, al, b1_[3 * kc], b1_[3 * kc + 1], b1_[3 * kc + 2], acc1);                                    \
     }
     F_STAMP(0)
     FF_LOAD2(p0, p1, 0)
@@ -145,7 +127,7 @@ __global__ __launch_bounds__(ff::NT, 2) void ffn_fused_kernel(FfnArgs a) {
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
             const int idx = tid + i * NT, row = idx >> 7, c4 = idx & 127;
-            put4(sB, row * PS + c4 * 8, v[i]);
+            put4<PLANE>(sB, row * PS + c4 * 8, v[i]);
         }
     }
     __syncthreads();
@@ -234,7 +216,7 @@ __global__ __launch_bounds__(ff::NT, 2) void ffn_fused_kernel(FfnArgs a) {
         F_STAMP(4)
         __syncthreads();   // every fp32 row is in registers: the planes go over them
 #pragma unroll
-        for (int i = 0; i < 8; ++i) put4(sB, row * PS + (part * 4 + 64 * i) * 2, v[i]);
+        for (int i = 0; i < 8; ++i) put4<PLANE>(sB, row * PS + (part * 4 + 64 * i) * 2, v[i]);
     }
     __syncthreads();
     F_STAMP(5)
@@ -247,7 +229,7 @@ __global__ __launch_bounds__(ff::NT, 2) void ffn_fused_kernel(FfnArgs a) {
         const unsigned char* ap = sB + c * PS + ((ch_) * 32 + kc * 16 + hh * 8) * 2;                             \
         const u32x4 ah = *reinterpret_cast<const u32x4*>(ap), am = *reinterpret_cast<const u32x4*>(ap + PLANE),  \
                     al = *reinterpret_cast<const u32x4*>(ap + 2 * PLANE);                                        \
-        FF_SIX(acc0, ah, am, al, b_, kc)                                                                         \
+        acc0 = six(ah, am, al, b_[3 * kc], b_[3 * kc + 1], b_[3 * kc + 2], acc0);                                       \
     }
 #pragma unroll 1
     for (int ch = 0; ch < 16; ch += 2) {
@@ -258,7 +240,6 @@ __global__ __launch_bounds__(ff::NT, 2) void ffn_fused_kernel(FfnArgs a) {
     }
 #undef FF_LOAD1
 #undef FF_MMA1
-#undef FF_SIX
     F_STAMP(6)
     const float bv = a.b3[ocol];
 #pragma unroll
@@ -303,22 +284,14 @@ __global__ __launch_bounds__(ff::NT, 4) void ffn_fused_split_kernel(FfnArgs a) {
         b0_[g] = __builtin_amdgcn_raw_buffer_load_b128(rW0, vb0, (unsigned)((kc_) * 3 + g) * 1024u, 0);              \
         b1_[g] = __builtin_amdgcn_raw_buffer_load_b128(rW0, vb0 + TILE_BYTES, (unsigned)((kc_) * 3 + g) * 1024u, 0); \
     }
-    // the six products of one 16-deep k chunk, small ones first: A planes (h, m, l) from LDS, B planes b[0, 1, 2]
-#define FF_SIX(acc_, ah_, am_, al_, b_)         \
-    acc_ = mfma_bf(ah_, b_[2], acc_);           \
-    acc_ = mfma_bf(al_, b_[0], acc_);           \
-    acc_ = mfma_bf(am_, b_[1], acc_);           \
-    acc_ = mfma_bf(ah_, b_[1], acc_);           \
-    acc_ = mfma_bf(am_, b_[0], acc_);           \
-    acc_ = mfma_bf(ah_, b_[0], acc_);
-    // k chunk `kc_` of 32 lies in the half-K planes at k = 16 (kc_ & 15)
+    // A planes (h, m, l) from LDS, B planes b[0, 1, 2]; k chunk `kc_` of 32 lies in the half-K planes at k = 16 (kc_ & 15)
 #define FF_MMA2(b0_, b1_, kc_)                                                                                   \
     {                                                                                                            \
         const unsigned char* ap = sB + c * PS2 + (((kc_) & 15) * 16 + hh * 8) * 2;                                \
         const u32x4 ah = *reinterpret_cast<const u32x4*>(ap), am = *reinterpret_cast<const u32x4*>(ap + PLANE2),  \
                     al = *reinterpret_cast<const u32x4*>(ap + 2 * PLANE2);                                        \
-        FF_SIX(acc0, ah, am, al, b0_)                                                                            \
-        FF_SIX(acc1, ah, am, al, b1_)                                                                            \
+        acc0 = six(ah, am, al, b0_[0], b0_[1], b0_[2], acc0);                                                           \
+        acc1 = six(ah, am, al, b1_[0], b1_[1], b1_[2], acc1);                                                           \
     }
     F_STAMP(0)
     FF_LOAD2(p0, p1, 0)
@@ -445,7 +418,7 @@ __global__ __launch_bounds__(ff::NT, 4) void ffn_fused_split_kernel(FfnArgs a) {
         const unsigned char* ap = sB + c * PS2 + (((kc_) & 15) * 16 + hh * 8) * 2;                                \
         const u32x4 ah = *reinterpret_cast<const u32x4*>(ap), am = *reinterpret_cast<const u32x4*>(ap + PLANE2),  \
                     al = *reinterpret_cast<const u32x4*>(ap + 2 * PLANE2);                                        \
-        FF_SIX(acc0, ah, am, al, b_)                                                                             \
+        acc0 = six(ah, am, al, b_[0], b_[1], b_[2], acc0);                                                              \
     }
 #pragma unroll 1
     for (int kc = 0; kc < 16; kc += 2) {
@@ -476,7 +449,6 @@ __global__ __launch_bounds__(ff::NT, 4) void ffn_fused_split_kernel(FfnArgs a) {
     }
 #undef FF_LOAD1
 #undef FF_MMA1
-#undef FF_SIX
     F_STAMP(10)
     const float bv = a.b3[ocol];
 #pragma unroll
@@ -489,39 +461,18 @@ __global__ __launch_bounds__(ff::NT, 4) void ffn_fused_split_kernel(FfnArgs a) {
 // 24 MFMAs) otherwise - one pair of 4096 keypoints is 256 blocks. IM_FFN_SPLIT=0 | 1 forces one (read per call: the tests run both forms in one process
 // and compare them bit for bit).
 hipError_t launch_ffn_fused(const FfnArgs& a, hipStream_t s) {
-    static size_t lds_optin[IM_MAX_DEVICES] = {0};   // per device: a process may hold contexts on several GPUs
-    static size_t lds_optin_relu[IM_MAX_DEVICES] = {0};
-    static size_t lds_optin2[IM_MAX_DEVICES] = {0};
-    static size_t lds_optin2_relu[IM_MAX_DEVICES] = {0};
-    static int n_cu[IM_MAX_DEVICES] = {0};
     if (a.m_max <= 0 || a.batch <= 0) return hipSuccess;
-    int dev = 0;
-    if (hipError_t e = hipGetDevice(&dev); e != hipSuccess) return e;
-    if (dev < 0 || dev >= IM_MAX_DEVICES) return hipErrorInvalidDevice;
-    if (!n_cu[dev]) {
-        if (hipError_t e = hipDeviceGetAttribute(&n_cu[dev], hipDeviceAttributeMultiprocessorCount, dev); e != hipSuccess) return e;
-    }
+    int n_cu = 0;
+    if (hipError_t e = device_cu_count(&n_cu); e != hipSuccess) return e;
     const dim3 grid((a.m_max + ff::BM - 1) / ff::BM, a.batch), block(ff::NT);
     const char* const split_env = getenv("IM_FFN_SPLIT");
-    const bool split = split_env ? split_env[0] == '1' : (long)grid.x * grid.y > n_cu[dev];
+    const bool split = split_env ? split_env[0] == '1' : (long)grid.x * grid.y > n_cu;
     if (split) {
-        if (a.act == 1) {
-            if (hipError_t e = ensure_dyn_lds(reinterpret_cast<const void*>(&ffn_fused_split_kernel<1>), ff::LDS_BYTES2, lds_optin2_relu); e != hipSuccess) return e;
-            hipLaunchKernelGGL(ffn_fused_split_kernel<1>, grid, block, ff::LDS_BYTES2, s, a);
-        } else {
-            if (hipError_t e = ensure_dyn_lds(reinterpret_cast<const void*>(&ffn_fused_split_kernel<0>), ff::LDS_BYTES2, lds_optin2); e != hipSuccess) return e;
-            hipLaunchKernelGGL(ffn_fused_split_kernel<0>, grid, block, ff::LDS_BYTES2, s, a);
-        }
-        return hipGetLastError();
+        if (a.act == 1) return launch_dyn_lds<ffn_fused_split_kernel<1>>(grid, block, ff::LDS_BYTES2, s, a);
+        return launch_dyn_lds<ffn_fused_split_kernel<0>>(grid, block, ff::LDS_BYTES2, s, a);
     }
-    if (a.act == 1) {
-        if (hipError_t e = ensure_dyn_lds(reinterpret_cast<const void*>(&ffn_fused_kernel<1>), ff::LDS_BYTES, lds_optin_relu); e != hipSuccess) return e;
-        hipLaunchKernelGGL(ffn_fused_kernel<1>, grid, block, ff::LDS_BYTES, s, a);
-    } else {
-        if (hipError_t e = ensure_dyn_lds(reinterpret_cast<const void*>(&ffn_fused_kernel<0>), ff::LDS_BYTES, lds_optin); e != hipSuccess) return e;
-        hipLaunchKernelGGL(ffn_fused_kernel<0>, grid, block, ff::LDS_BYTES, s, a);
-    }
-    return hipGetLastError();
+    if (a.act == 1) return launch_dyn_lds<ffn_fused_kernel<1>>(grid, block, ff::LDS_BYTES, s, a);
+    return launch_dyn_lds<ffn_fused_kernel<0>>(grid, block, ff::LDS_BYTES, s, a);
 }
 
 }  // namespace im

@@ -16,7 +16,6 @@
 #include "bf16x3.h"
 #include "common.h"
 #include "kernels.h"
-#include "sp_post.h"
 
 namespace im {
 
@@ -154,7 +153,7 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel(GemmArgs a) {
 #pragma unroll
                 for (int i = 0; i < MB; ++i)
 #pragma unroll
-                    for (int j = 0; j < NB; ++j) {
+                    for (int j = 0; j < NB; ++j) {      // bf16x3.h's six(), spelled out: as a call the register names of this kernel move (not yet A/B-timed)
                         acc[i][j] = mfma_bf(fa[i][0], fb[j][2], acc[i][j]);
                         acc[i][j] = mfma_bf(fa[i][2], fb[j][0], acc[i][j]);
                         acc[i][j] = mfma_bf(fa[i][1], fb[j][1], acc[i][j]);
@@ -331,7 +330,7 @@ __global__ __launch_bounds__(pr::NT, 4) void proj_rows_kernel(GemmArgs a) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int idx = tid + i * NT;
-            unsigned h0, m0_, l0, h1, m1, l1;
+            unsigned h0, m0_, l0, h1, m1, l1;      // bf16x3.h's put4(), spelled out: as a call the register numbering of this kernel moves (not yet A/B-timed)
             split2(v[i].x, v[i].y, h0, m0_, l0);
             split2(v[i].z, v[i].w, h1, m1, l1);
             unsigned char* d = psm + (idx >> 6) * PS + (idx & 63) * 8;
@@ -343,6 +342,7 @@ __global__ __launch_bounds__(pr::NT, 4) void proj_rows_kernel(GemmArgs a) {
     __syncthreads();
     P_STAMP(1)
 
+    // the products are bf16x3.h's six(), spelled out: as a call two register quads of this kernel swap names (not yet A/B-timed)
 #define PR_SIX(b_, kc_)                                                                                              \
     {                                                                                                                \
         const unsigned char* ap = psm + c * PS + ((kc_) * 16 + hh * 8) * 2;                                          \
@@ -426,11 +426,8 @@ __global__ __launch_bounds__(pr::NT, 4) void proj_rows_kernel(GemmArgs a) {
 
 template <int EPI, int TILES>
 static hipError_t launch_proj_rows_t(const GemmArgs& a, hipStream_t s) {
-    static size_t lds_optin[IM_MAX_DEVICES] = {0};
-    if (hipError_t e = ensure_dyn_lds(reinterpret_cast<const void*>(&proj_rows_kernel<EPI, TILES>), pr::LDS_BYTES, lds_optin); e != hipSuccess) return e;
     const dim3 grid((a.m_max + pr::BM - 1) / pr::BM, a.batch), block(pr::NT);
-    hipLaunchKernelGGL((proj_rows_kernel<EPI, TILES>), grid, block, pr::LDS_BYTES, s, a);
-    return hipGetLastError();
+    return launch_dyn_lds<proj_rows_kernel<EPI, TILES>>(grid, block, pr::LDS_BYTES, s, a);
 }
 
 // GemmArgs::wp set (W's planes in fragment order, pack_frag_weights(W, N, 256)): K = 256, lda = 256, N = 768 with EPI_QKV_ROPE or N = 512 with EPI_HEADS_QV,

@@ -8,13 +8,59 @@
 #include <cstdlib>
 #include <vector>
 
+#include "common.h"
+
 namespace im {
 
-// an A/B or debugging switch of the environment is on: NAME=1 (the IM_ATTN_* switches parse a number themselves). Reads the environment on every
+// an A/B or debugging switch of the environment is on: NAME=1. Reads the environment on every
 // call; a site that decides once per process keeps the answer in a function-local static (DESIGN.md section 4 lists which)
 inline bool env_is_1(const char* name) {
     const char* e = getenv(name);
     return e && e[0] == '1';
+}
+// a switch that carries a number (the IM_ATTN_* ones): atoi of NAME, 0 when unset
+inline int env_int(const char* name) {
+    const char* e = getenv(name);
+    return e ? atoi(e) : 0;
+}
+
+// ------------------------------------------------------------------ launching (host)
+// the current device as an index into a per-device cache: a process may hold contexts on several GPUs
+inline hipError_t current_device(int* dev) {
+    if (hipError_t e = hipGetDevice(dev); e != hipSuccess) return e;
+    return (*dev < 0 || *dev >= IM_MAX_DEVICES) ? hipErrorInvalidDevice : hipSuccess;
+}
+// compute units of the current device
+inline hipError_t device_cu_count(int* n) {
+    static int n_cu[IM_MAX_DEVICES] = {0};
+    int dev = 0;
+    if (hipError_t e = current_device(&dev); e != hipSuccess) return e;
+    if (!n_cu[dev]) {
+        if (hipError_t e = hipDeviceGetAttribute(&n_cu[dev], hipDeviceAttributeMultiprocessorCount, dev); e != hipSuccess) return e;
+    }
+    *n = n_cu[dev];
+    return hipSuccess;
+}
+// Per-device opt-in of `Kernel` for `bytes` of dynamic LDS (needed above 64 KB). The cache of what was asked for is per KERNEL, not per
+// signature: two kernels with one signature and different sizes (flash_attn_bx_kernel<true, true> / <true, false>) must not share it, or
+// the opt-in of the second would be skipped.
+template <auto Kernel>
+hipError_t optin_dyn_lds(size_t bytes) {
+    static size_t have[IM_MAX_DEVICES] = {0};
+    int dev = 0;
+    if (hipError_t e = current_device(&dev); e != hipSuccess) return e;
+    if (bytes > have[dev]) {
+        if (hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes); e != hipSuccess) return e;
+        have[dev] = bytes;
+    }
+    return hipSuccess;
+}
+// opt-in, launch, launch error: launch_dyn_lds<kernel<...>>(grid, block, lds_bytes, stream, kernel arguments...)
+template <auto Kernel, typename... Args>
+hipError_t launch_dyn_lds(dim3 grid, dim3 block, size_t lds_bytes, hipStream_t s, const Args&... args) {
+    if (hipError_t e = optin_dyn_lds<Kernel>(lds_bytes); e != hipSuccess) return e;
+    hipLaunchKernelGGL(Kernel, grid, block, lds_bytes, s, args...);
+    return hipGetLastError();
 }
 
 // ------------------------------------------------------------------ gemm.hip
@@ -103,7 +149,8 @@ static constexpr int ATTN_MAX_SPLIT = 4;
 inline size_t attn_part_floats(int n_max, int batch, int heads) { return (size_t)ATTN_MAX_SPLIT * batch * heads * n_max * 66; }
 inline size_t attn_planes_bytes(int n_max, int batch, int heads) { return (size_t)2 * batch * heads * n_max * 384; }
 inline size_t attn_counter_ints(int n_max, int batch, int heads) { return (size_t)batch * heads * ((n_max + 127) / 128); }
-hipError_t launch_flash_attn(const AttnArgs& a, hipStream_t s);      // attention_bx.hip unless IM_ATTN_F32=1 (attention.hip: the f32-input MFMA form)
+bool attn_f32_form(const AttnArgs& a);                               // this launch runs attention.hip's kernel: a.f32_form, or IM_ATTN_F32 != 0 (read once per process)
+hipError_t launch_flash_attn(const AttnArgs& a, hipStream_t s);      // attention_bx.hip unless attn_f32_form (attention.hip: the f32-input MFMA form)
 hipError_t launch_attn_planes(const AttnArgs& a, hipStream_t s);     // a.planes <- K / V as bf16 triples; call before launch_flash_attn when a.planes is set
 hipError_t launch_flash_attn_bx(const AttnArgs& a, hipStream_t s);   // fp32 accuracy from six bf16 products per fp32 product on the bf16 matrix cores
 

@@ -12,7 +12,6 @@ struct SelBuffers {
     size_t ties_cap = 0;   // entries of `ties`: also the per-tile staging of the candidate keys (32 x 64 entries per NMS tile), while it is free
 };
 size_t sel_state_bytes(int B);
-hipError_t ensure_dyn_lds(const void* fn, size_t bytes, size_t* cache);   // cache: static size_t [IM_MAX_DEVICES] of the call site
 hipError_t launch_det_softmax(const float* logits, int ld, float* smap, int B, int hc, int wc, hipStream_t s);
 hipError_t launch_nms(const float* s, float* out, uint8_t* mask, uint8_t* supp, float* rest, int B, int H, int W, int r, hipStream_t st);
 hipError_t launch_nms_select(const float* s, float* nms_out, uint8_t* mask, uint8_t* supp, float* rest, int B, int H, int W, int r,

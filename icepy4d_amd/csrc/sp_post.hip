@@ -626,20 +626,6 @@ __global__ __launch_bounds__(RK_N) void sel_rank_kernel(const unsigned long long
     if (tid < RK_T && i < m) emit_kp(mine, W, kpts + ((long)b * kmax + rank) * 2, scores + (long)b * kmax + rank);
 }
 
-// per-device opt-in for more than 64 KB of dynamic LDS (a process may hold contexts on several GPUs)
-hipError_t ensure_dyn_lds(const void* fn, size_t bytes, size_t* cache) {
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    if (dev < 0 || dev >= IM_MAX_DEVICES) return hipErrorInvalidDevice;
-    if (bytes > cache[dev]) {
-        e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-        if (e != hipSuccess) return e;
-        cache[dev] = bytes;
-    }
-    return hipSuccess;
-}
-
 size_t sel_state_bytes(int B) { return (size_t)B * sizeof(int) + 16 + (size_t)B * sizeof(SelState); }
 
 static hipError_t sel_reset(const SelBuffers& sb, int B, hipStream_t st) {   // a kernel, not a memset node (see lg_misc.hip)

@@ -435,8 +435,7 @@ static int sinkhorn(im_ctx* ctx, hipStream_t s, const float* sim, int ld, const 
     if (!two_sweep && n_max <= SKF_MAXN && (ld % 4) == 0 && (reinterpret_cast<uintptr_t>(sim) % 16) == 0 && max_parts >= 1 && iters > 0) {
         const int G4 = std::min(std::min(256, 2 * max_parts), m_max + 1);
         const size_t lds4 = (SKF_MAXN + 2 * 16 * 4) * sizeof(float);
-        static size_t lo4[IM_MAX_DEVICES] = {0};
-        IM_HIP(ctx, ensure_dyn_lds(reinterpret_cast<const void*>(&sinkhorn_fused4_kernel<512, 8>), lds4, lo4));
+        IM_HIP(ctx, (optin_dyn_lds<sinkhorn_fused4_kernel<512, 8>>(lds4)));     // once for the loop's launches below
         float* csum = reinterpret_cast<float*>(ws->part);       // [G4][pstride] floats in the partials buffer (room for 2 x max_parts rows)
         int* list = ws->ridx;                                   // free until the assignment stage: [0 .. n] column list, then counter and ticket
         int* cnt = ws->ridx + (ctx->max_kpts + 1);
