@@ -88,6 +88,9 @@ SIGNATURES = {
     "im_dsm_group_mean": [_P, _P, _P, _P, _P, _P, _P, _L, _P, _P, _P, _P, _P],
     "im_dsm_rasterize": [_P, _P, _P, _P, _P, _P, _L, _P, _P, _I, _P, _I, _D, _D, _D, _D, _D, _P, _P],
     "im_project_colors": [_P, _P, _L, _L, _P, _L, _L, _P, _L, _L, _I, _I, _I, _P, _P, _I, _I, _I, _P, _I, _P, _P, _P, _P],
+    "im_undistort_points": [_P, _P, _L, _P, _P, _P],
+    "im_triangulate_iterative": [_P, _P, _P, _I, _L, _P, _P, _P, _P, _D, _I, _P, _P, _P, _P, _P],
+    "im_triangulate_table": [_P, _P, _I, _I, _P, _I, _I, _D, _I, _L, _P, _P, _P, _P, _P, _P],
 }
 
 

@@ -1,0 +1,2 @@
+"""The part of `icepy4d.core` the reconstruction needs (reference `src/icepy4d/core/camera.py`)."""
+from .camera import Camera, read_opencv_calibration  # noqa: F401

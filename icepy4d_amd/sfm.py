@@ -6,13 +6,19 @@ triangulation is pure numpy in the reference: host and device path here solve th
 reference's OUTPUTS (tests/golden/g10_triangulation.npz, written by importing the reference module; oracle/sfm_cpu.py restates it). Small host-side linear algebra on S <= 1e4 matched points: not a device workload; the RANSAC inside
 `estimate_pose(engine=...)` generates and scores essential-matrix hypotheses on the device (`im_ransac_essential`, csrc/geometry.hip)
 and `triangulate_points_linear(engine=...)` triangulates on the device (`im_triangulate_linear`); the cheirality test and the 5-7
-match case (five-point solver on every 5-subset) stay host numpy: one 3 x 3 matrix."""
-from typing import Optional, Tuple
+match case (five-point solver on every 5-subset) stay host numpy: one 3 x 3 matrix.
+The reference's classes on top (`RelativeOrientation`, `Triangulate`) and what `Triangulate.triangulate_two_views` runs by default -
+`undistort_points`, `iterative_LS_triangulation`, point colours - are at the end of the module: per-point float64 kernels (csrc/sfm.hip),
+for flat arrays of matched points and for every record of a gathered match table at once (`triangulate_table`)."""
+import logging
+from typing import NamedTuple, Optional, Tuple
 
 import numpy as np
 
 from .matching.enums import GeometricVerification
 from .matching.geometric_verification import geometric_verification
+
+logger = logging.getLogger(__name__)
 
 
 def _lift(P, ip) -> np.ndarray:
@@ -299,22 +305,29 @@ def _points(points3d) -> np.ndarray:
 
 def _project_colors(engine, points: np.ndarray, cam: np.ndarray, image=None, chmap=None, want_proj=True):
     import torch
+    proj, col = _project_colors_device(engine, torch.from_numpy(points).to(engine.device), cam, image, chmap, want_proj)
+    return (None if proj is None else proj.cpu().numpy()), (None if col is None else col.cpu().numpy())
+
+
+def _project_colors_device(engine, dp, cam: np.ndarray, image=None, chmap=None, want_proj=True):
+    """`im_project_colors` on [n, 3] float64 points that are on the device already (`Triangulate`, `triangulate_table`: the points never
+    visit the host between the triangulation and the colouring); `image` a host uint8 array or a device tensor. Device tensors out."""
+    import torch
     from ._lib import ptr
     dev = engine.device
-    n = len(points)
-    dp = torch.from_numpy(points).to(dev)
+    n = len(dp)
     proj = torch.empty((n, 2), dtype=torch.float32, device=dev) if want_proj else None
     col = img = None
     h = w = cin = cout = 0
     if image is not None:
         h, w, cin = image.shape
         cout = len(chmap)
-        img = torch.from_numpy(np.ascontiguousarray(image)).to(dev)
+        img = image if torch.is_tensor(image) else torch.from_numpy(np.ascontiguousarray(image)).to(dev)
         col = torch.empty((n, cout), dtype=torch.float64, device=dev)
     base = ptr(dp)
     engine.ctx.call("im_project_colors", base, 0, 3, base + 8, 0, 3, base + 16, 0, 3, 1 if n else 0, n, 0, cam.ctypes.data,
                     ptr(img), h, w, cin, None if chmap is None else chmap.ctypes.data, cout, ptr(proj), ptr(col), None, engine.stream_ptr())
-    return (None if proj is None else proj.cpu().numpy()), (None if col is None else col.cpu().numpy())
+    return proj, col
 
 
 def project_points(points3d, camera, engine=None) -> np.ndarray:
@@ -338,3 +351,297 @@ def interpolate_point_colors(points3d, image, camera, convert_BRG2RGB=True, engi
     cam = _camera_params(camera)
     p = _points(points3d)
     return _project_colors(_engine(engine), p, cam, image, chmap, want_proj=False)[1]
+
+
+# ---- undistortion and least-squares triangulation of matched points (`sfm/geometry.py:103-118`, `thirdparty/triangulation.py:10-177`,
+# `sfm/triangulation.py:42-148`, `sfm/two_view_geometry.py:38-197`): csrc/sfm.hip. No host fallback: `_engine(engine)`.
+DEFAULT_TOLERANCE = 3.0e-5      # depth convergence tolerance of `iterative_LS_triangulation`, absolute
+MAX_SOLVES = 10                 # "Hartley suggests 10 iterations at most"
+
+
+def _intrinsics(camera) -> np.ndarray:
+    """[12] float64 for the kernels of csrc/sfm.hip: fx, fy, cx, cy, k1 k2 p1 p2 k3 k4 k5 k6. Reads only `.K` and `.dist`; distortion
+    vectors of length 0, 4, 5 or 8, like `_camera_params`."""
+    K = np.asarray(camera.K, np.float64).reshape(3, 3)
+    dist = np.zeros(0) if camera.dist is None else np.asarray(camera.dist, np.float64).ravel()
+    if len(dist) not in (0, 4, 5, 8):
+        raise ValueError(f"undistort_points: distortion vectors of length 0, 4, 5 or 8 are supported (got {len(dist)})")
+    if not (np.isfinite(K[0, 0]) and np.isfinite(K[1, 1]) and K[0, 0] != 0 and K[1, 1] != 0):
+        raise ValueError("undistort_points: the focal lengths of K must be finite and non-zero")
+    k = np.zeros(8)
+    k[:len(dist)] = dist
+    return np.ascontiguousarray(np.concatenate([[K[0, 0], K[1, 1], K[0, 2], K[1, 2]], k]))
+
+
+def _projection(camera_or_P) -> np.ndarray:
+    """[12] float64, row-major 3 x 4: a matrix as given (the upper 3 x 4 of a 4 x 4 one), `.P` of a camera, or K [R | t]."""
+    P = camera_or_P
+    if not isinstance(P, np.ndarray):
+        P = P.P if hasattr(P, "P") else np.asarray(P.K, np.float64).reshape(3, 3) @ np.c_[np.asarray(P.R, np.float64).reshape(3, 3),
+                                                                                          np.asarray(P.t, np.float64).reshape(3, 1)]
+    P = np.asarray(P, np.float64)
+    if P.ndim != 2 or P.shape[0] < 3 or P.shape[1] != 4:
+        raise ValueError(f"expected a 3x4 projection matrix (got shape {P.shape})")
+    return np.ascontiguousarray(P[0:3, 0:4]).reshape(12)
+
+
+def _image_points(pts, dtype=np.float32) -> np.ndarray:
+    p = np.ascontiguousarray(pts, dtype=dtype)
+    if p.ndim == 3 and p.shape[1] == 1:          # cv2's [n, 1, 2] layout
+        p = p[:, 0, :]
+    if p.ndim != 2 or p.shape[1] != 2:
+        raise ValueError(f"expected an Nx2 array of image points (got shape {p.shape})")
+    return np.ascontiguousarray(p)
+
+
+def undistort_points(pts, camera, engine=None) -> np.ndarray:
+    """`undistort_points` of the reference (`sfm/geometry.py:103-118`): [n, 2] float32 image points with the lens distortion removed,
+    in pixels of the same K. The reference calls cv2.undistortPoints(pts, K, dist, None, K); here its default path is restated in
+    float64 on the device (`im_undistort_points`): x0 = (u - cx) / fx, FIVE fixed-point iterations of the Brown / rational model
+    (OpenCV's default criteria; its icdist < 0 guard falls back to the distorted point), fx x + cx, cast to float32. Five iterations
+    leave about 1e-6 px of the inverse undone on a 24 MP frame: that is the reference's result, not an error of this port."""
+    cam = _intrinsics(camera)
+    p = _image_points(pts)
+    import torch
+    from ._lib import ptr
+    eng = _engine(engine)
+    d = torch.from_numpy(p).to(eng.device)
+    out = torch.empty_like(d)
+    eng.ctx.call("im_undistort_points", ptr(d), len(p), cam.ctypes.data, ptr(out), eng.stream_ptr())
+    return out.cpu().numpy()
+
+
+def _triangulate_device(eng, u1, u2, P1, P2, cam1=None, cam2=None, tolerance=DEFAULT_TOLERANCE, max_solves=MAX_SOLVES, want_und=False):
+    """`im_triangulate_iterative` on host point arrays: device tensors (X [n, 3] float64, status [n] int32, und1, und2 [n, 2] float32 or None)."""
+    import torch
+    from ._lib import ptr
+    f64 = cam1 is None and (np.asarray(u1).dtype == np.float64 or np.asarray(u2).dtype == np.float64)
+    u1, u2 = _image_points(u1, np.float64 if f64 else np.float32), _image_points(u2, np.float64 if f64 else np.float32)
+    if len(u1) != len(u2):
+        raise ValueError("Number of points don't match.")
+    if not (float(tolerance) >= 0.0):
+        raise ValueError(f"the tolerance must be >= 0 (got {tolerance})")
+    n, dev = len(u1), eng.device
+    d1, d2 = torch.from_numpy(u1).to(dev), torch.from_numpy(u2).to(dev)
+    dX = torch.empty((n, 3), dtype=torch.float64, device=dev)
+    dst = torch.empty(n, dtype=torch.int32, device=dev)
+    und1 = torch.empty((n, 2), dtype=torch.float32, device=dev) if want_und else None
+    und2 = torch.empty((n, 2), dtype=torch.float32, device=dev) if want_und else None
+    eng.ctx.call("im_triangulate_iterative", ptr(d1), ptr(d2), int(f64), n, P1.ctypes.data, P2.ctypes.data,
+                 None if cam1 is None else cam1.ctypes.data, None if cam2 is None else cam2.ctypes.data, float(tolerance), int(max_solves),
+                 ptr(dX), ptr(dst), ptr(und1), ptr(und2), eng.stream_ptr())
+    return dX, dst, und1, und2
+
+
+def iterative_LS_triangulation(u1, P1, u2, P2, tolerance=DEFAULT_TOLERANCE, engine=None) -> Tuple[np.ndarray, np.ndarray]:
+    """`iterative_LS_triangulation` of the reference (`thirdparty/triangulation.py:79-177`; Hartley & Sturm 1997): (points [n, 3] float64,
+    status [n] int64) from image points u1, u2 [n, 2] (pixels of P1, P2: float32 as `undistort_points` returns them, or float64) on the
+    device (`im_triangulate_iterative`), one thread per point. The reference's recurrence, quirks included: the rows of the 4 x 3 system
+    are re-weighted by 1 / depth CUMULATIVELY (the weights of all earlier solves stay on them), the stop test is |d_new - d| <= tolerance
+    on both depths in absolute terms (d = 1 before the first solve), ten solves at most. Each solve is `cv2.solve(DECOMP_SVD)`'s
+    definition, x = V S^+ U^T b with singular values <= 2 DBL_EPSILON * their sum treated as zero, by one-sided Jacobi.
+    Status: 1 in front of both cameras, -1 only in front of the second, -2 only in front of the first, -3 behind both. The reference
+    documents 0 for "not converged, in front of both", but its loop index never reaches 10, so the ten-solve exit is not flagged: a
+    point that used all ten solves has status 1 like one that converged (0 only appears for a NaN depth). Kept as it is."""
+    eng = _engine(engine)
+    dX, dst, _, _ = _triangulate_device(eng, u1, u2, _projection(np.asarray(P1)), _projection(np.asarray(P2)), tolerance=tolerance)
+    return dX.cpu().numpy(), dst.cpu().numpy().astype(np.int64)
+
+
+def linear_LS_triangulation(u1, P1, u2, P2, engine=None) -> Tuple[np.ndarray, np.ndarray]:
+    """`linear_LS_triangulation` of the reference (`thirdparty/triangulation.py:10-76`): the first solve of the iterative form (the same
+    kernel with one solve); (points [n, 3] float64, status [n] bool, all True)."""
+    eng = _engine(engine)
+    dX, _, _, _ = _triangulate_device(eng, u1, u2, _projection(np.asarray(P1)), _projection(np.asarray(P2)), max_solves=1)
+    X = dX.cpu().numpy()
+    return X, np.ones(len(X), dtype=bool)
+
+
+class Triangulate:
+    """`Triangulate` of the reference (`sfm/triangulation.py:42-148`): cameras = list of camera objects (`.K .dist .R .t`, and `.P` or it is
+    formed as K [R | t]), image_points = list of [n, 2] arrays of matched image points, one per camera. Results in `points3d` / `colors`
+    (and `status`, the per-point status of the iterative triangulation)."""
+
+    def __init__(self, cameras=None, image_points=None, engine=None) -> None:
+        self.cameras = cameras
+        self.image_points = image_points
+        self.engine = engine
+        self.points3d = None
+        self.colors = None
+        self.status = None
+
+    def triangulate_two_views(self, views_ids=(0, 1), approach: str = "iterative_LS_triangulation", compute_colors: bool = False,
+                              image: np.ndarray = None, cam_id: int = 0) -> np.ndarray:
+        """[n, 3] float64 points of the two views. "iterative_LS_triangulation" (default): undistortion of both point sets and the
+        iterative triangulation in ONE launch, and with `compute_colors` the colours of `image` seen by `cameras[cam_id]` in a second one
+        that reads the points on the device. "linear_triangulation": `triangulate_points_linear` on the undistorted points (as in the
+        reference this branch computes no colours). Any other approach leaves `points3d` as it was, like the reference."""
+        i0, i1 = views_ids[0], views_ids[1]
+        c0, c1 = self.cameras[i0], self.cameras[i1]
+        if approach == "iterative_LS_triangulation":
+            if compute_colors:
+                assert image is not None and type(image) == np.ndarray, "Invalid input image for interpolating point colors"
+            eng = _engine(self.engine)
+            dX, dst, _, _ = _triangulate_device(eng, self.image_points[i0], self.image_points[i1], _projection(c0), _projection(c1),
+                                                _intrinsics(c0), _intrinsics(c1))
+            self.points3d = dX.cpu().numpy()
+            self.status = dst.cpu().numpy().astype(np.int64)
+            logger.info("Point triangulation succeded: %s.", self.status.sum() / max(self.status.size, 1))
+            if compute_colors:
+                self.colors = _colors_of_device_points(eng, dX, image, self.cameras[cam_id], True)
+            return self.points3d
+        if approach == "linear_triangulation":
+            eng = _engine(self.engine)
+            p0 = undistort_points(self.image_points[i0], c0, engine=eng).astype(np.float64)
+            p1 = undistort_points(self.image_points[i1], c1, engine=eng).astype(np.float64)
+            X = triangulate_points_linear(_projection(c0).reshape(3, 4), _projection(c1).reshape(3, 4), np.c_[p0, np.ones(len(p0))],
+                                          np.c_[p1, np.ones(len(p1))], engine=eng)
+            self.points3d = X[:, :3] / X[:, 3:4]
+        return self.points3d
+
+    def triangulate_nviews(self) -> np.ndarray:
+        """One point seen by every camera: `image_points` = list of homogeneous image points [x, y, 1], one per camera."""
+        return triangulate_nviews([_projection(c).reshape(3, 4) for c in self.cameras], self.image_points)
+
+    def interpolate_colors_from_image(self, image: np.ndarray, camera, convert_BRG2RGB: bool = True) -> np.ndarray:
+        assert self.points3d is not None, "points 3D are not available, Triangulate homologous points first."
+        self.colors = interpolate_point_colors(self.points3d, image, camera, convert_BRG2RGB=convert_BRG2RGB, engine=self.engine)
+        return self.colors
+
+
+def _colors_of_device_points(eng, dX, image, camera, convert_BRG2RGB=True):
+    """`interpolate_point_colors` on points that are on the device: [n, channels] float64 on the host."""
+    assert image.ndim == 3, "invalid input image. Image has not 3 channel"
+    if not (isinstance(image, np.ndarray) and image.dtype == np.uint8) and not (hasattr(image, "device") and str(image.dtype) == "torch.uint8"):
+        raise ValueError(f"interpolate_point_colors: a uint8 image is expected (got {image.dtype})")
+    chmap = _channel_map(image, convert_BRG2RGB)
+    if len(dX) == 0:
+        return np.zeros((0, len(chmap)))
+    return _project_colors_device(eng, dX, _camera_params(camera), image, chmap, want_proj=False)[1].cpu().numpy()
+
+
+class TableReconstruction(NamedTuple):
+    """What `triangulate_table` returns: per-epoch views (lists of length E) into one array each, and the offsets [E + 1] int64."""
+    points3d: list
+    status: list
+    colors: Optional[list]
+    offsets: np.ndarray
+
+
+def _camera_pairs(cameras) -> list:
+    """[cam0, cam1] -> [[cam0, cam1]]; a list of pairs as it is."""
+    return [cameras] if len(cameras) == 2 and not isinstance(cameras[0], (list, tuple)) else list(cameras)
+
+
+def _camera_table(cameras, n_records: int) -> np.ndarray:
+    """[n_cams, 2, 24] float64: P (12), fx fy cx cy, k1..k6 in OpenCV order per camera; one pair, or one pair per record."""
+    pairs = _camera_pairs(cameras)
+    if len(pairs) not in (1, n_records):
+        raise ValueError(f"triangulate_table: one camera pair or one per record ({n_records}) is expected (got {len(pairs)})")
+    out = np.empty((len(pairs), 2, 24))
+    for e, pair in enumerate(pairs):
+        if len(pair) != 2:
+            raise ValueError("triangulate_table: a camera pair has two cameras")
+        for v, c in enumerate(pair):
+            out[e, v, :12] = _projection(c)
+            out[e, v, 12:] = _intrinsics(c)
+    return out
+
+
+def triangulate_table(table, max_kpts: int, cameras, engine=None, undistort: bool = True, image=None, cam_id: int = 1,
+                      tolerance: float = DEFAULT_TOLERANCE, convert_BRG2RGB: bool = True) -> TableReconstruction:
+    """`Triangulate(...).triangulate_two_views(compute_colors=..., cam_id=1)` for EVERY epoch of a gathered match table at once
+    (`sequence.py`: int32 [E, 8 + 6 max_kpts] records with the keypoint payload, a device tensor or a host array). `cameras` is one pair
+    [cam0, cam1] for all epochs or a list of E pairs. Per epoch the matched keypoints are taken in ascending keypoint-0 index (the
+    reference's `kpts0[matches0 > -1]`, `kpts1[matches0[matches0 > -1]]`), undistorted (unless `undistort=False`) and triangulated in one
+    launch over all records; a failed record (n_matches = -1) and an empty one give zero points. `image` (uint8 [h, w, c], or a list of
+    E of them) adds the colours seen by camera `cam_id` of the epoch's pair, read from the points on the device.
+    Returns per-epoch views of points3d [n_e, 3] float64, status [n_e] int64, colors [n_e, channels] float64 (or None), and offsets [E + 1]."""
+    import torch
+    from ._lib import ptr
+    from .sequence import record_words
+    eng = _engine(engine)
+    dev = eng.device
+    K = int(max_kpts)
+    t = table if torch.is_tensor(table) else torch.from_numpy(np.ascontiguousarray(table, dtype=np.int32))
+    if t.dtype != torch.int32 or t.ndim != 2 or t.shape[1] != record_words(K, True):
+        raise ValueError(f"triangulate_table: an int32 table with rows of {record_words(K, True)} words (max_kpts = {K}, with_keypoints=True) "
+                         f"is expected (got {t.dtype}, shape {tuple(t.shape)})")
+    t = t.to(dev).contiguous()
+    E = int(t.shape[0])
+    images = None
+    if image is not None:
+        images = list(image) if isinstance(image, (list, tuple)) else [image]
+        if len(images) not in (1, E):
+            raise ValueError(f"triangulate_table: one image or one per record ({E}) is expected (got {len(images)})")
+    cams = _camera_table(cameras, E) if E else np.zeros((1, 2, 24))
+    if images is not None and len(images) == 1 and len(cams) != 1 and E > 1:
+        raise ValueError("triangulate_table: one image needs one camera pair (with a camera pair per record give an image per record)")
+    dcams = torch.from_numpy(cams).to(dev)
+    M = int(t[:, 3].clamp(min=0).sum().item()) if E else 0
+    doff = torch.empty(E + 1, dtype=torch.int64, device=dev)
+    dX = torch.empty((M, 3), dtype=torch.float64, device=dev)
+    dst = torch.empty(M, dtype=torch.int32, device=dev)
+    eng.ctx.call("im_triangulate_table", ptr(t), E, K, ptr(dcams), len(cams), int(bool(undistort)), float(tolerance), MAX_SOLVES, M,
+                 ptr(doff), ptr(dX) if M else None, ptr(dst) if M else None, None, None, eng.stream_ptr())
+    offsets = doff.cpu().numpy()
+    if int(offsets[-1]) != M:
+        raise RuntimeError(f"triangulate_table: the table changed during the call ({int(offsets[-1])} matches, {M} expected)")
+    X, status = dX.cpu().numpy(), dst.cpu().numpy().astype(np.int64)
+    cuts = offsets[1:-1]
+    colors = None
+    if images is not None and E:
+        pairs = _camera_pairs(cameras)
+        if len(images) == 1:
+            colors = np.split(_colors_of_device_points(eng, dX, images[0], pairs[0][cam_id], convert_BRG2RGB), cuts)
+        else:
+            colors = [_colors_of_device_points(eng, dX[int(offsets[e]):int(offsets[e + 1])], images[e], pairs[e if len(pairs) > 1 else 0][cam_id],
+                                               convert_BRG2RGB) for e in range(E)]
+    if E == 0:
+        return TableReconstruction([], [], None if images is None else [], offsets)
+    return TableReconstruction(np.split(X, cuts), np.split(status, cuts), colors, offsets)
+
+
+class RelativeOrientation:
+    """`RelativeOrientation` of the reference (`sfm/two_view_geometry.py:38-197`): cameras = [cam0, cam1] (`core.Camera`), features = the
+    matched image points [n, 2] of each. The estimation runs in `estimate_pose` / `geometric_verification` (RANSAC on the device)."""
+
+    def __init__(self, cameras, features, engine=None) -> None:
+        self.cameras = cameras
+        self.features = features
+        self.engine = engine
+
+    def estimate_pose(self, threshold: float = 1.0, confidence: float = 0.9999, scale_factor=None) -> np.ndarray:
+        """Relative pose of camera 1 from the matches, chained with the pose of camera 0; updates `cameras[1]`'s extrinsics and returns
+        the inlier mask. With `scale_factor` the translation (estimated up to scale) is multiplied by it."""
+        assert self.cameras[0].extrinsics is not None, \
+            "Extrinsics matrix is not available for camera 0. Please, compute it before running RelativeOrientation estimation."
+        ret = estimate_pose(self.features[0], self.features[1], self.cameras[0].K, self.cameras[1].K, thresh=threshold, conf=confidence,
+                            engine=_engine(self.engine))
+        if ret is None:
+            raise ValueError("RelativeOrientation.estimate_pose: at least 5 matches are needed")
+        R, t, valid = ret
+        logger.info("Relative Orientation - valid points: %d/%d", valid.sum(), len(valid))
+        if scale_factor is not None:
+            t = t * scale_factor
+        else:
+            logger.warning("No scaling factor (e.g., computed from camera baseline) is provided. Two-view-geometry estimated up to a scale factor.")
+        # camera 1 relative to camera 0 first, then its pose chained with camera 0's: world <- cam0 <- cam1 (`two_view_geometry.py:99-105`)
+        cam1 = self.cameras[1]
+        cam1.update_extrinsics(cam1.Rt_to_extrinsics(R, t))
+        cam1.update_extrinsics(cam1.pose_to_extrinsics(self.cameras[0].pose @ cam1.pose))
+        return valid
+
+    def get_scale_factor_from_baseline(self, baseline_world: float) -> float:
+        """baseline_world / |C0 - C1|: the factor that brings the model's baseline to the one measured in the world."""
+        return baseline_world / np.linalg.norm(self.cameras[0].C - self.cameras[1].C)
+
+    def estimate_F_matrix(self, threshold: float = 1, confidence: float = 0.9999, max_iters: int = 10000, **_pydegensac_options):
+        """(F [3, 3], inlier mask [n] bool) by `geometric_verification` (the reference calls pydegensac here, whose remaining options are
+        accepted and not used); `features` keep the inliers only, as in the reference."""
+        self.F, self.inlMask = geometric_verification(self.features[0], self.features[1], GeometricVerification.PYDEGENSAC,
+                                                      threshold=threshold, confidence=confidence, max_iters=max_iters,
+                                                      engine=_engine(self.engine))
+        self.features[0] = self.features[0][self.inlMask]
+        self.features[1] = self.features[1][self.inlMask]
+        return self.F, self.inlMask

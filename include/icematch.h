@@ -286,6 +286,37 @@ int im_project_colors(im_ctx* ctx, const double* d_x, long long sxr, long long s
                       const unsigned char* d_img, int h, int w, int cin, const int32_t* h_chmap, int cout, float* d_proj,
                       double* d_col, unsigned char* d_ortho, void* stream);
 
+/* ---- reconstruction of matched points (`src/icepy4d/sfm/geometry.py`: `undistort_points`; `thirdparty/triangulation.py`:
+ * `iterative_LS_triangulation`, `linear_LS_triangulation`; `sfm/triangulation.py`: `Triangulate`); csrc/sfm.hip ---------------------
+ * A camera's h_cam is [12] float64 in HOST memory: fx, fy, cx, cy, k1 k2 p1 p2 k3 k4 k5 k6 (zeros where absent); a projection matrix
+ * h_P is 3 x 4 row-major float64 in HOST memory. One thread per point, float64, the operations of tests/sfm_oracle.py. Enqueue only.
+ *
+ * im_undistort_points restates cv2.undistortPoints(pts, K, dist, None, K) with the default criteria: x0 = (u - cx) / fx, five
+ * fixed-point iterations of the Brown / rational model (OpenCV's icdist < 0 guard falls back to x0, y0), fx x + cx, float32.
+ * d_pts, d_out [n][2] float32. */
+int im_undistort_points(im_ctx* ctx, const float* d_pts, long long n, const double* h_cam, float* d_out, void* stream);
+/* n point pairs d_u1, d_u2 [n][2] (float32, or float64 with f64 = 1) and one camera pair -> d_X [n][3] float64, d_status [n] int32.
+ * The reference's recurrence: at most max_solves (1..10) least-squares solves of the 4 x 3 system (one-sided Jacobi SVD, singular
+ * values <= 2 DBL_EPSILON * their sum treated as zero, as cv2.solve(DECOMP_SVD)), cumulative re-weighting by 1 / depth, stop when
+ * both depths move by <= tolerance (absolute). status = (d1 > 0 and d2 > 0) - (d1 <= 0) - 2 (d2 <= 0): 1, -1, -2 or -3 (0 only for a
+ * NaN depth; the reference's documented 0 for non-convergence cannot occur). max_solves = 1 is `linear_LS_triangulation`: status 1.
+ * h_cam1 and h_cam2 both given (float32 points only): the points are undistorted first, in the same launch, and rounded to float32
+ * as `undistort_points` returns them; d_und1 / d_und2 [n][2] float32 (optional) receive the points the triangulation used. */
+int im_triangulate_iterative(im_ctx* ctx, const void* d_u1, const void* d_u2, int f64, long long n, const double* h_P1,
+                             const double* h_P2, const double* h_cam1, const double* h_cam2, double tolerance, int max_solves,
+                             double* d_X, int32_t* d_status, float* d_und1, float* d_und2, void* stream);
+/* The same for every record of a gathered match table (`sequence.py`: d_table int32 [n_records][8 + 6 max_kpts] with the keypoint
+ * payload; word [3] = n_matches, -1 for a failed pair = no points; matches0 at word 8, keypoints0 at 8 + 2K, keypoints1 at 8 + 4K).
+ * d_cams [n_cams][2][24] float64 in DEVICE memory, n_cams = n_records or 1: per camera P (12), fx fy cx cy, k1 k2 p1 p2 k3 k4 k5 k6.
+ * d_offsets [n_records + 1] int64 = exclusive scan of max(n_matches, 0) (always written; with m_cap = 0 nothing else is). Record e
+ * fills rows d_offsets[e] .. d_offsets[e + 1] - 1 of d_X [m_cap][3], d_status [m_cap] and (optional) d_und0 / d_und1 [m_cap][2] with
+ * its matched keypoints in ascending keypoint-0 index (the reference's `kpts0[matches0 > -1]` order). Rows >= m_cap are dropped (the
+ * caller compares d_offsets[n_records] with m_cap); a record with fewer valid matches0 entries than n_matches leaves the remaining
+ * rows NaN with status 0. max_kpts <= 16384 (the compaction uses 4 max_kpts bytes of LDS). */
+int im_triangulate_table(im_ctx* ctx, const int32_t* d_table, int n_records, int max_kpts, const double* d_cams, int n_cams,
+                         int undistort, double tolerance, int max_solves, long long m_cap, long long* d_offsets, double* d_X,
+                         int32_t* d_status, float* d_und0, float* d_und1, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,218 @@
+"""The host side of the reconstruction (`icepy4d_amd/core/camera.py`, `icepy4d_amd/sfm.py`: `RelativeOrientation`, `Triangulate`) and the
+numpy restatement of its kernels (tests/sfm_oracle.py) against the reference's outputs in tests/golden/g13_sfm.npz
+(tools/gen_golden_sfm.py: the reference's modules with a stub cv2). No GPU.
+
+Bounds: the restatement reproduces the fixture's undistorted points bit for bit (they were made by it) and the reference's triangulated
+points within 1e-9 * max(1, |X|) * max(1, cond / 1e3) with identical status and solve counts: for a full-rank system the solution of each
+solve is unique, so two SVDs differ by rounding amplified by the condition number, and 1e-9 is the project's bound for g10. The camera
+algebra is products of 4 x 4 matrices in the reference's order: 1e-12."""
+import os
+import re
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import sfm_oracle as S  # noqa: E402
+
+
+@pytest.fixture(scope="module")
+def g13():
+    return S.load_g13(os.path.join(ROOT, "tests", "golden", "g13_sfm.npz"))
+
+
+def bound(g):
+    return 1e-9 * np.maximum(1.0, np.linalg.norm(g["X"], axis=1)) * np.maximum(1.0, g["cond"] / 1e3)
+
+
+def test_oracle_reproduces_g13(g13):
+    g = g13
+    for k, K, d in (("0", g["K0"], g["dist0"]), ("1", g["K1"], g["dist1"])):
+        und = S.undistort_points_f64(g["kpts" + k], K, d)
+        assert und.dtype == np.float32 and np.array_equal(und.view(np.int32), g["und" + k].view(np.int32))
+    X, status, solves, margin = S.triangulate_iterative(g["und0"], g["P0"], g["und1"], g["P1"], 3e-5, 10, details=True)
+    assert np.array_equal(status, g["status"].astype(np.int64)) and np.array_equal(solves, g["solves"].astype(np.int64))
+    assert np.all(np.linalg.norm(X - g["X"], axis=1) <= bound(g))
+    Xl, sl = S.triangulate_iterative(g["und0"], g["P0"], g["und1"], g["P1"], 3e-5, 1)
+    assert (sl == 1).all() and np.all(np.linalg.norm(Xl - g["X_linear"], axis=1) <= bound(g))
+    # what the fixture promises about itself
+    assert set(np.unique(g["status"]).tolist()) >= {1, -3} and ((g["status"] == -1) | (g["status"] == -2)).any()
+    assert g["margin"].min() >= 1e-6 and (g["solves"] == 10).mean() > 0.1 and (g["cond"] > 1e3).sum() >= 80
+    assert (g["status"][g["solves"] == 10] == 1).any()          # ten solves without convergence still give status 1: no 0 anywhere
+    assert not (g["status"] == 0).any()
+
+
+def test_oracle_rank_deficient_solve_is_minimum_norm():
+    rng = np.random.default_rng(3)
+    A = rng.normal(size=(50, 4, 3))
+    A[:25, :, 2] = 2.0 * A[:25, :, 0] - A[:25, :, 1]            # rank 2
+    A[:5] = 0.0                                                  # rank 0
+    b = rng.normal(size=(50, 4))
+    x = S.lstsq43_svd(A, b)
+    for i in range(50):
+        ref = np.linalg.lstsq(A[i], b[i], rcond=1e-13)[0]
+        assert np.allclose(x[i], ref, rtol=1e-9, atol=1e-11), i
+
+
+def test_undistort_guard_and_distortion_lengths():
+    K = np.array([[1000.0, 0, 500.0], [0, 1000.0, 400.0], [0, 0, 1]])
+    pts = np.array([[400.0, 350.0], [500.0, 400.0], [4000.0, -3000.0]], np.float32)
+    assert np.array_equal(S.undistort_points_f64(pts, K, None), S.undistort_points_f64(pts, K, np.zeros(5)))
+    assert np.allclose(S.undistort_points_f64(pts, K, np.zeros(4)), pts, atol=1e-3)
+    # a strongly negative k1 drives icdist below zero far from the centre: the guard returns the distorted point
+    out = S.undistort_points_f64(pts, K, np.array([-0.9, 0.0, 0.0, 0.0]))
+    assert np.array_equal(out[2], pts[2]) and not np.array_equal(out[0], pts[0])
+    with pytest.raises(AssertionError):
+        S.undistort_points_f64(pts, K, np.zeros(3))
+
+
+def replay_camera(g, Camera):
+    """The update sequence of tools/gen_golden_sfm.py:camera_states on `Camera`; yields (state index, camera)."""
+    R, C, t = g["cam_in_R"], g["cam_in_C"], g["cam_in_t"]
+    cam = Camera(6012, 4008, g["K0"], g["dist0"], R=R, t=t[:, 0])
+    yield 0, cam
+    cam.update_extrinsics(cam.pose_to_extrinsics(cam.build_pose_matrix(R.T, C)))
+    yield 1, cam
+    cam.update_K(g["K1"])
+    cam.update_dist(g["dist1"])
+    yield 2, cam
+    cam.update_extrinsics(g["cam_in_ext2"].copy())
+    yield 3, cam
+    cam.reset_EO()
+    yield 4, cam
+
+
+def test_camera_matches_reference_states(g13):
+    from icepy4d_amd.core import Camera
+    g = g13
+    assert g["cam_n_states"].item() == 5
+    for i, cam in replay_camera(g, Camera):
+        for name in ("K", "dist", "extrinsics", "pose", "C", "t", "R", "P"):
+            got, ref = np.asarray(getattr(cam, name), np.float64), g[f"cam_s{i}_{name}"]
+            assert got.shape == ref.shape and np.max(np.abs(got - ref), initial=0.0) <= 1e-12 * max(1.0, np.abs(ref).max()), (i, name)
+        Kf, Rf, tf = cam.factor_P()
+        for got, key in ((Kf, "factor_K"), (Rf, "factor_R"), (tf, "factor_t"), (cam.C_from_P(cam.P), "C_from_P")):
+            ref = g[f"cam_s{i}_{key}"]
+            assert got.shape == ref.shape and np.max(np.abs(got - ref)) <= 1e-12 * max(1.0, np.abs(ref).max()), (i, key)
+        if i == 3:
+            assert np.max(np.abs(cam.extrinsics_to_pose(g["cam_s0_extrinsics"]) - g["cam_s3_pose_of_ext0"])) <= 1e-12
+            assert np.max(np.abs(cam.Rt_to_extrinsics(g["cam_in_R"], g["cam_in_t"]) - g["cam_s3_Rt_to_extrinsics"])) <= 1e-12
+    assert cam.width == 6012 and cam.height == 4008 and np.array_equal(cam.extrinsics, np.eye(4))
+
+
+def test_camera_argument_errors(g13, tmp_path):
+    from icepy4d_amd.core import Camera
+    cam = Camera(100, 80, g13["K0"], g13["dist0"])
+    assert np.array_equal(cam.extrinsics, np.eye(4)) and np.array_equal(cam.C, np.zeros((3, 1)))
+    with pytest.raises(AssertionError):
+        cam.update_extrinsics(np.eye(3))
+    with pytest.raises(AssertionError):
+        cam.update_extrinsics(np.eye(4, dtype=np.float32))
+    bad = np.eye(4)
+    bad[3, 0] = 1.0
+    with pytest.raises(AssertionError):
+        cam.update_extrinsics(bad)
+    with pytest.raises(ValueError):
+        cam.build_pose_matrix(np.eye(4), np.zeros(3))
+    with pytest.raises(ValueError):
+        cam.build_pose_matrix(np.eye(3), np.zeros(4))
+    with pytest.raises(AssertionError):
+        cam.Rt_to_extrinsics(np.eye(3), np.zeros(4))
+    assert cam.build_pose_matrix(np.eye(3), np.array([1.0, 2.0, 3.0]))[:3, 3].tolist() == [1.0, 2.0, 3.0]
+    with pytest.raises(FileNotFoundError):
+        Camera(1, 1, calib_path=tmp_path / "missing.txt")
+    f = tmp_path / "cam.txt"
+    f.write_text("6012 4008 6.6e+03 0. 3.0e+03 0. 6.6e+03 1.9e+03 0. 0. 1. -9.4e-02 8.5e-02 1.7e-04 -8.7e-04 0.\n")
+    c2 = Camera(1, 1, calib_path=f)
+    assert c2.width == 6012 and c2.K[0, 0] == 6600.0 and len(c2.dist) == 5
+
+
+def test_relative_orientation_camera_algebra(g13, monkeypatch):
+    from icepy4d_amd import sfm
+    from icepy4d_amd.core import Camera
+    g = g13
+    seen = {}
+
+    def fixed(kpts0, kpts1, K0, K1, thresh, conf=0.9999, **kw):
+        seen.update(thresh=thresh, conf=conf, n=len(kpts0), engine=kw.get("engine"))
+        return g["ro_R"], g["ro_t"], g["ro_valid"]
+    monkeypatch.setattr(sfm, "estimate_pose", fixed)
+    engine = object()                                   # never touched: the estimate is the fixture's
+    cam0 = Camera(6012, 4008, g["K0"], g["dist0"], extrinsics=g["ro_cam0_extrinsics"].copy())
+    cam1 = Camera(6012, 4008, g["K1"], g["dist1"])
+    feats = [np.zeros((len(g["ro_valid"]), 2)), np.zeros((len(g["ro_valid"]), 2))]
+    ro = sfm.RelativeOrientation([cam0, cam1], feats, engine=engine)
+    valid = ro.estimate_pose(threshold=1.5, confidence=0.999999, scale_factor=g["ro_scale"].item())
+    assert np.array_equal(valid, g["ro_valid"]) and seen == dict(thresh=1.5, conf=0.999999, n=len(feats[0]), engine=engine)
+    for got, key in ((cam1.extrinsics, "ro_cam1_extrinsics"), (cam1.P, "ro_cam1_P"), (cam1.C, "ro_cam1_C")):
+        assert np.max(np.abs(got - g[key])) <= 1e-12 * max(1.0, np.abs(g[key]).max()), key
+    assert abs(ro.get_scale_factor_from_baseline(280.0) - g["ro_scale_from_baseline_280"].item()) <= 1e-12
+    monkeypatch.setattr(sfm, "estimate_pose", lambda *a, **k: None)
+    with pytest.raises(ValueError):
+        ro.estimate_pose()
+
+
+def test_argument_errors_before_any_device_work(g13):
+    """Shapes, distortion lengths and camera tables are checked on the host, before an engine is asked for."""
+    import types
+    from icepy4d_amd import sfm
+    g = g13
+    cam = types.SimpleNamespace(K=g["K0"], dist=np.zeros(3), R=np.eye(3), t=np.zeros(3))
+    with pytest.raises(ValueError):
+        sfm.undistort_points(np.zeros((4, 2), np.float32), cam)
+    cam.dist = g["dist0"]
+    with pytest.raises(ValueError):
+        sfm.undistort_points(np.zeros((4, 3), np.float32), cam)
+    with pytest.raises(ValueError):
+        sfm._projection(np.eye(3))
+    assert np.array_equal(sfm._projection(np.vstack([g["P0"], [0, 0, 0, 1]])), g["P0"].ravel())
+    assert np.allclose(sfm._projection(cam).reshape(3, 4), g["K0"] @ np.eye(3, 4))
+    with pytest.raises(ValueError):
+        sfm._camera_table([[cam, cam], [cam, cam]], 3)
+    tab = sfm._camera_table([cam, cam], 7)
+    assert tab.shape == (1, 2, 24) and tab[0, 1, 12] == g["K0"][0, 0] and np.array_equal(tab[0, 0, 16:21], g["dist0"])
+    t = sfm.Triangulate([cam, cam], [np.zeros((2, 2)), np.zeros((2, 2))])
+    assert t.points3d is None and t.colors is None
+    with pytest.raises(AssertionError):
+        t.interpolate_colors_from_image(np.zeros((4, 4, 3), np.uint8), cam)
+    with pytest.raises(AssertionError):
+        t.triangulate_two_views(compute_colors=True, image=None)
+    X = sfm.Triangulate([types.SimpleNamespace(P=g["P0"]), types.SimpleNamespace(P=g["P1"])],
+                        [np.r_[g["und0"][0], 1.0], np.r_[g["und1"][0], 1.0]]).triangulate_nviews()
+    assert X.shape == (4,) and X[3] == 1.0 and np.linalg.norm(X[:3] - g["X"][0]) < 1e-2 * np.linalg.norm(g["X"][0])
+
+
+def test_pack_table_layout():
+    from icepy4d_amd.sequence import HEADER, record_words
+    rng = np.random.default_rng(0)
+    k0, k1, m0 = S.scatter_matches(rng, rng.uniform(0, 9, (5, 2)).astype(np.float32), rng.uniform(0, 9, (5, 2)).astype(np.float32), 16)
+    t = S.pack_table([(k0, k1, m0), None], 16)
+    assert t.shape == (2, record_words(16, True)) and S.HEADER == HEADER and t[0, 3] == 5 and t[1, 3] == -1
+    assert (t[1, HEADER:HEADER + 16] == -1).all() and np.array_equal(k0[m0 > -1], k0[np.flatnonzero(m0 > -1)])
+    assert np.array_equal(t[0, HEADER + 32:HEADER + 32 + 2 * len(k0)].view(np.float32).reshape(-1, 2), k0)
+
+
+def test_sfm_kernels_stay_in_registers(tmp_path):
+    """csrc/sfm.hip compiled to assembly for gfx950: every kernel without spills and without a private segment (the small matrices of the
+    Jacobi solver are indexed with compile-time constants only, so none of them lands in scratch)."""
+    hipcc = "/opt/rocm/bin/hipcc"
+    if not os.path.exists(hipcc):
+        pytest.skip("no hipcc")
+    out = tmp_path / "sfm.s"
+    r = subprocess.run([hipcc, "-O3", "-std=c++17", "--offload-arch=gfx950", "-S", "--cuda-device-only", "-I" + os.path.join(ROOT, "include"),
+                        os.path.join(ROOT, "icepy4d_amd", "csrc", "sfm.hip"), "-o", str(out)], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-2000:]
+    seen = {}
+    for blk in re.split(r"\n  - \.agpr_count:", out.read_text())[1:]:
+        def field(k):
+            m = re.search(r"\." + k + r":\s+(\S+)", blk)
+            return m.group(1) if m else "0"
+        seen[field("name")] = (int(field("vgpr_spill_count")), int(field("sgpr_spill_count")), int(field("private_segment_fixed_size")))
+    names = " ".join(seen)
+    for k in ("undistort_points_kernel", "triangulate_iterative_kernelIf", "triangulate_iterative_kernelId", "table_offsets_kernel",
+              "triangulate_table_kernel"):
+        assert k in names, (k, list(seen))
+    assert all(v == (0, 0, 0) for v in seen.values()), {k: v for k, v in seen.items() if v != (0, 0, 0)}
