@@ -91,6 +91,10 @@ SIGNATURES = {
     "im_undistort_points": [_P, _P, _L, _P, _P, _P],
     "im_triangulate_iterative": [_P, _P, _P, _I, _L, _P, _P, _P, _P, _D, _I, _P, _P, _P, _P, _P],
     "im_triangulate_table": [_P, _P, _I, _I, _P, _I, _I, _D, _I, _L, _P, _P, _P, _P, _P, _P],
+    "im_binned_lds_capacity": [],
+    "im_binned_cells": [_P, _P, _L, _I, _P, _P, _P, _P, _P, _I, _P, _P],
+    "im_binned_stats": [_P, _P, _P, _L, _I, _L, _P, _I, _P, _P, _P],
+    "im_tracked_points": [_P, _P, _P, _L, _P, _I, _P, _P, _P, _L, _P, _P, _P, _I, _P, _P, _P, _P, _P],
 }
 
 

@@ -7,7 +7,7 @@
 //
 //   dsm_round_kernel        one thread per point: float32 rounding of x, y to the step and the sort keys
 //   dsm_zero_first_kernel   the first row (in the reference's sort order) whose x or y key is +-0: the sign the group keeps
-//   scan_*_kernel           exclusive scans (block sums, one block over them, block-local scan + write) for the group starts
+//   scan_*_kernel (scan.h)  exclusive scans (block sums, one block over them, block-local scan + write) for the group starts
 //                           and for the row spans of the triangles
 //   dsm_group_mean_kernel   one thread per group: pandas' Kahan mean of the group's z in ascending-z order
 //   dsm_raster_kernel       one thread per (triangle, grid row) span: the exact inside test on the span's cells, atomicMin of the
@@ -27,7 +27,6 @@ namespace im {
 namespace {
 
 constexpr double DSM_EPS = 100.0 * 2.220446049250313e-16;   // scipy's inside tolerance, 100 * DBL_EPSILON
-constexpr int SCAN_THREADS = 256;
 constexpr int WIN_NONE = 0x7f7f7f7f;                           // hipMemset byte 0x7f: no triangle contains the cell
 
 // sortable keys: ascending unsigned order == ascending value; -0.0 folded into +0.0 (pandas groups by value)
@@ -70,28 +69,8 @@ __global__ __launch_bounds__(256) void dsm_zero_first_kernel(const float* __rest
     if (yr[i] == 0.f) atomicMin(&first[1], j);
 }
 
-// ---- exclusive scans over per-item counts (group starts: 0 / 1 per sorted row; triangles: grid rows per triangle) ----------------
-__device__ __forceinline__ long long block_excl_scan(long long v, long long& total) {
-    __shared__ long long ws[SCAN_THREADS / IM_WAVE];
-    const int lane = threadIdx.x & (IM_WAVE - 1), w = threadIdx.x / IM_WAVE;
-    long long inc = v;
-#pragma unroll
-    for (int o = 1; o < IM_WAVE; o <<= 1) {
-        const long long u = __shfl_up(inc, o);
-        if (lane >= o) inc += u;
-    }
-    if (lane == IM_WAVE - 1) ws[w] = inc;
-    __syncthreads();
-    long long off = 0, tot = 0;
-#pragma unroll
-    for (int k = 0; k < SCAN_THREADS / IM_WAVE; ++k) {
-        if (k < w) off += ws[k];
-        tot += ws[k];
-    }
-    __syncthreads();
-    total = tot;
-    return off + inc - v;
-}
+// ---- exclusive scans over per-item counts (group starts: 0 / 1 per sorted row; triangles: grid rows per triangle): scan.h -----------
+#include "scan.h"
 
 struct GroupScan {            // 1 where a sorted row starts a new (x, y) group
     const long long* key;     // [n] (x, y) keys
@@ -132,33 +111,6 @@ struct RowScan {              // grid rows (spans) per triangle
     }
     __device__ void write(long long t, long long pos) const { if (t < g.T) offs[t] = pos; }
 };
-
-template <typename S>
-__global__ __launch_bounds__(SCAN_THREADS) void scan_sums_kernel(S s, long long* __restrict__ sums) {
-    long long tot;
-    block_excl_scan(s.count(blockIdx.x * (long long)SCAN_THREADS + threadIdx.x), tot);
-    if (threadIdx.x == 0) sums[blockIdx.x] = tot;
-}
-
-__global__ __launch_bounds__(SCAN_THREADS) void scan_top_kernel(long long* __restrict__ sums, long long nb, long long* __restrict__ total) {
-    long long carry = 0;
-    for (long long base = 0; base < nb; base += SCAN_THREADS) {
-        const long long k = base + threadIdx.x;
-        long long tot;
-        const long long e = block_excl_scan(k < nb ? sums[k] : 0, tot);
-        if (k < nb) sums[k] = carry + e;
-        carry += tot;
-    }
-    if (threadIdx.x == 0) *total = carry;
-}
-
-template <typename S>
-__global__ __launch_bounds__(SCAN_THREADS) void scan_write_kernel(S s, const long long* __restrict__ sums) {
-    const long long j = blockIdx.x * (long long)SCAN_THREADS + threadIdx.x;
-    long long tot;
-    const long long e = block_excl_scan(s.count(j), tot);
-    s.write(j, sums[blockIdx.x] + e);
-}
 
 __global__ __launch_bounds__(256) void dsm_group_mean_kernel(const double* __restrict__ pts, const float* __restrict__ xr,
                                                              const float* __restrict__ yr, const long long* __restrict__ perm_b,
@@ -333,22 +285,9 @@ __global__ __launch_bounds__(256) void proj_color_kernel(ColorArgs a, CamParams 
     }
 }
 
-long long blocks_of(long long n, int t) { return (n + t - 1) / t; }
-
 template <typename K, typename... A>
 hipError_t launch(K kernel, long long blocks, hipStream_t s, A... args) {
     hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(256), 0, s, args...);
-    return hipGetLastError();
-}
-
-size_t up256(size_t b) { return (b + 255) & ~size_t(255); }
-
-template <typename S>
-hipError_t launch_scan(const S& s, long long n, long long* sums, long long* total, hipStream_t st) {
-    const long long nb = std::max(1LL, blocks_of(n, SCAN_THREADS));
-    hipLaunchKernelGGL(scan_sums_kernel<S>, dim3((unsigned)nb), dim3(SCAN_THREADS), 0, st, s, sums);
-    hipLaunchKernelGGL(scan_top_kernel, dim3(1), dim3(SCAN_THREADS), 0, st, sums, nb, total);
-    hipLaunchKernelGGL(scan_write_kernel<S>, dim3((unsigned)nb), dim3(SCAN_THREADS), 0, st, s, (const long long*)sums);
     return hipGetLastError();
 }
 

@@ -317,6 +317,46 @@ int im_triangulate_table(im_ctx* ctx, const int32_t* d_table, int n_records, int
                          int undistort, double tolerance, int max_solves, long long m_cap, long long* d_offsets, double* d_X,
                          int32_t* d_status, float* d_und0, float* d_und1, void* stream);
 
+/* ---- velocity fields (`src/icepy4d/utils/binned_stats.py`: `compute_binned_stats2D`, `compute_binned_stats3D` over
+ * `scipy.stats.binned_statistic_2d / _dd`; `utils/tracking_features_utils.py`: `tracked_points_time_series`, `tracked_dict_to_df`);
+ * csrc/binned.hip. float64, the reference's operations in the reference's order: outputs are bit-identical (tests/golden/g14_velocity.npz).
+ *
+ * im_binned_cells restates scipy's `_bin_numbers` (`_binned_statistic.py:766-795`) for dims = 1..3: d_pts [n][dims]; d_edges = the edge
+ * arrays one behind the other, h_n_edges[d] doubles each, ascending (`bins_from_nodes`: `binned_stats.py:12-31`, `:197-221`). Per
+ * dimension b = np.digitize(x, edges) (a search over the edge doubles; NaN beyond the last edge), one bin to the left when
+ * x >= edges[-1] and np.around(x, decimal) == np.around(edges[-1], decimal), with h_scale[d] = 10 ** |decimal| and h_mode[d] = sign of
+ * decimal (np.around multiplies, rounds and divides for decimal > 0, divides first for decimal < 0). The call carries n_sets point sets
+ * that share the edges: set e = rows d_offsets[e] .. d_offsets[e + 1] - 1 (d_offsets [n_sets + 1] int64, from 0 to n). d_key [n] int64 =
+ * set * cells + cell (row-major over the dimensions) for a point inside in every dimension, n_sets * cells otherwise. Enqueue only.
+ * The caller sorts d_key stably (values -> d_sorted_key, indices -> d_perm): every cell is then a segment of points in input order.
+ * im_binned_stats replaces the statistics of `binned_statistic_dd` (`:596-647`) for n_values columns d_values [n_values][n] at once.
+ * h_slots [7] int32 in the order count, sum, mean, std, min, max, median: the plane of d_out [planes][n_sets][n_values][cells] that
+ * receives the statistic, or -1. count and sum fill empty cells with 0, the others with NaN. sum adds in input order from +0.0
+ * (np.bincount), std = sqrt(sum((v - sum / count)^2) / count) in the same order, min ignores NaN, max is NaN when the cell holds one,
+ * median = (a[(n - 1) / 2] + a[n / 2]) / 2 of the values sorted as numbers (-0.0 == 0.0, NaN last, ties to the lower input index).
+ * Cells of up to im_binned_lds_capacity() points are selected in LDS, larger ones from global memory; both are exact. Scratch from the
+ * context. Enqueue only. */
+int im_binned_lds_capacity(void);
+int im_binned_cells(im_ctx* ctx, const double* d_pts, long long n, int dims, const double* d_edges, const int32_t* h_n_edges,
+                    const double* h_scale, const int32_t* h_mode, const long long* d_offsets, int n_sets, long long* d_key, void* stream);
+int im_binned_stats(im_ctx* ctx, const long long* d_sorted_key, const long long* d_perm, long long n, int n_sets, long long cells,
+                    const double* d_values, int n_values, const int32_t* h_slots, double* d_out, void* stream);
+/* The table of `tracked_dict_to_df` (`tracking_features_utils.py:219-300`) from the series of `tracked_points_time_series` (`:123-169`).
+ * The epochs' rows are concatenated: epoch e = rows d_offsets[e] .. d_offsets[e + 1] - 1 of d_xyz [n_rows][3] (and of every camera's
+ * d_image_points [n_cams][n_rows][2], optional); the caller sorts the track ids stably (d_sorted_ids, d_perm), which orders them by
+ * (id, epoch). d_days [n_epochs] int64 day numbers. Per id: the epochs in which it occurs, inside h_volume (min x y z, max x y z,
+ * inclusive, `geospatial.py:113-117`; null = no volume); tracked when there are at least max(1, min_tracked_epochs); ini / fin = the
+ * first / last of them; d = fin - ini, dt = day_fin - day_ini, v = d / (double)dt, V = sqrt((vx vx + vy vy) + vz vz). Rows are kept
+ * when dt >= *h_min_dt (null = no bound) and lo <= v < hi on every axis whose h_vlims [3][2] lo is not NaN, compacted in ascending id.
+ * d_int_cols [6][n_rows] int64: fid, num_tracked_eps, ep_ini, ep_fin (epoch indices), dt, the row's index among the tracked ids (the
+ * DataFrame's index); d_f64_cols [13 + 4 n_cams][n_rows]: X_ini Y_ini Z_ini X_fin Y_fin Z_fin dX dY dZ vX vY vZ V, then per camera
+ * x_ini y_ini x_fin y_fin. d_member [n_rows] uint8: the input row belongs to the series of a tracked id. *d_n_rows: rows kept. An id
+ * occurs at most once per epoch (the caller checks). Scratch from the context. Enqueue only. */
+int im_tracked_points(im_ctx* ctx, const long long* d_sorted_ids, const long long* d_perm, long long n_rows, const long long* d_offsets,
+                      int n_epochs, const double* d_xyz, const long long* d_days, const double* h_volume, long long min_tracked_epochs,
+                      const long long* h_min_dt, const double* h_vlims, const double* d_image_points, int n_cams, long long* d_int_cols,
+                      double* d_f64_cols, unsigned char* d_member, long long* d_n_rows, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
