@@ -11,8 +11,6 @@ import warnings
 
 import numpy as np
 
-from ..sfm import _engine
-
 STATISTICS = ("count", "sum", "mean", "std", "min", "max", "median")      # the order of `im_binned_stats`' h_slots
 
 
@@ -86,6 +84,7 @@ def binned_statistics(points, values, statistics, edges, offsets=None, engine=No
         decimal = int(-np.log10(dmin)) + 6
         scale.append(10.0 ** abs(decimal))
         mode.append(int(np.sign(decimal)))
+    from ..sfm import _engine      # not at import time: sfm imports matching, which imports this package
     eng = _engine(engine)
     dev = eng.device
     if not isinstance(points, torch.Tensor) and not isinstance(points, np.ndarray):

@@ -8,8 +8,6 @@ from typing import NamedTuple
 
 import numpy as np
 
-from ..sfm import _engine
-
 INT_COLS = ("fid", "num_tracked_eps", "ep_ini", "ep_fin", "dt", "index")
 F64_COLS = ("X_ini", "Y_ini", "Z_ini", "X_fin", "Y_fin", "Z_fin", "dX", "dY", "dZ", "vX", "vY", "vZ", "V")
 
@@ -119,6 +117,7 @@ def tracked_points_table(track_ids, points3d, days, min_tracked_epoches=1, volum
             if np.isnan(lims[k]).any():
                 raise ValueError("tracked_points_table: velocity limits must be numbers")
     h_min_dt = None if min_dt is None else np.array([int(min_dt)], np.int64)
+    from ..sfm import _engine      # not at import time: sfm imports matching, which imports this package
     eng = _engine(engine)
     dev = eng.device
     d_ids = torch.from_numpy(np.concatenate(ids) if M else np.zeros(0, np.int64)).to(dev)

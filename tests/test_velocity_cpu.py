@@ -125,3 +125,14 @@ def test_new_symbols_are_declared_bound_and_built():
         assert name in declared and name in _lib.SIGNATURES and hasattr(lib, name), name
     from icepy4d_amd.utils import binned_stats as M
     assert M.lds_cell_capacity() == lib.im_binned_lds_capacity() > 64
+
+
+@pytest.mark.parametrize("first", ["sfm", "utils.binned_stats"])
+def test_every_module_can_be_the_first_import(first):
+    """`sfm` imports `matching`, which imports `utils`, which imports the velocity modules: these must not need `sfm` at import time.
+    A fresh interpreter, because the order of the imports in this process is the suite's."""
+    import subprocess
+    code = (f"import icepy4d_amd.{first}; from icepy4d_amd import sfm, utils; from icepy4d_amd.sfm import _engine; "
+            "assert callable(utils.binned_stats.binned_statistics) and callable(utils.tracking_features_utils.tracked_points_table)")
+    r = subprocess.run([sys.executable, "-c", code], cwd=ROOT, capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-2000:]
