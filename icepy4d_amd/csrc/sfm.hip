@@ -22,73 +22,13 @@
 #include <cmath>
 
 #include "ctx.h"
-#include "lstsq_jacobi.h"
+#include "sfm_point.h"
 
 namespace im {
 namespace {
 
 constexpr int SFM_THREADS = 256;
 constexpr int SFM_MAX_K = 16384;         // 64 KB of LDS for the compacted indices of one record
-
-// one camera: P (3 x 4, row-major), fx fy cx cy, k1 k2 p1 p2 k3 k4 k5 k6
-struct CamParam { double P[12]; double in[4]; double k[8]; };
-struct CamPair { CamParam c[2]; };
-static_assert(sizeof(CamPair) == 48 * sizeof(double), "camera table rows are 48 doubles");
-
-__device__ __forceinline__ void undistort_one(double u, double v, const CamParam& c, float& ou, float& ov) {
-#pragma clang fp contract(off)
-    const double fx = c.in[0], fy = c.in[1], cx = c.in[2], cy = c.in[3];
-    const double k1 = c.k[0], k2 = c.k[1], p1 = c.k[2], p2 = c.k[3], k3 = c.k[4], k4 = c.k[5], k5 = c.k[6], k6 = c.k[7];
-    const double x0 = (u - cx) / fx, y0 = (v - cy) / fy;
-    double x = x0, y = y0;
-    for (int it = 0; it < 5; ++it) {
-        const double r2 = x * x + y * y;
-        const double icdist = (1.0 + ((k6 * r2 + k5) * r2 + k4) * r2) / (1.0 + ((k3 * r2 + k2) * r2 + k1) * r2);
-        if (icdist < 0.0) { x = x0; y = y0; break; }
-        const double dx = 2.0 * p1 * x * y + p2 * (r2 + 2.0 * x * x);
-        const double dy = p1 * (r2 + 2.0 * y * y) + 2.0 * p2 * x * y;
-        x = (x0 - dx) * icdist;
-        y = (y0 - dy) * icdist;
-    }
-    ou = (float)(fx * x + cx);
-    ov = (float)(fy * y + cy);
-}
-
-// one point from its two (undistorted) image points; returns the status
-__device__ __forceinline__ int triangulate_one(double u1x, double u1y, double u2x, double u2y, const double (&P1)[12], const double (&P2)[12],
-                                               double tol, int max_solves, double (&X)[3]) {
-#pragma clang fp contract(off)
-    double A[4][3], b[4];
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-        A[0][j] = u1x * P1[8 + j] - P1[j];
-        A[1][j] = u1y * P1[8 + j] - P1[4 + j];
-        A[2][j] = u2x * P2[8 + j] - P2[j];
-        A[3][j] = u2y * P2[8 + j] - P2[4 + j];
-    }
-    b[0] = -(u1x * P1[11] - P1[3]);
-    b[1] = -(u1y * P1[11] - P1[7]);
-    b[2] = -(u2x * P2[11] - P2[3]);
-    b[3] = -(u2y * P2[11] - P2[7]);
-    double d1 = 1.0, d2 = 1.0, d1n = 1.0, d2n = 1.0;
-    for (int i = 0; i < max_solves; ++i) {
-        lstsq43_svd(A, b, X);
-        d1n = ((P1[8] * X[0] + P1[9] * X[1]) + P1[10] * X[2]) + P1[11];
-        d2n = ((P2[8] * X[0] + P2[9] * X[1]) + P2[10] * X[2]) + P2[11];
-        if (fabs(d1n - d1) <= tol && fabs(d2n - d2) <= tol) break;
-        const double i1 = 1.0 / d1n, i2 = 1.0 / d2n;     // cumulative: the rows keep the weights of the earlier solves
-#pragma unroll
-        for (int j = 0; j < 3; ++j) { A[0][j] *= i1; A[1][j] *= i1; A[2][j] *= i2; A[3][j] *= i2; }
-        b[0] *= i1; b[1] *= i1; b[2] *= i2; b[3] *= i2;
-        d1 = d1n;
-        d2 = d2n;
-    }
-    if (max_solves == 1) return 1;
-    int st = (d1n > 0.0 && d2n > 0.0) ? 1 : 0;
-    if (d1n <= 0.0) st -= 1;
-    if (d2n <= 0.0) st -= 2;
-    return st;
-}
 
 // image points of one pair -> (undistorted points,) point and status at row `o` of the outputs
 __device__ __forceinline__ void reconstruct_one(float a0, float a1, float b0, float b1, const CamPair& c, int undistort, double tol,
@@ -295,9 +235,11 @@ extern "C" int im_triangulate_table(im_ctx* ctx, const int32_t* d_table, int n_r
     const long long W = 8 + 6LL * max_kpts;
     IM_LAUNCH(ctx, "table_offsets", s, launch(table_offsets_kernel, 1, 0, s, d_table, n_records, W, d_offsets));
     if (n_records && m_cap) {
-        IM_LAUNCH(ctx, "triangulate_table", s, launch(triangulate_table_kernel, n_records, sizeof(int) * (size_t)max_kpts, s, d_table, max_kpts,
-                                                      reinterpret_cast<const CamPair*>(d_cams), n_cams, undistort ? 1 : 0, tolerance, max_solves,
-                                                      m_cap, (const long long*)d_offsets, d_X, d_status, d_und0, d_und1));
+        // K ints of dynamic LDS next to the 16 static bytes of wave_cnt: above 64 KB from K = 16381 on, hence the opt-in (kernels.h)
+        IM_LAUNCH(ctx, "triangulate_table", s, launch_dyn_lds<triangulate_table_kernel>(
+                                                   dim3((unsigned)n_records), dim3(SFM_THREADS), sizeof(int) * (size_t)max_kpts, s, d_table, max_kpts,
+                                                   reinterpret_cast<const CamPair*>(d_cams), n_cams, undistort ? 1 : 0, tolerance, max_solves,
+                                                   m_cap, (const long long*)d_offsets, d_X, d_status, d_und0, d_und1));
     }
     IM_GUARD_CHECK(ctx, s, "im_triangulate_table");
     return 0;

@@ -6,6 +6,8 @@ appears here as one numpy operation on all points, so nothing is fused and nothi
   lstsq43_svd              csrc/lstsq_jacobi.h: x = V S^+ U^T b by one-sided Jacobi, singular values <= 2 DBL_EPSILON * sum treated as zero
   triangulate_iterative    `thirdparty/triangulation.py:79-177` (max_solves = 1: `linear_LS_triangulation`) with its cumulative re-weighting,
                            absolute tolerance and status arithmetic; optionally the per-point diagnostics the fixture stores
+  triangulate_table        the contract of `im_triangulate_table` (one record after the other, one slot after the other): offsets, the
+                           compaction order, the NaN rows of a header that promises too much, the capacity cut
 
 and the helpers the tests share: the procedural colour image, the packing of matches into match-table records, the fixture loader.
 A port of the reference's per-point Python loop to whole-array numpy: its run time is not the reference's."""
@@ -199,3 +201,59 @@ def scatter_matches(rng, kpts0, kpts1, max_kpts):
     m0 = np.full(n0, -1, np.int64)
     m0[slot0] = slot1
     return k0, k1, m0
+
+
+def camera_row(P, K=None, dist=None):
+    """One camera of the device's camera table: [24] float64 = P (12, row-major), fx fy cx cy, k1 k2 p1 p2 k3 k4 k5 k6. Without K: the
+    intrinsics a call without undistortion never reads (focal lengths 1, everything else 0)."""
+    row = np.zeros(24)
+    row[:12] = np.asarray(P, np.float64).reshape(12)
+    row[12:14] = 1.0
+    if K is not None:
+        K = np.asarray(K, np.float64)
+        row[12:16] = K[0, 0], K[1, 1], K[0, 2], K[1, 2]
+        row[16:] = dist8(dist)
+    return row
+
+
+def _undistort_row(pts, row):
+    K = np.array([[row[12], 0.0, row[14]], [0.0, row[13], row[15]], [0.0, 0.0, 1.0]])
+    return undistort_points_f64(pts, K, row[16:24])
+
+
+def triangulate_table(table, K, cams, undistort, tolerance, max_solves, m_cap):
+    """The contract of `im_triangulate_table`, sequentially. table int32 [E, 8 + 6K]; cams float64 [1 or E, 2, 24] (`camera_row`).
+    -> offsets [E + 1] int64 (always the full exclusive scan of max(word 3, 0), the total at [E]) and the rows the call writes, that is rows
+    0 .. min(total, m_cap) - 1 of X [., 3] float64, status [.] int32, und0, und1 [., 2] float32. Per record n_m = max(word 3, 0); the slots
+    i = 0 .. K - 1 with 0 <= matches0[i] < K in ascending order, the first min(count, n_m) of them reconstructed (undistortion through
+    float32 when `undistort`, else the keypoints as they are; `triangulate_iterative`; the record's camera pair or the only one) into rows
+    offsets[e] + r; the rows up to n_m NaN with status 0."""
+    table = np.asarray(table, np.int32)
+    K = int(K)
+    E = len(table)
+    assert table.shape == (E, HEADER + 6 * K)
+    cams = np.asarray(cams, np.float64).reshape(-1, 2, 24)
+    assert len(cams) in (1, E) or E == 0
+    n_m = np.maximum(table[:, 3].astype(np.int64), 0)
+    offsets = np.r_[0, np.cumsum(n_m)].astype(np.int64)
+    total = int(offsets[E])
+    X = np.full((total, 3), np.nan)
+    status = np.zeros(total, np.int32)
+    und0 = np.full((total, 2), np.nan, np.float32)
+    und1 = np.full((total, 2), np.nan, np.float32)
+    for e in range(E):
+        rec = table[e]
+        m0 = rec[HEADER:HEADER + K].astype(np.int64)
+        slots = np.flatnonzero((m0 >= 0) & (m0 < K))[:n_m[e]]
+        if not len(slots):
+            continue
+        k0 = rec[HEADER + 2 * K:HEADER + 4 * K].view(np.float32).reshape(K, 2)[slots]
+        k1 = rec[HEADER + 4 * K:HEADER + 6 * K].view(np.float32).reshape(K, 2)[m0[slots]]
+        c = cams[0 if len(cams) == 1 else e]
+        if undistort:
+            k0, k1 = _undistort_row(k0, c[0]), _undistort_row(k1, c[1])
+        x, st = triangulate_iterative(k0, c[0, :12].reshape(3, 4), k1, c[1, :12].reshape(3, 4), tolerance, max_solves)
+        rows = slice(int(offsets[e]), int(offsets[e]) + len(slots))
+        X[rows], status[rows], und0[rows], und1[rows] = x, st, k0, k1
+    cut = min(total, int(m_cap))
+    return offsets, X[:cut], status[:cut], und0[:cut], und1[:cut]

@@ -5,8 +5,9 @@ Bounds:
   undistortion   float32 output identical to the fixture and to the restatement (same float64 operations in the same order; on the
                  24 MP frame no float32 result sits within 1e-6 ulp of a rounding boundary, so the identity does not hang on the last
                  float64 bits). Five iterations leave ~1e-6 px of round-trip error: the algorithm's own, not tested here.
-  triangulation  status identical; |X - X_ref| <= 1e-9 * max(1, |X_ref|) where the stored cond(A) <= 1e3 (the project's bound for g10),
-                 scaled by cond / 1e3 above. Points whose stored margin to the convergence tolerance is below 1e-6 may be left out, on at
+  triangulation  status and points identical to the restatement; against the fixture status identical and
+                 |X - X_ref| <= 1e-9 * max(1, |X_ref|) where the stored cond(A) <= 1e3 (the project's bound for g10), scaled by
+                 cond / 1e3 above. Points whose stored margin to the convergence tolerance is below 1e-6 may be left out, on at
                  most 1 % of the points (the fixture has none).
   fused / table  bit-identical to the separate calls; colours bit-identical to `interpolate_point_colors`, within 1e-12 of the fixture."""
 import os
@@ -99,9 +100,9 @@ def test_iterative_triangulation_matches_reference(g13, eng):
     assert X.dtype == np.float64 and X.shape == (len(g13["X"]), 3) and status.dtype == np.int64
     check_points(X, status, g13)
     assert set(np.unique(status).tolist()) >= {1, -2, -3}
-    # the restatement follows the same operations: closer than the reference by orders of magnitude
+    # the restatement follows the same operations in the same order: the same bits
     Xo, so = S.triangulate_iterative(g13["und0"], g13["P0"], g13["und1"], g13["P1"])
-    assert np.array_equal(so, status)
+    assert np.array_equal(so, status) and np.array_equal(bits(X), bits(Xo))
     # float64 points take the float64 kernel: the same values here, since float32 converts exactly
     X64, s64 = sfm.iterative_LS_triangulation(g13["und0"].astype(np.float64), g13["P0"], g13["und1"].astype(np.float64), g13["P1"], engine=eng)
     assert np.array_equal(bits(X64), bits(X)) and np.array_equal(s64, status)

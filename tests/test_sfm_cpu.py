@@ -5,7 +5,13 @@ numpy restatement of its kernels (tests/sfm_oracle.py) against the reference's o
 Bounds: the restatement reproduces the fixture's undistorted points bit for bit (they were made by it) and the reference's triangulated
 points within 1e-9 * max(1, |X|) * max(1, cond / 1e3) with identical status and solve counts: for a full-rank system the solution of each
 solve is unique, so two SVDs differ by rounding amplified by the condition number, and 1e-9 is the project's bound for g10. The camera
-algebra is products of 4 x 4 matrices in the reference's order: 1e-12."""
+algebra is products of 4 x 4 matrices in the reference's order: 1e-12.
+The kernels' own text (csrc/sfm_point.h, csrc/lstsq_jacobi.h) compiled for the host equals the restatement bit for bit on every case of
+tests/sfm_cases.py: the same IEEE float64 operations in the same order, contraction off on both sides, division and square root
+correctly rounded. Whoever edits the solver without a device at hand is held to the restatement by that test. It pins the order of the
+operations, the thresholds and the statuses, not the contraction: the host build is for plain x86-64, which has no fused multiply-add, so
+a lost `#pragma clang fp contract(off)` does not show here. That is seen on the device only (tests/test_gpu_sfm_edges.py)."""
+import ctypes
 import os
 import re
 import subprocess
@@ -16,6 +22,7 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
+import sfm_cases as C  # noqa: E402
 import sfm_oracle as S  # noqa: E402
 
 
@@ -216,3 +223,153 @@ def test_sfm_kernels_stay_in_registers(tmp_path):
               "triangulate_table_kernel"):
         assert k in names, (k, list(seen))
     assert all(v == (0, 0, 0) for v in seen.values()), {k: v for k, v in seen.items() if v != (0, 0, 0)}
+
+
+# ---- the kernels' text on the host ---------------------------------------------------------------------------------------------------
+def bits(a):
+    a = np.ascontiguousarray(a)
+    return a.view({4: np.int32, 8: np.int64}[a.dtype.itemsize])
+
+
+@pytest.fixture(scope="module")
+def host_lib(tmp_path_factory):
+    """tests/sfm_host_harness.cpp + csrc/sfm_point.h as a shared library, behind a stub <hip/hip_runtime.h>."""
+    cxx = "/opt/rocm/llvm/bin/clang++"
+    if not os.path.exists(cxx):
+        pytest.skip("no clang++")
+    d = tmp_path_factory.mktemp("sfm_host")
+    (d / "hip").mkdir()
+    (d / "hip" / "hip_runtime.h").write_text("#define __device__\n#define __forceinline__ inline\n")
+    so = d / "libsfm_host.so"
+    r = subprocess.run([cxx, "-O2", "-std=c++17", "-shared", "-fPIC", "-I" + str(d), "-I" + os.path.join(ROOT, "icepy4d_amd", "csrc"),
+                        os.path.join(ROOT, "tests", "sfm_host_harness.cpp"), "-o", str(so)], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lib = ctypes.CDLL(str(so))
+    P, L = ctypes.c_void_p, ctypes.c_longlong
+    lib.sfm_host_undistort.argtypes, lib.sfm_host_undistort.restype = [P, L, P, P], None
+    lib.sfm_host_triangulate.argtypes, lib.sfm_host_triangulate.restype = [P, P, L, P, P, ctypes.c_double, ctypes.c_int, P, P], None
+    return lib
+
+
+def host_triangulate(lib, u1, P1, u2, P2, tolerance, max_solves):
+    a, b = np.ascontiguousarray(u1, np.float64), np.ascontiguousarray(u2, np.float64)
+    p1, p2 = np.ascontiguousarray(P1, np.float64), np.ascontiguousarray(P2, np.float64)
+    X, status = np.empty((len(a), 3)), np.empty(len(a), np.int32)
+    lib.sfm_host_triangulate(a.ctypes.data, b.ctypes.data, len(a), p1.ctypes.data, p2.ctypes.data, tolerance, max_solves, X.ctypes.data,
+                             status.ctypes.data)
+    return X, status
+
+
+def host_undistort(lib, pts, K, dist):
+    p = np.ascontiguousarray(pts, np.float32)
+    cam = np.ascontiguousarray(S.camera_row(np.zeros((3, 4)), K, dist)[12:])
+    out = np.empty_like(p)
+    lib.sfm_host_undistort(p.ctypes.data, len(p), cam.ctypes.data, out.ctypes.data)
+    return out
+
+
+def test_cases_reach_every_status_and_branch(g13):
+    """What tests/sfm_cases.py promises, from the restatement alone: every status value, every solve count, the early exit at every limit,
+    no float64 point on the convergence edge, rank-deficient systems with finite minimum-norm points."""
+    g = g13
+    rows = C.value_rows(g)
+    _, st, solves, _ = S.triangulate_iterative(g["und0"][rows], g["P0"], g["und1"][rows], g["P1"], 3e-5, 10, details=True)
+    assert len(rows) == 237 and len(np.unique(rows)) == 237 and np.array_equal(solves, g["solves"][rows])
+    assert set(np.unique(solves).tolist()) == set(range(2, 11)) and set(np.unique(st).tolist()) == {1, -2, -3}
+    cases = {c[0]: c for c in C.value_cases(g) + C.degenerate_cases(g)}
+    assert len(cases) == len(C.value_cases(g)) + len(C.degenerate_cases(g))
+    Xs = [C.expected(cases[f"max_solves={k}"])[0] for k in range(1, 11)]
+    assert all(not np.array_equal(Xs[k], Xs[k + 1]) for k in range(9))            # each further solve moves some point
+    assert all(not np.array_equal(C.expected(cases[f"tolerance={t}"])[0], Xs[9]) for t in ("0", "1e-09", "0.01"))
+    sw = C.expected(cases["views swapped"])[1]
+    assert (sw == -1).sum() == 60 and (st == -2).sum() == 60 and np.array_equal(sw == -1, st == -2)
+    a, b = C.perturbed64(g)
+    X64, _, _, margin = S.triangulate_iterative(a, g["P0"], b, g["P1"], 3e-5, 10, details=True)
+    assert margin.min() > 5e-5                                                      # 1e-4: far from the edge for any rounding
+    X32 = S.triangulate_iterative(g["und0"], g["P0"], g["und1"], g["P1"], 3e-5, 10)[0]
+    assert (X64 != X32).any(1).all() and np.array_equal(C.expected(cases["float64 points"])[0], X64[rows])
+    X, st2 = C.expected(cases["rank 2: one camera, one image point twice"])
+    assert np.isfinite(X).all() and (X != 0).all() and set(np.unique(st2).tolist()) == {1, -3}
+    X, st0 = C.expected(cases["rank 0: zero projection matrices"])
+    assert (bits(X) == 0).all() and (st0 == -3).all()
+    for name, want in (("NaN in P1[0, 0]", -3), ("NaN in P1[2, 3]", -2), ("NaN in P2[2, 3]", -1), ("NaN in P[2, 3] of both cameras", 0),
+                       ("inf in P1[2, 3], -inf in P2[2, 3]", -2), ("-inf in P1[2, 3], inf in P2[2, 3]", -1)):
+        X, stp = C.expected(cases["non-finite projection: " + name])
+        assert (bits(X) == 0).all() and (stp == want).all(), name                   # X = 0; the status follows P[2, 3] alone
+    for name in ("float32", "float64"):
+        X, stn = C.expected(cases[f"non-finite image points, {name}"])
+        zero = (X == 0).all(1)
+        assert zero.sum() == 48 and np.isfinite(X).all() and (stn[zero] == -3).all() and (stn[~zero] == 1).all()
+    assert not any(np.isnan(C.expected(c)[0]).any() for c in cases.values())        # no NaN out: bit equality has no payload to argue about
+
+
+def test_host_build_equals_the_restatement(g13, host_lib):
+    g = g13
+    for case in C.value_cases(g) + C.degenerate_cases(g):
+        X, status = host_triangulate(host_lib, *case[1:])
+        Xo, so = C.expected(case)
+        bad_x, bad_s = int((bits(X) != bits(Xo)).any(1).sum()), int((status != so).sum())
+        assert bad_x == 0 and bad_s == 0, f"{case[0]}: {bad_x} points and {bad_s} statuses of {len(so)} differ"
+    X, status = host_triangulate(host_lib, g["und0"], g["P0"], g["und1"], g["P1"], 3e-5, 10)
+    Xo, so = S.triangulate_iterative(g["und0"], g["P0"], g["und1"], g["P1"], 3e-5, 10)
+    assert np.array_equal(bits(X), bits(Xo)) and np.array_equal(status, so)
+    for k in ("0", "1"):
+        assert np.array_equal(bits(host_undistort(host_lib, g["kpts" + k], g["K" + k], g["dist" + k])), bits(g["und" + k]))
+    rng = np.random.default_rng(5)
+    pts = np.stack([rng.uniform(0, 6012, 5000), rng.uniform(0, 4008, 5000)], 1).astype(np.float32)
+    pts[:6] = [[np.nan, 1.0], [np.inf, 2.0], [3.0, -np.inf], [3.0e38, 3.0e38], [0.0, 0.0], [-5000.0, 9000.0]]
+    for dist in (g["dist0"], g["dist0"][:4], None, np.r_[g["dist1"], 0.01, -0.02, 0.005], np.array([-0.9, 0.0, 0.0, 0.0])):
+        got, want = host_undistort(host_lib, pts, g["K0"], dist), S.undistort_points_f64(pts, g["K0"], dist)
+        # The NaN rows are rows 0..2 (a NaN or infinite coordinate: r2 is NaN or inf, and inf / inf or 0 * inf makes both coordinates
+        # NaN) and, with the eight-term model alone, row 3 (3e38: within the five iterations both polynomials of icdist overflow, inf / inf). Such a NaN comes out of
+        # an invalid operation, whose sign IEEE 754 leaves open, so only there "NaN on both sides" stands in for equal bits.
+        both_nan = np.isnan(got) & np.isnan(want)
+        assert np.array_equal(bits(got)[~both_nan], bits(want)[~both_nan]), dist
+        assert both_nan[:3].all() and not both_nan[4:].any() and both_nan[3].all() == both_nan[3].any() == (dist is not None and len(dist) == 8), dist
+
+
+# ---- the table contract --------------------------------------------------------------------------------------------------------------
+def test_table_restatement_is_the_flat_calls_per_record(g13):
+    g = g13
+    rng = np.random.default_rng(11)
+    K = 96
+    cuts = [(0, 60), (60, 60), (5040, 5100), (4990, 5053)]
+    epochs = [S.scatter_matches(rng, g["kpts0"][a:b], g["kpts1"][a:b], K) for a, b in cuts]
+    epochs.insert(2, None)
+    cuts.insert(2, (0, 0))
+    table = S.pack_table(epochs, K)
+    pair = [S.camera_row(g["P0"], g["K0"], g["dist0"]), S.camera_row(g["P1"], g["K1"], g["dist1"])]
+    total = int(np.maximum(table[:, 3], 0).sum())
+    assert total == 60 + 60 + 63
+    for undistort in (1, 0):
+        off, X, st, u0, u1 = S.triangulate_table(table, K, [pair], undistort, 3e-5, 10, total)
+        assert off.dtype == np.int64 and off.tolist() == [0, 60, 60, 60, 120, 183] and len(X) == len(st) == len(u0) == len(u1) == total
+        for e, (a, b) in enumerate(cuts):
+            p0, p1 = g["kpts0"][a:b], g["kpts1"][a:b]
+            if undistort:
+                p0, p1 = S.undistort_points_f64(p0, g["K0"], g["dist0"]), S.undistort_points_f64(p1, g["K1"], g["dist1"])
+            Xf, sf = S.triangulate_iterative(p0, g["P0"], p1, g["P1"], 3e-5, 10)
+            rows = slice(off[e], off[e + 1])
+            assert np.array_equal(bits(X[rows]), bits(Xf)) and np.array_equal(st[rows], sf), (undistort, e)
+            assert np.array_equal(bits(u0[rows]), bits(p0)) and np.array_equal(bits(u1[rows]), bits(p1))
+    # the capacity cuts the rows and never the offsets; one pair per record: the record's own
+    off2, X2, st2, _, _ = S.triangulate_table(table, K, [pair], 1, 3e-5, 10, 100)
+    assert np.array_equal(off2, off) and len(X2) == 100 and np.array_equal(st2, S.triangulate_table(table, K, [pair], 1, 3e-5, 10, total)[2][:100])
+    pairs = [pair, pair, pair, [pair[1], pair[0]], pair]
+    _, X3, st3, _, _ = S.triangulate_table(table, K, pairs, 1, 3e-5, 10, total)
+    Xa = S.triangulate_table(table, K, [pair], 1, 3e-5, 10, total)[1]
+    assert np.array_equal(bits(X3[:60]), bits(Xa[:60])) and np.array_equal(bits(X3[120:]), bits(Xa[120:])) and (X3[60:120] != Xa[60:120]).any(1).all()
+    # a header that promises more: NaN rows with status 0; one that promises fewer: the first ones in slot order; a negative one: nothing
+    t2 = table.copy()
+    t2[0, 3], t2[3, 3], t2[4, 3] = 65, 10, -7
+    off4, X4, st4, u04, _ = S.triangulate_table(t2, K, [pair], 1, 3e-5, 10, 10 ** 6)
+    assert off4.tolist() == [0, 65, 65, 65, 75, 75] and len(X4) == 75
+    assert np.isnan(X4[60:65]).all() and (st4[60:65] == 0).all() and np.isnan(u04[60:65]).all()
+    assert np.array_equal(bits(X4[:60]), bits(Xa[:60])) and np.array_equal(bits(X4[65:75]), bits(Xa[60:70]))
+    # entries of matches0 outside [0, K) are no matches
+    t3 = table.copy()
+    slots = np.flatnonzero(t3[0, S.HEADER:S.HEADER + K] >= 0)
+    t3[0, S.HEADER + slots[[1, 5, 7]]] = [K, -2, np.iinfo(np.int32).max]
+    _, X5, _, _, _ = S.triangulate_table(t3, K, [pair], 1, 3e-5, 10, total)
+    keep = np.delete(np.arange(60), [1, 5, 7])
+    assert np.array_equal(bits(X5[:57]), bits(Xa[keep])) and np.isnan(X5[57:60]).all() and np.array_equal(bits(X5[60:]), bits(Xa[60:]))
