@@ -95,6 +95,8 @@ SIGNATURES = {
     "im_binned_cells": [_P, _P, _L, _I, _P, _P, _P, _P, _P, _I, _P, _P],
     "im_binned_stats": [_P, _P, _P, _L, _I, _L, _P, _I, _P, _P, _P],
     "im_tracked_points": [_P, _P, _P, _L, _P, _I, _P, _P, _P, _L, _P, _P, _P, _I, _P, _P, _P, _P, _P],
+    "im_undistort_image": [_P, _P, _I, _I, _I, _I, _P, _P, _P],
+    "im_warp_perspective": [_P, _P, _I, _I, _I, _I, _P, _I, _I, _P, _P],
 }
 
 

@@ -411,6 +411,15 @@ def undistort_points(pts, camera, engine=None) -> np.ndarray:
     return out.cpu().numpy()
 
 
+def undistort_image(image, camera, out_path=None, engine=None):
+    """`undistort_image` of the reference (`sfm/geometry.py:121-143`): a uint8 H x W [x C] image (numpy array or device tensor) with the
+    lens distortion removed, in pixels of the same K; returns the same kind. The reference calls cv2.undistort(image, K, dist, None, K);
+    here its 8-bit bilinear path is restated on the device (`im_undistort_image`, csrc/warp.hip; `utils/homography.py`): bit-identical
+    with tests/warp_oracle.py, parity with an OpenCV binary not pinned. `out_path` writes through PIL, channels as given."""
+    from .utils.homography import undistort_image as impl
+    return impl(image, camera, out_path=out_path, engine=engine)
+
+
 def _triangulate_device(eng, u1, u2, P1, P2, cam1=None, cam2=None, tolerance=DEFAULT_TOLERANCE, max_solves=MAX_SOLVES, want_und=False):
     """`im_triangulate_iterative` on host point arrays: device tensors (X [n, 3] float64, status [n] int32, und1, und2 [n, 2] float32 or None)."""
     import torch

@@ -357,6 +357,23 @@ int im_tracked_points(im_ctx* ctx, const long long* d_sorted_ids, const long lon
                       const long long* h_min_dt, const double* h_vlims, const double* d_image_points, int n_cams, long long* d_int_cols,
                       double* d_f64_cols, unsigned char* d_member, long long* d_n_rows, void* stream);
 
+/* ---- image stabilisation (`src/icepy4d/sfm/geometry.py`: `undistort_image`; `utils/homography.py`: `homography_warping`); csrc/warp.hip.
+ * The reference calls cv2.undistort(src, K, dist, None, K) and cv2.warpPerspective(src, H, (w, h)) on 8-bit images; both are restated
+ * here as OpenCV documents its 8-bit INTER_LINEAR path with BORDER_CONSTANT 0: a float64 source coordinate per output pixel, rounded
+ * to 1/32 pixel (ties to even), four taps with integer weights that sum to 32768, (sum + 16384) >> 15 (csrc/warp_pixel.h,
+ * tests/warp_oracle.py: bit-identical; parity with an OpenCV binary is not pinned). Images are [n_images][h][w][channels] uint8 in
+ * DEVICE memory, channels interleaved and independent. One thread per output pixel. Enqueue only.
+ * im_undistort_image: one camera for all images, h_cam [21] float64 in HOST memory = the inverse of K (9, row-major, by cofactors),
+ * fx fy cx cy, k1 k2 p1 p2 k3 k4 k5 k6 (zeros where absent); d_dst has the shape of d_src.
+ * im_warp_perspective: d_minv [n_images][9] float64 in DEVICE memory, the INVERSE of every image's homography (output -> source,
+ * row-major); d_dst [n_images][oh][ow][channels]. A pixel whose homogeneous w is exactly 0 samples source pixel (0, 0), as OpenCV does.
+ * Both return -74 for a null pointer, source and destination ranges that overlap, channels outside 1..4, a side (h, w, oh, ow) outside
+ * 1..32766 or n_images outside 1..65535. */
+int im_undistort_image(im_ctx* ctx, const uint8_t* d_src, int n_images, int h, int w, int channels, const double* h_cam, uint8_t* d_dst,
+                       void* stream);
+int im_warp_perspective(im_ctx* ctx, const uint8_t* d_src, int n_images, int h, int w, int channels, const double* d_minv, int oh, int ow,
+                        uint8_t* d_dst, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
