@@ -97,6 +97,10 @@ SIGNATURES = {
     "im_tracked_points": [_P, _P, _P, _L, _P, _I, _P, _P, _P, _L, _P, _P, _P, _I, _P, _P, _P, _P, _P],
     "im_undistort_image": [_P, _P, _I, _I, _I, _I, _P, _P, _P],
     "im_warp_perspective": [_P, _P, _I, _I, _I, _I, _P, _I, _I, _P, _P],
+    "im_knn_max_cells": [],
+    "im_knn_cells": [_P, _P, _L, _P, _I, _I, _I, _P, _P],
+    "im_knn_cell_ranges": [_P, _P, _L, _L, _P, _P],
+    "im_knn_self": [_P, _P, _P, _P, _L, _P, _I, _I, _I, _I, _D, _P, _P, _P, _P, _P, _P, _P],
 }
 
 

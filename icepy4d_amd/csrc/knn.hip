@@ -1,0 +1,295 @@
+// Point-cloud neighbourhoods on the device: the exact k nearest neighbours of every point of a cloud within the same cloud, and on top of
+// them the statistic of statistical outlier removal and the normals (`core/point_cloud.py`: `PointCloud.sor_filter`;
+// `post_processing/open3d_fun.py`: `MeshingPoisson.SOR`, `estimate_normals(KDTreeSearchParamHybrid)`). The reference goes through Open3D,
+// an un-vendored dependency: the k nearest neighbours have a definition of their own (ascending d2, the lower index first among equal
+// distances) and are pinned bit for bit against tests/knn_oracle.py; Open3D's published SOR and normal algorithms are restated on top.
+//
+//   knn_cells_kernel    one thread per point: the key (iz * ny + iy) * nx + ix of its cell in a uniform grid (knn_point.h)
+//   knn_ranges_kernel   one thread per cell: the first position of the cell in the key-sorted order (binary search; the stable sort by
+//                       key between the two is torch's, plumbing)
+//   knn_gather_kernel   the cloud in cell order as three coordinate planes plus the original indices (scratch of the context)
+//   knn_self_kernel     one wave per query, queries in cell order so that neighbouring waves read the same cells. The wave visits the
+//                       query's cell, then the shells of cells at Chebyshev ring 1, 2, ... clipped to the grid; a shell is walked as its six
+//                       faces (only those inside the grid), inside a face every run of cells along x is one contiguous range of the
+//                       sorted cloud; the lanes look up the ranges of 64 rows at a time and the ranges that hold points are read 64
+//                       candidates at a time as coalesced loads. A search whose rings have cost more steps than one pass over the whole
+//                       cloud (n / 64) is given up for that pass: the work of a query is bounded whatever the grid.
+//                       The best-k list lives one slot per lane (k <= 64), ascending; a batch is filtered against the k-th entry with one
+//                       ballot and the survivors are inserted one by one by rank counting (ballot + popcount, a shift by one lane): no
+//                       per-thread array, no LDS, no barrier. The search ends by knn_done (knn_point.h): the k-th d2 strictly below the
+//                       conservative bound of everything unvisited, the box covering the grid, or the bound beyond the radius.
+// float64 throughout, contraction off in knn_point.h.
+#include <cmath>
+
+#include "common.h"
+#include "ctx.h"
+#include "knn_point.h"
+
+namespace im {
+namespace {
+
+constexpr long long KNN_MAX_CELLS = 1LL << 24;
+constexpr int KNN_WAVES = 4;          // waves (queries) per block
+constexpr int KNN_MIN_STEPS = 1024;   // steps (64 rows looked up, or 64 candidates read) every ring search may take, whatever the cloud's size
+
+inline size_t up256(size_t b) { return (b + 255) & ~size_t(255); }
+
+__global__ __launch_bounds__(256) void knn_cells_kernel(KnnGrid g, const double* __restrict__ pts, long long n, long long* __restrict__ key) {
+    const long long i = blockIdx.x * 256LL + threadIdx.x;
+    if (i >= n) return;
+    int c[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) c[a] = knn_cell_of(knn_cell_coord(pts[3 * i + a], g.o[a], g.s), g.n[a]);
+    key[i] = knn_key(g, c[0], c[1], c[2]);
+}
+
+// start[c] = the number of sorted keys below c, c = 0..cells
+__global__ __launch_bounds__(256) void knn_ranges_kernel(const long long* __restrict__ skey, long long n, long long cells, int* __restrict__ start) {
+    const long long c = blockIdx.x * 256LL + threadIdx.x;
+    if (c > cells) return;
+    long long lo = 0, hi = n;
+    while (lo < hi) {
+        const long long mid = (lo + hi) >> 1;
+        if (skey[mid] < c) lo = mid + 1; else hi = mid;
+    }
+    start[c] = (int)lo;
+}
+
+struct KnnSorted { double* x; double* y; double* z; int* idx; };
+
+// an index outside the cloud (a permutation that is none) is clamped: the result is then meaningless, but every access stays inside
+__global__ __launch_bounds__(256) void knn_gather_kernel(const double* __restrict__ pts, const long long* __restrict__ perm, long long n, KnnSorted s) {
+    const long long j = blockIdx.x * 256LL + threadIdx.x;
+    if (j >= n) return;
+    long long i = perm[j];
+    i = i < 0 ? 0 : (i >= n ? n - 1 : i);
+    s.x[j] = pts[3 * i]; s.y[j] = pts[3 * i + 1]; s.z[j] = pts[3 * i + 2];
+    s.idx[j] = (int)i;
+}
+
+struct KnnArgs {
+    KnnGrid g;
+    KnnSorted s;
+    const double* pts;      // [n][3], original order
+    const int* start;       // [cells + 1]
+    int n, k;
+    double radius2;
+    int* count; int* idx; double* d2; double* mean; double* normal; int* rings;
+};
+
+// The best-k list of one wave: slot `lane` holds (d2, idx), ascending by knn_less; empty slots and the slots from k on hold (+inf,
+// KNN_NONE). (thr_d2, thr_idx) is slot k - 1, the same in every lane.
+struct KnnList {
+    double d2; int idx;
+    double thr_d2; int thr_idx;
+};
+
+// the candidates at sorted positions [b, e) against the list
+__device__ __forceinline__ void knn_scan(const KnnArgs& a, KnnList& L, int lane, double qx, double qy, double qz, int b, int e) {
+    for (long long base = b; base < e; base += IM_WAVE) {
+        const long long j = base + lane;
+        double cd2 = knn_inf();
+        int ci = KNN_NONE;
+        if (j < e) {
+            cd2 = knn_d2(qx, qy, qz, a.s.x[j], a.s.y[j], a.s.z[j]);
+            ci = a.s.idx[j];
+        }
+        const bool ok = j < e && !knn_outside(cd2, a.radius2) && knn_less(cd2, ci, L.thr_d2, L.thr_idx);
+        unsigned long long m = __ballot(ok);
+        while (m) {
+            const int src = __ffsll((long long)m) - 1;
+            m &= m - 1;
+            const double d = __shfl(cd2, src);
+            const int i = __shfl(ci, src);
+            if (!knn_less(d, i, L.thr_d2, L.thr_idx)) continue;      // the list has moved on since the ballot
+            const int pos = __popcll(__ballot(knn_less(L.d2, L.idx, d, i)));      // the entries before the candidate are a prefix
+            const double ud2 = __shfl_up(L.d2, 1);
+            const int uidx = __shfl_up(L.idx, 1);
+            if (lane == pos) { L.d2 = d; L.idx = i; }
+            else if (lane > pos && lane < a.k) { L.d2 = ud2; L.idx = uidx; }
+            L.thr_d2 = __shfl(L.d2, a.k - 1);
+            L.thr_idx = __shfl(L.idx, a.k - 1);
+        }
+    }
+}
+
+// the sorted positions [b, e) of the cells ix0..ix1 of row (iy, iz): one contiguous range of the sorted cloud
+__device__ __forceinline__ void knn_row_range(const KnnArgs& a, int ix0, int ix1, int iy, int iz, int& b, int& e) {
+    const long long k0 = knn_key(a.g, ix0, iy, iz), k1 = knn_key(a.g, ix1, iy, iz) + 1;
+    b = a.start[k0];
+    e = a.start[k1];
+    b = b < 0 ? 0 : b;
+    e = e > a.n ? a.n : e;          // offsets that are none read nothing outside the cloud
+}
+
+// One strip of a shell: the rows (iy, iz) with iy in ya..yb and iz in za..zb, of each the cells xa..xb (one contiguous range of the
+// sorted cloud). 64 rows per step, one per lane: every lane looks its range up, a ballot keeps the ranges that hold points, and those are
+// scanned one after the other. An empty strip (ya > yb or za > zb) costs nothing. Returns the steps taken, the measure of the search's work.
+__device__ __forceinline__ int knn_strip(const KnnArgs& a, KnnList& L, int lane, double qx, double qy, double qz, int xa, int xb, int ya, int yb,
+                                         int za, int zb) {
+    if (ya > yb || za > zb) return 0;
+    const int wy = yb - ya + 1, rows = wy * (zb - za + 1);              // <= 2^24
+    int steps = 0;
+    for (int base = 0; base < rows; base += IM_WAVE) {
+        const int row = base + lane;
+        int b = 0, e = 0;
+        if (row < rows) knn_row_range(a, xa, xb, ya + row % wy, za + row / wy, b, e);
+        unsigned long long m = __ballot(e > b);
+        ++steps;
+        while (m) {
+            const int src = __ffsll((long long)m) - 1;
+            m &= m - 1;
+            const int sb = __shfl(b, src), se = __shfl(e, src);
+            knn_scan(a, L, lane, qx, qy, qz, sb, se);
+            steps += (se - sb + IM_WAVE - 1) / IM_WAVE;
+        }
+    }
+    return steps;
+}
+
+// The steps a ring search may take before it is given up for one scan of the whole cloud, which takes n / 64 of them: a query far from
+// everything (the lone outlier of a cloud whose grid is long and thin, a line of 2^24 cells) would otherwise walk up to 2^24 empty rings.
+__device__ __forceinline__ long long knn_step_budget(int n) { return KNN_MIN_STEPS + n / (IM_WAVE / 2); }
+
+__global__ __launch_bounds__(IM_WAVE * KNN_WAVES) void knn_self_kernel(KnnArgs a) {
+    const int lane = threadIdx.x & (IM_WAVE - 1);
+    const long long q = (unsigned)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * KNN_WAVES + threadIdx.x / IM_WAVE));      // < 2^31 + 4
+    if (q >= a.n) return;                                             // the whole wave
+    const double qx = a.s.x[q], qy = a.s.y[q], qz = a.s.z[q];
+    const int qi = a.s.idx[q];
+    const double t[3] = {knn_cell_coord(qx, a.g.o[0], a.g.s), knn_cell_coord(qy, a.g.o[1], a.g.s), knn_cell_coord(qz, a.g.o[2], a.g.s)};
+    const int c[3] = {knn_cell_of(t[0], a.g.n[0]), knn_cell_of(t[1], a.g.n[1]), knn_cell_of(t[2], a.g.n[2])};
+    const int nx = a.g.n[0], ny = a.g.n[1], nz = a.g.n[2];
+    const long long budget = knn_step_budget(a.n);
+    KnnList L{knn_inf(), KNN_NONE, knn_inf(), KNN_NONE};
+    long long steps = knn_strip(a, L, lane, qx, qy, qz, c[0], c[0], c[1], c[1], c[2], c[2]);      // ring 0: the query's cell
+    int rings = 1;
+    for (int r = 1; !knn_done(a.g, t, c, r - 1, L.thr_d2, a.radius2); ++r) {
+        if (steps > budget) {
+            // the rings have cost more than the whole cloud would: start again and scan it all, which needs no stop rule
+            L = KnnList{knn_inf(), KNN_NONE, knn_inf(), KNN_NONE};
+            knn_scan(a, L, lane, qx, qy, qz, 0, a.n);
+            rings = -rings;
+            break;
+        }
+        // The shell of ring r, clipped to the grid, as six strips that share no cell: the two z faces over the whole box in x and y,
+        // the two y faces between them, the two x faces between those. Only faces inside the grid are walked, so a grid that is
+        // thin along an axis pays nothing for the faces it does not have.
+        const int x0 = max(0, c[0] - r), x1 = min(nx - 1, c[0] + r);
+        const int y0 = max(0, c[1] - r), y1 = min(ny - 1, c[1] + r);
+        const int yi0 = max(0, c[1] - r + 1), yi1 = min(ny - 1, c[1] + r - 1);
+        const int zi0 = max(0, c[2] - r + 1), zi1 = min(nz - 1, c[2] + r - 1);
+        if (c[2] - r >= 0) steps += knn_strip(a, L, lane, qx, qy, qz, x0, x1, y0, y1, c[2] - r, c[2] - r);
+        if (c[2] + r <= nz - 1) steps += knn_strip(a, L, lane, qx, qy, qz, x0, x1, y0, y1, c[2] + r, c[2] + r);
+        if (c[1] - r >= 0) steps += knn_strip(a, L, lane, qx, qy, qz, x0, x1, c[1] - r, c[1] - r, zi0, zi1);
+        if (c[1] + r <= ny - 1) steps += knn_strip(a, L, lane, qx, qy, qz, x0, x1, c[1] + r, c[1] + r, zi0, zi1);
+        if (c[0] - r >= 0) steps += knn_strip(a, L, lane, qx, qy, qz, c[0] - r, c[0] - r, yi0, yi1, zi0, zi1);
+        if (c[0] + r <= nx - 1) steps += knn_strip(a, L, lane, qx, qy, qz, c[0] + r, c[0] + r, yi0, yi1, zi0, zi1);
+        rings = r + 1;
+    }
+    const bool held = L.idx != KNN_NONE;
+    const int count = __popcll(__ballot(held));
+    if (lane < a.k) {
+        if (a.idx) a.idx[(long long)qi * a.k + lane] = held ? L.idx : -1;
+        if (a.d2) a.d2[(long long)qi * a.k + lane] = held ? L.d2 : knn_inf();
+    }
+    if (lane == 0) {
+        if (a.count) a.count[qi] = count;
+        if (a.rings) a.rings[qi] = rings;
+    }
+    if (a.mean) {
+        const double m = knn_mean_distance([&](int j) { return __shfl(L.d2, j); }, count);
+        if (lane == 0) a.mean[qi] = m;
+    }
+    if (a.normal) {
+        double px = 0.0, py = 0.0, pz = 0.0;
+        if (held) { px = a.pts[3LL * L.idx]; py = a.pts[3LL * L.idx + 1]; pz = a.pts[3LL * L.idx + 2]; }
+        double nrm[3];
+        knn_normal([&](int j, double& x, double& y, double& z) { x = __shfl(px, j); y = __shfl(py, j); z = __shfl(pz, j); }, count, nrm);
+        if (lane == 0) { a.normal[3LL * qi] = nrm[0]; a.normal[3LL * qi + 1] = nrm[1]; a.normal[3LL * qi + 2] = nrm[2]; }
+    }
+}
+
+// what the three entry points refuse about the grid; nullptr when it is fine
+const char* bad_grid(const double* h_grid, int nx, int ny, int nz, KnnGrid& g) {
+    if (!h_grid) return "null grid";
+    const double s = h_grid[3];
+    if (!(s > 0.0) || std::isinf(s)) return "the cell size must be finite and positive";
+    for (int a = 0; a < 3; ++a)
+        if (!std::isfinite(h_grid[a])) return "the origin must be finite";
+    if (nx < 1 || ny < 1 || nz < 1) return "a grid dimension is below 1";
+    if ((long long)nx * ny > KNN_MAX_CELLS || (long long)nx * ny * nz > KNN_MAX_CELLS) return "more cells than im_knn_max_cells()";
+    g.o[0] = h_grid[0]; g.o[1] = h_grid[1]; g.o[2] = h_grid[2];
+    g.s = s;
+    g.n[0] = nx; g.n[1] = ny; g.n[2] = nz;
+    return nullptr;
+}
+
+inline long long blocks_of(long long n, int per) { return (n + per - 1) / per; }
+
+template <typename K, typename... A>
+hipError_t launch(K kernel, long long blocks, hipStream_t s, A... args) {
+    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(256), 0, s, args...);
+    return hipGetLastError();
+}
+static_assert(IM_WAVE * KNN_WAVES == 256, "launch() starts blocks of 256 threads");
+
+}  // namespace
+}  // namespace im
+
+using namespace im;
+
+extern "C" {
+
+int im_knn_max_cells(void) { return (int)KNN_MAX_CELLS; }
+
+int im_knn_cells(im_ctx* ctx, const double* d_pts, long long n, const double* h_grid, int nx, int ny, int nz, long long* d_key, void* stream) {
+    IM_CHECK_CTX(ctx);
+    KnnGrid g;
+    if (!d_pts || !d_key) return ctx->fail(-75, "im_knn_cells: null pointer");
+    if (n < 0 || n >= (1LL << 31)) return ctx->fail(-75, "im_knn_cells: n must be 0..2^31-1");
+    if (const char* why = bad_grid(h_grid, nx, ny, nz, g)) return ctx->fail(-75, "im_knn_cells: %s", why);
+    if (n == 0) return 0;
+    hipStream_t s = (hipStream_t)stream;
+    IM_LAUNCH(ctx, "knn_cells", s, launch(knn_cells_kernel, blocks_of(n, 256), s, g, d_pts, n, d_key));
+    IM_GUARD_CHECK(ctx, s, "im_knn_cells");
+    return 0;
+}
+
+int im_knn_cell_ranges(im_ctx* ctx, const long long* d_sorted_keys, long long n, long long cells, int32_t* d_start, void* stream) {
+    IM_CHECK_CTX(ctx);
+    if (!d_sorted_keys || !d_start) return ctx->fail(-75, "im_knn_cell_ranges: null pointer");
+    if (n < 0 || n >= (1LL << 31)) return ctx->fail(-75, "im_knn_cell_ranges: n must be 0..2^31-1");
+    if (cells < 1 || cells > KNN_MAX_CELLS) return ctx->fail(-75, "im_knn_cell_ranges: cells must be 1..im_knn_max_cells()");
+    if (n == 0) return 0;
+    hipStream_t s = (hipStream_t)stream;
+    IM_LAUNCH(ctx, "knn_ranges", s, launch(knn_ranges_kernel, blocks_of(cells + 1, 256), s, d_sorted_keys, n, cells, d_start));
+    IM_GUARD_CHECK(ctx, s, "im_knn_cell_ranges");
+    return 0;
+}
+
+int im_knn_self(im_ctx* ctx, const double* d_pts, const long long* d_perm, const int32_t* d_start, long long n, const double* h_grid, int nx,
+                int ny, int nz, int k, double radius2, int32_t* d_count, int32_t* d_idx, double* d_d2, double* d_mean, double* d_normal,
+                int32_t* d_rings, void* stream) {
+    IM_CHECK_CTX(ctx);
+    KnnArgs a;
+    if (!d_pts || !d_perm || !d_start) return ctx->fail(-75, "im_knn_self: null pointer");
+    if (n < 0 || n >= (1LL << 31)) return ctx->fail(-75, "im_knn_self: n must be 0..2^31-1");
+    if (k < 1 || k > IM_WAVE) return ctx->fail(-75, "im_knn_self: k must be 1..64");
+    if (const char* why = bad_grid(h_grid, nx, ny, nz, a.g)) return ctx->fail(-75, "im_knn_self: %s", why);
+    if (!(radius2 >= 0.0)) return ctx->fail(-75, "im_knn_self: radius2 must be >= 0 (+inf: no radius)");
+    if (n == 0) return 0;
+    const size_t plane = up256((size_t)n * sizeof(double));
+    IM_GROW(ctx, ctx->grow(ctx->scratch.knn, 3 * plane + up256((size_t)n * sizeof(int)), "knn_sorted"), -22, "im_knn_self: allocation failed");
+    char* base = ctx->scratch.knn.as<char>();
+    a.s.x = (double*)base; a.s.y = (double*)(base + plane); a.s.z = (double*)(base + 2 * plane); a.s.idx = (int*)(base + 3 * plane);
+    a.pts = d_pts; a.start = d_start; a.n = (int)n; a.k = k; a.radius2 = radius2;
+    a.count = d_count; a.idx = d_idx; a.d2 = d_d2; a.mean = d_mean; a.normal = d_normal; a.rings = d_rings;
+    hipStream_t s = (hipStream_t)stream;
+    IM_LAUNCH(ctx, "knn_gather", s, launch(knn_gather_kernel, blocks_of(n, 256), s, d_pts, d_perm, n, a.s));
+    IM_LAUNCH(ctx, "knn_self", s, launch(knn_self_kernel, blocks_of(n, KNN_WAVES), s, a));
+    IM_GUARD_CHECK(ctx, s, "im_knn_self");
+    return 0;
+}
+
+}  // extern "C"

@@ -1,0 +1,196 @@
+"""Neighbourhood work on point clouds, on the device: `knn_search` (the exact k nearest neighbours of every point within its own cloud),
+`remove_statistical_outlier` (SOR; the reference's `core/point_cloud.py::PointCloud.sor_filter` with 10 / 3.0 and
+`post_processing/open3d_fun.py::MeshingPoisson.SOR` with 50 / 1.5) and `estimate_normals` (`open3d_fun.py:178-180`, hybrid search with
+radius 1 and 30 neighbours). One primitive carries all three: csrc/knn.hip (`im_knn_cells`, `im_knn_cell_ranges`, `im_knn_self`; the one
+stable sort by cell key is torch's). Every entry point takes an optional `engine=` (default: the shared engine of device 0) and numpy
+arrays or device tensors; there is no CPU fallback: without a HIP device the calls raise. Non-finite coordinates raise ValueError before
+any launch.
+
+Numerics (tests/test_gpu_pointcloud.py): neighbour indices, counts, squared distances and the mean neighbour distance are bit-identical to
+the brute-force restatement tests/knn_oracle.py: float64, d2 = ((dx*dx) + (dy*dy)) + (dz*dz), ascending, the lower index first among
+equal distances, the point itself included at distance 0. That holds for any cell size: the grid decides the speed, never the result.
+
+PARITY WITH AN OPEN3D BINARY IS UNPINNED. Open3D is not a dependency; its published algorithms are restated:
+  - remove_statistical_outlier: avg_i = mean distance to the nb_neighbors nearest (the point itself among them), cloud mean and sample
+    standard deviation over the avg_i > 0 (the mean divided by the number of points with a neighbour), kept iff 0 < avg_i < mean +
+    std_ratio * std. What could differ from a binary: its KD-tree's choice among neighbours at exactly equal distance (ours: the lower
+    index), the order and width of its sums (ours: float64, left to right, on the host), hence a point whose avg_i lies within rounding
+    of the threshold.
+  - estimate_normals: the eigenvector of the smallest eigenvalue of the two-pass covariance of the neighbours with d2 <= radius^2, at most
+    max_nn of them, by cyclic Jacobi; fewer than three neighbours give (0, 0, 1). Open3D's closed-form eigen solver and its sign are not
+    reproduced: ours makes the first non-zero of (n_z, n_y, n_x) positive. What could differ: the sign, and the direction where two
+    eigenvalues nearly coincide."""
+import math
+
+import numpy as np
+
+MAX_K = 64
+CELL_OCCUPANCY = 0.25      # tunable: the cell size is chosen so that an occupied cell holds about CELL_OCCUPANCY * k points
+
+
+def max_cells() -> int:
+    """The largest grid (in cells) `im_knn_self` accepts."""
+    from .._lib import load
+    return int(load().im_knn_max_cells())
+
+
+def _device_points(points, dev):
+    import torch
+    if isinstance(points, torch.Tensor):
+        pts = points.to(device=dev, dtype=torch.float64).contiguous()
+    else:
+        host = np.ascontiguousarray(points, dtype=np.float64)
+        pts = torch.from_numpy(host if host.flags.writeable else host.copy()).to(dev)
+    if pts.ndim != 2 or pts.shape[1] != 3:
+        raise ValueError(f"points must be [n, 3] (got {tuple(pts.shape)})")
+    if pts.shape[0] >= 2 ** 31:
+        raise ValueError("at most 2^31 - 1 points")
+    if pts.shape[0] and not bool(torch.isfinite(pts).all()):
+        raise ValueError("points hold non-finite coordinates")
+    return pts
+
+
+def grid_dims(lo, hi, s):
+    """Cells per axis of the grid of cell size s over the box [lo, hi]: floor((hi - lo) / s) + 1, the kernels' own arithmetic."""
+    return [int(v) + 1 for v in np.floor((np.asarray(hi, np.float64) - np.asarray(lo, np.float64)) / np.float64(s))]
+
+
+def fit_cell_size(lo, hi, s, cap):
+    """s, enlarged until the grid over [lo, hi] holds at most `cap` cells."""
+    s = float(s)
+    for _ in range(200):
+        with np.errstate(over="ignore"):
+            n = np.floor((np.asarray(hi, np.float64) - np.asarray(lo, np.float64)) / np.float64(s)) + 1.0
+        cells = float(n[0]) * float(n[1]) * float(n[2])
+        if cells <= cap:
+            return s
+        s *= max(1.05, min(2.0 ** 300, (cells / cap) ** (1.0 / 3.0)))
+    raise ValueError("no cell size fits the grid under the cell cap")
+
+
+def _occupied(eng, pts, lo, s, dims):
+    import torch
+    from .._lib import ptr
+    key = torch.empty(pts.shape[0], dtype=torch.int64, device=pts.device)
+    grid = np.array([lo[0], lo[1], lo[2], s], np.float64)
+    eng.ctx.call("im_knn_cells", ptr(pts), pts.shape[0], grid.ctypes.data, dims[0], dims[1], dims[2], ptr(key), eng.stream_ptr())
+    return int(torch.unique(key).numel())
+
+
+def choose_cell_size(eng, pts, lo, hi, k, occupancy=None):
+    """The heuristic behind `cell_size=None`: two coarse binnings (64 and 128 cells along the longest axis) give the number of occupied
+    cells m at two sizes, hence the cloud's box-counting dimension D in 1..3 (a surface: about 2); m(s) ~ s^-D is then solved for
+    n / m(s) = occupancy * k points per occupied cell. A tunable, not a condition of correctness."""
+    n = pts.shape[0]
+    ext = float(np.max(np.asarray(hi) - np.asarray(lo)))
+    if n < 2 or not ext > 0.0:
+        return 1.0
+    target = max(1.0, (CELL_OCCUPANCY if occupancy is None else float(occupancy)) * k)
+    s1, s2 = ext / 64.0, ext / 128.0
+    if not (s2 > 0.0 and math.isfinite(s1)):
+        return ext
+    m1 = _occupied(eng, pts, lo, s1, grid_dims(lo, hi, s1))
+    m2 = _occupied(eng, pts, lo, s2, grid_dims(lo, hi, s2))
+    D = min(3.0, max(1.0, math.log2(max(m2, 1) / max(m1, 1)))) if m2 > m1 else 1.0
+    s = s2 * (m2 * target / n) ** (1.0 / D)
+    return s if (s > 0.0 and math.isfinite(s)) else ext
+
+
+def knn_self(points, k, radius=None, cell_size=None, want=("idx", "d2", "count"), occupancy=None, engine=None):
+    """The primitive: {name: device tensor} for the names in `want` out of idx [n, k] int32, d2 [n, k] float64, count [n] int32, mean [n]
+    float64 (SOR's statistic), normal [n, 3] float64, rings [n] int32 (rings of cells the search visited, the query's cell counted; negated where
+    the search spent its step budget and ended by a scan of the whole cloud),
+    plus "cell_size" and "dims" (host values). All are addressed by the original point index."""
+    import torch
+    from .._lib import ptr
+    from ..sfm import _engine      # not at import time: sfm imports matching, which imports this package
+    k = int(k)
+    if not 1 <= k <= MAX_K:
+        raise ValueError(f"k must be 1..{MAX_K} (got {k})")
+    if radius is not None and not float(radius) >= 0.0:
+        raise ValueError(f"radius must be >= 0 (got {radius})")
+    if cell_size is not None and not (float(cell_size) > 0.0 and math.isfinite(float(cell_size))):
+        raise ValueError(f"cell_size must be finite and positive (got {cell_size})")
+    unknown = set(want) - {"idx", "d2", "count", "mean", "normal", "rings"}
+    if unknown:
+        raise ValueError(f"unknown outputs {sorted(unknown)}")
+    eng = _engine(engine)
+    dev = eng.device
+    pts = _device_points(points, dev)
+    n = pts.shape[0]
+    shapes = {"idx": ((n, k), torch.int32), "d2": ((n, k), torch.float64), "count": ((n,), torch.int32), "mean": ((n,), torch.float64),
+              "normal": ((n, 3), torch.float64), "rings": ((n,), torch.int32)}
+    out = {name: torch.empty(shapes[name][0], dtype=shapes[name][1], device=dev) for name in want}
+    if n == 0:
+        out["cell_size"], out["dims"] = 1.0 if cell_size is None else float(cell_size), [1, 1, 1]
+        return out
+    lo, hi = pts.min(0).values.cpu().numpy(), pts.max(0).values.cpu().numpy()
+    s = choose_cell_size(eng, pts, lo, hi, k, occupancy) if cell_size is None else float(cell_size)
+    s = fit_cell_size(lo, hi, s, max_cells())
+    dims = grid_dims(lo, hi, s)
+    cells = dims[0] * dims[1] * dims[2]
+    st = eng.stream_ptr()
+    grid = np.array([lo[0], lo[1], lo[2], s], np.float64)
+    key = torch.empty(n, dtype=torch.int64, device=dev)
+    eng.ctx.call("im_knn_cells", ptr(pts), n, grid.ctypes.data, dims[0], dims[1], dims[2], ptr(key), st)
+    skey, perm = torch.sort(key, stable=True)
+    start = torch.empty(cells + 1, dtype=torch.int32, device=dev)
+    eng.ctx.call("im_knn_cell_ranges", ptr(skey), n, cells, ptr(start), st)
+    r2 = math.inf if radius is None else float(radius) * float(radius)
+    eng.ctx.call("im_knn_self", ptr(pts), ptr(perm), ptr(start), n, grid.ctypes.data, dims[0], dims[1], dims[2], k, r2,
+                 ptr(out.get("count")), ptr(out.get("idx")), ptr(out.get("d2")), ptr(out.get("mean")), ptr(out.get("normal")),
+                 ptr(out.get("rings")), st)
+    out["cell_size"], out["dims"] = s, dims
+    return out
+
+
+def knn_search(points, k, radius=None, cell_size=None, engine=None, occupancy=None):
+    """(idx [n, k] int32, d2 [n, k] float64, count [n] int32), device tensors: for every point its `count` nearest points of the same
+    cloud, itself first at distance 0, ascending by squared distance with the lower index first among equal distances; unused slots are
+    -1 / +inf. count = min(k, n), or fewer under `radius` (a neighbour is dropped iff d2 > radius^2). `cell_size=None` chooses the grid
+    from the cloud (`choose_cell_size`; `occupancy` overrides CELL_OCCUPANCY); the result does not depend on it."""
+    r = knn_self(points, k, radius=radius, cell_size=cell_size, want=("idx", "d2", "count"), occupancy=occupancy, engine=engine)
+    return r["idx"], r["d2"], r["count"]
+
+
+def sor_indices(avg, count, std_ratio):
+    """Open3D's published rule on the downloaded statistic: (ind ascending int64, threshold). The two sums run in index order on the host
+    (np.cumsum adds left to right), which keeps the threshold bit-identical to the restatement; eight bytes per point is nothing next to
+    the search."""
+    avg = np.asarray(avg, np.float64)
+    valid = int((np.asarray(count) > 0).sum())
+    pos = avg > 0
+    if valid == 0 or not pos.any():
+        return np.zeros(0, np.int64), math.nan
+    with np.errstate(invalid="ignore", divide="ignore"):
+        cloud_mean = np.cumsum(avg[pos])[-1] / np.float64(valid)
+        dev = avg[pos] - cloud_mean
+        std_dev = np.sqrt(np.cumsum(dev * dev)[-1] / np.float64(valid - 1))       # valid == 1: NaN, nothing is kept
+        threshold = cloud_mean + np.float64(std_ratio) * std_dev
+        keep = pos & (avg < threshold)
+    return np.nonzero(keep)[0].astype(np.int64), float(threshold)
+
+
+def remove_statistical_outlier(points, nb_neighbors, std_ratio, engine=None, cell_size=None):
+    """Statistical outlier removal as Open3D publishes it (module docstring; parity with an Open3D binary is unpinned):
+    (kept_points [m, 3], ind [m] ascending). numpy in, numpy out; device tensors in, device tensors out."""
+    import torch
+    if int(nb_neighbors) < 1 or not float(std_ratio) > 0.0:
+        raise ValueError("remove_statistical_outlier: nb_neighbors must be >= 1 and std_ratio > 0")
+    if int(nb_neighbors) > MAX_K:
+        raise ValueError(f"remove_statistical_outlier: nb_neighbors above {MAX_K} is not supported")
+    is_tensor = isinstance(points, torch.Tensor)
+    r = knn_self(points, int(nb_neighbors), cell_size=cell_size, want=("count", "mean"), engine=engine)
+    ind, _ = sor_indices(r["mean"].cpu().numpy(), r["count"].cpu().numpy(), std_ratio)
+    if is_tensor:
+        d_ind = torch.from_numpy(ind).to(points.device)
+        return points.reshape(-1, 3)[d_ind], d_ind
+    return np.asarray(points).reshape(-1, 3)[ind], ind
+
+
+def estimate_normals(points, radius=1.0, max_nn=30, engine=None, cell_size=None):
+    """Normals [n, 3] float64 of the hybrid neighbourhoods (d2 <= radius^2, at most max_nn, the point itself among them); `radius=None`
+    is a plain k-nearest search. See the module docstring for what is and is not Open3D's. numpy in, numpy out; tensor in, tensor out."""
+    import torch
+    r = knn_self(points, int(max_nn), radius=radius, cell_size=cell_size, want=("normal",), engine=engine)
+    return r["normal"] if isinstance(points, torch.Tensor) else r["normal"].cpu().numpy()

@@ -374,6 +374,36 @@ int im_undistort_image(im_ctx* ctx, const uint8_t* d_src, int n_images, int h, i
 int im_warp_perspective(im_ctx* ctx, const uint8_t* d_src, int n_images, int h, int w, int channels, const double* d_minv, int oh, int ow,
                         uint8_t* d_dst, void* stream);
 
+/* ---- point-cloud neighbourhoods (`src/icepy4d/core/point_cloud.py`: `PointCloud.sor_filter`; `post_processing/open3d_fun.py`:
+ * `MeshingPoisson.SOR`, `estimate_normals`); csrc/knn.hip, csrc/knn_point.h. The exact k nearest neighbours of every point of a cloud
+ * within the same cloud, through a uniform grid: origin = the cloud's minimum corner, cubic cells of side s, nx x ny x nz cells,
+ * h_grid [4] float64 in HOST memory = origin x y z, s. The cell of a point is min(n_a - 1, floor((p_a - o_a) / s)) per axis, its key
+ * (iz * ny + iy) * nx + ix. float64, d2 = ((dx*dx) + (dy*dy)) + (dz*dz), no fused operations (tests/knn_oracle.py: bit-identical).
+ * The grid must hold the whole cloud (a point outside is clamped into it: memory-safe, but the neighbours are then not guaranteed).
+ * im_knn_max_cells: the largest nx * ny * nz accepted (2^24).
+ * im_knn_cells: d_pts [n][3] float64 -> d_key [n] int64. The caller sorts the keys (stable) and hands the sorted keys and the
+ * permutation (sorted position -> original index) to the next two calls.
+ * im_knn_cell_ranges: d_sorted_keys [n] -> d_start [cells + 1] int32, the first sorted position of every cell (d_start[cells] = n).
+ * im_knn_self: for every point the k (1..64) nearest points of the cloud, itself included at distance 0, ascending by d2, the lower
+ * original index first among equal distances (which also decides who is kept at the k-th place). radius2 = +inf: plain search;
+ * otherwise a neighbour is dropped iff d2 > radius2 (Open3D's hybrid search). Outputs, each may be NULL, all addressed by ORIGINAL point
+ * index: d_count [n] int32 (min(k, n), fewer under a radius), d_idx [n][k] int32 and d_d2 [n][k] float64 (unused slots -1 / +inf),
+ * d_mean [n] float64 = (sum of sqrt(d2_j), j ascending, from 0.0) / (double)count, -1.0 for count 0 (the statistic of statistical outlier
+ * removal), d_normal [n][3] float64 = unit eigenvector of the smallest eigenvalue of the two-pass covariance of the neighbours (cyclic
+ * Jacobi; first non-zero of (n_z, n_y, n_x) positive; (0, 0, 1) for count < 3), d_rings [n] int32 = rings of cells visited, the query's cell counted (statistics);
+ * negated when the rings had cost more than 1024 + n / 32 steps of 64 rows or candidates and the search ended by one scan of the whole
+ * cloud instead, which bounds the work of a query far from everything whatever the grid.
+ * One wave per query; the cloud in cell order lives in scratch of the context. Enqueue only.
+ * All three return -75, without launching, for a null required pointer (d_pts, d_key; d_sorted_keys, d_start; d_pts, d_perm, d_start,
+ * h_grid), n < 0 or n >= 2^31, k outside 1..64, s or an origin coordinate non-finite or s <= 0, a grid dimension below 1, more cells
+ * than im_knn_max_cells(), radius2 negative or NaN. n == 0 returns 0 and launches nothing. */
+int im_knn_max_cells(void);
+int im_knn_cells(im_ctx* ctx, const double* d_pts, long long n, const double* h_grid, int nx, int ny, int nz, long long* d_key, void* stream);
+int im_knn_cell_ranges(im_ctx* ctx, const long long* d_sorted_keys, long long n, long long cells, int32_t* d_start, void* stream);
+int im_knn_self(im_ctx* ctx, const double* d_pts, const long long* d_perm, const int32_t* d_start, long long n, const double* h_grid, int nx,
+                int ny, int nz, int k, double radius2, int32_t* d_count, int32_t* d_idx, double* d_d2, double* d_mean, double* d_normal,
+                int32_t* d_rings, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
