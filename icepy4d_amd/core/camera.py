@@ -172,3 +172,30 @@ class Camera:
         assert points3d.shape[1] == 3, "Wrong size of the input point array. Provide a nx3 numpy array."
         from ..sfm import project_points
         return project_points(points3d, self, engine=engine)
+
+
+# ---- argument packing of `im_project_colors` (csrc/dsm.hip), shared by `sfm` and `utils.dsm_orthophoto`
+def _camera_params(camera) -> np.ndarray:
+    """[28] float64 for `im_project_colors`: fx, fy, cx, cy, R (row-major), t, k1 k2 p1 p2 k3 k4 k5 k6 s1..s4. Reads only `.K`, `.dist`,
+    `.R` and `.t`, as the reference does. Distortion vectors of length 0, 4, 5 or 8 (OpenCV's forms without thin prism / tilt terms)."""
+    K = np.asarray(camera.K, np.float64).reshape(3, 3)
+    R = np.asarray(camera.R, np.float64).reshape(9)
+    t = np.asarray(camera.t, np.float64).reshape(3)
+    dist = np.zeros(0) if camera.dist is None else np.asarray(camera.dist, np.float64).ravel()
+    if len(dist) not in (0, 4, 5, 8):
+        raise ValueError(f"project_points: distortion vectors of length 0, 4, 5 or 8 are supported (got {len(dist)})")
+    k = np.zeros(12)
+    k[:len(dist)] = dist
+    return np.ascontiguousarray(np.concatenate([[K[0, 0], K[1, 1], K[0, 2], K[1, 2]], R, t, k]))
+
+
+def _channel_map(image: np.ndarray, convert_BRG2RGB: bool) -> np.ndarray:
+    """Output channel -> image channel: cv2.cvtColor(BGR2RGB) keeps B, G, R reversed (and drops a fourth channel)."""
+    c = image.shape[2]
+    if convert_BRG2RGB:
+        if c not in (3, 4):
+            raise ValueError(f"interpolate_point_colors: BGR to RGB needs a 3- or 4-channel image (got {c})")
+        return np.array([2, 1, 0], np.int32)
+    if not 1 <= c <= 4:
+        raise ValueError(f"interpolate_point_colors: 1 to 4 channels are supported (got {c})")
+    return np.arange(c, dtype=np.int32)

@@ -21,13 +21,13 @@
 
 #include "common.h"
 #include "ctx.h"
+#include "stage_scratch.h"
 
 namespace im {
 namespace {
 
 #include "scan.h"
 
-constexpr int BIN_GROUP = 8;          // cells up to this size: eight lanes each
 constexpr int BIN_LDS_CAP = 4096;     // cells up to this size are selected from LDS (32 KB of keys), larger ones from global memory
 constexpr unsigned long long KEY_ZERO = 0x8000000000000000ull, KEY_NAN = ~0ull;
 enum { ST_COUNT, ST_SUM, ST_MEAN, ST_STD, ST_MIN, ST_MAX, ST_MEDIAN, ST_N };
@@ -384,12 +384,6 @@ struct KeptRowScan {          // the rows that pass `tracked_dict_to_df`'s filte
     }
 };
 
-template <typename K, typename... A>
-hipError_t launch(K kernel, long long blocks, hipStream_t s, A... args) {
-    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(256), 0, s, args...);
-    return hipGetLastError();
-}
-
 }  // namespace
 }  // namespace im
 
@@ -417,7 +411,7 @@ extern "C" int im_binned_cells(im_ctx* ctx, const double* d_pts, long long n, in
     if (!n) return 0;
     if (!d_pts || !d_key) return ctx->fail(-72, "im_binned_cells: bad arguments");
     hipStream_t s = (hipStream_t)stream;
-    IM_LAUNCH(ctx, "bin_cells", s, launch(bin_cells_kernel, blocks_of(n, 256), s, g, d_pts, n, d_offsets, n_sets, cells, d_key));
+    IM_LAUNCH(ctx, "bin_cells", s, launch(bin_cells_kernel, blocks_of(n, 256), 256, 0, s, g, d_pts, n, d_offsets, n_sets, cells, d_key));
     IM_GUARD_CHECK(ctx, s, "im_binned_cells");
     return 0;
 }
@@ -439,36 +433,34 @@ extern "C" int im_binned_stats(im_ctx* ctx, const long long* d_sorted_key, const
     }
     if (!n_slots) return 0;
     hipStream_t s = (hipStream_t)stream;
-    const long long nb = blocks_of(n_seg, SCAN_THREADS);
-    const size_t o_counts = 0, o_starts = up256(n_seg * sizeof(unsigned)), o_list = o_starts + up256((n_seg + 1) * sizeof(long long));
-    const size_t o_sums = o_list + up256((n / BIN_GROUP + 1) * sizeof(long long)), o_nlist = o_sums + up256(nb * sizeof(long long));
-    IM_GROW(ctx, ctx->grow(ctx->scratch.binned, o_nlist + 256, "binned.scratch"), -71, "im_binned_stats: out of device memory (%lld cells)", n_seg);
-    char* const sc = ctx->scratch.binned.as<char>();
-    unsigned* counts = reinterpret_cast<unsigned*>(sc + o_counts);
-    long long* starts = reinterpret_cast<long long*>(sc + o_starts);
-    long long* list = reinterpret_cast<long long*>(sc + o_list);
-    long long* sums = reinterpret_cast<long long*>(sc + o_sums);
-    long long* n_list = reinterpret_cast<long long*>(sc + o_nlist);
+    const BinnedStatsScratch lay(n, n_seg);
+    IM_GROW(ctx, ctx->grow(ctx->scratch.binned, lay.bytes, "binned.scratch"), -71, "im_binned_stats: out of device memory (%lld cells)", n_seg);
+    void* const sc = ctx->scratch.binned.p;
+    unsigned* counts = lay.counts.at(sc);
+    long long* starts = lay.starts.at(sc);
+    long long* list = lay.list.at(sc);
+    long long* sums = lay.sums.at(sc);
+    long long* n_list = lay.n_list.at(sc);
     IM_HIP(ctx, hipMemsetAsync(counts, 0, n_seg * sizeof(unsigned), s));
-    if (n) IM_LAUNCH(ctx, "bin_hist", s, launch(bin_hist_kernel, blocks_of(n, 256), s, d_sorted_key, n, n_seg, counts));
+    if (n) IM_LAUNCH(ctx, "bin_hist", s, launch(bin_hist_kernel, blocks_of(n, 256), 256, 0, s, d_sorted_key, n, n_seg, counts));
     const CountScan cs{counts, n_seg, starts};
     IM_LAUNCH(ctx, "bin_offsets_scan", s, launch_scan(cs, n_seg, sums, starts + n_seg, s));
     a.starts = starts; a.perm = d_perm; a.vals = d_values; a.N = n; a.n_seg = n_seg; a.C = cells; a.E = n_sets; a.V = n_values; a.out = d_out;
-    if (basic) IM_LAUNCH(ctx, "bin_basic", s, launch(bin_basic_kernel, blocks_of(items, 256), s, a));
+    if (basic) IM_LAUNCH(ctx, "bin_basic", s, launch(bin_basic_kernel, blocks_of(items, 256), 256, 0, s, a));
     if (a.slot[ST_MEDIAN] >= 0) {
         const LargeScan ls{starts, n_seg, list};
         IM_LAUNCH(ctx, "bin_large_scan", s, launch_scan(ls, n_seg, sums, n_list, s));
-        int cus = 256;
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device) != hipSuccess) cus = 256;
+        int cus = 0;
+        IM_HIP(ctx, device_cu_count(&cus));
         const long long n_large_max = n / (BIN_GROUP + 1);       // the listed cells hold more than BIN_GROUP points each
-        IM_LAUNCH(ctx, "bin_median_8", s, launch(bin_median_group_kernel<BIN_GROUP>, std::min(blocks_of(items, 256 / BIN_GROUP), cus * 64LL), s, a,
+        IM_LAUNCH(ctx, "bin_median_8", s, launch(bin_median_group_kernel<BIN_GROUP>, std::min(blocks_of(items, 256 / BIN_GROUP), cus * 64LL), 256, 0, s, a,
                                                  (const long long*)nullptr, (const long long*)nullptr));
         if (n_large_max) {
             const long long large_items = n_large_max * n_values;
-            IM_LAUNCH(ctx, "bin_median_64", s, launch(bin_median_group_kernel<IM_WAVE>, std::min(blocks_of(large_items, 256 / IM_WAVE), cus * 32LL), s, a,
+            IM_LAUNCH(ctx, "bin_median_64", s, launch(bin_median_group_kernel<IM_WAVE>, std::min(blocks_of(large_items, 256 / IM_WAVE), cus * 32LL), 256, 0, s, a,
                                                       (const long long*)list, (const long long*)n_list));
             if (n > IM_WAVE)
-                IM_LAUNCH(ctx, "bin_median_block", s, launch(bin_median_block_kernel, std::min((n / (IM_WAVE + 1)) * n_values, cus * 8LL), s, a,
+                IM_LAUNCH(ctx, "bin_median_block", s, launch(bin_median_block_kernel, std::min((n / (IM_WAVE + 1)) * n_values, cus * 8LL), 256, 0, s, a,
                                                              (const long long*)list, (const long long*)n_list));
         }
     }
@@ -487,10 +479,10 @@ extern "C" int im_tracked_points(im_ctx* ctx, const long long* d_sorted_ids, con
     IM_HIP(ctx, hipMemsetAsync(d_n_rows, 0, sizeof(long long), s));
     if (!n_rows) return 0;
     if (!d_sorted_ids || !d_perm || !d_xyz || !d_int_cols || !d_f64_cols || !d_member) return ctx->fail(-72, "im_tracked_points: bad arguments");
-    const long long M = n_rows, nb = blocks_of(M, SCAN_THREADS);
-    const size_t o_starts = 0, o_pre = up256(M * sizeof(long long)), o_sums = 2 * o_pre, o_nids = o_sums + up256(nb * sizeof(long long));
-    IM_GROW(ctx, ctx->grow(ctx->scratch.binned, o_nids + 512, "binned.scratch"), -71, "im_tracked_points: out of device memory");
-    char* const sc = ctx->scratch.binned.as<char>();
+    const long long M = n_rows;
+    const TrackedPointsScratch lay(M);
+    IM_GROW(ctx, ctx->grow(ctx->scratch.binned, lay.bytes, "binned.scratch"), -71, "im_tracked_points: out of device memory");
+    void* const sc = ctx->scratch.binned.p;
     TrackArgs a{};
     a.sid = d_sorted_ids; a.perm = d_perm; a.M = M; a.offsets = d_offsets; a.E = n_epochs; a.xyz = d_xyz; a.days = d_days;
     a.has_vol = h_volume != nullptr;
@@ -503,10 +495,10 @@ extern "C" int im_tracked_points(im_ctx* ctx, const long long* d_sorted_ids, con
         a.lim[2 * k] = h_vlims[2 * k]; a.lim[2 * k + 1] = h_vlims[2 * k + 1];
     }
     a.img = d_image_points; a.n_cams = n_cams;
-    a.starts = reinterpret_cast<long long*>(sc + o_starts);
-    a.pre = reinterpret_cast<long long*>(sc + o_pre);
-    long long* sums = reinterpret_cast<long long*>(sc + o_sums);
-    long long* n_ids = reinterpret_cast<long long*>(sc + o_nids);
+    a.starts = lay.starts.at(sc);
+    a.pre = lay.pre.at(sc);
+    long long* sums = lay.sums.at(sc);
+    long long* n_ids = lay.n_ids.at(sc);
     long long* n_tracked = n_ids + 1;
     a.n_ids = n_ids;
     a.oi = d_int_cols; a.od = d_f64_cols; a.member = d_member;

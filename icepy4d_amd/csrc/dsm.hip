@@ -22,6 +22,7 @@
 
 #include "common.h"
 #include "ctx.h"
+#include "stage_scratch.h"
 
 namespace im {
 namespace {
@@ -285,12 +286,6 @@ __global__ __launch_bounds__(256) void proj_color_kernel(ColorArgs a, CamParams 
     }
 }
 
-template <typename K, typename... A>
-hipError_t launch(K kernel, long long blocks, hipStream_t s, A... args) {
-    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(256), 0, s, args...);
-    return hipGetLastError();
-}
-
 }  // namespace
 }  // namespace im
 
@@ -303,8 +298,7 @@ extern "C" int im_dsm_round(im_ctx* ctx, const double* d_pts, long long n, float
     if (step == 0.f || !std::isfinite(step)) return ctx->fail(-72, "im_dsm_round: the step must be non-zero and finite");
     if (!n) return 0;
     hipStream_t s = (hipStream_t)stream;
-    IM_LAUNCH(ctx, "dsm_round", s, launch(dsm_round_kernel, blocks_of(n, 256), s, d_pts, n, step, d_xr,
-                                                       d_yr, d_xykey, d_ykey, d_zkey));
+    IM_LAUNCH(ctx, "dsm_round", s, launch(dsm_round_kernel, blocks_of(n, 256), 256, 0, s, d_pts, n, step, d_xr, d_yr, d_xykey, d_ykey, d_zkey));
     IM_GUARD_CHECK(ctx, s, "im_dsm_round");
     return 0;
 }
@@ -320,19 +314,16 @@ extern "C" int im_dsm_group_mean(im_ctx* ctx, const double* d_pts, const float* 
         IM_HIP(ctx, hipMemsetAsync(d_n_groups, 0, sizeof(long long), s));
         return 0;
     }
-    const long long nb = blocks_of(n, SCAN_THREADS);
-    const size_t o_sums = 0, o_starts = up256(nb * sizeof(long long)), o_first = o_starts + up256(n * sizeof(long long));
-    IM_GROW(ctx, ctx->grow(ctx->scratch.dsm, o_first + 256, "dsm.scratch"), -71, "im_dsm_group_mean: out of device memory");
-    char* const sc = ctx->scratch.dsm.as<char>();
-    long long* sums = reinterpret_cast<long long*>(sc + o_sums);
-    long long* starts = reinterpret_cast<long long*>(sc + o_starts);
-    int* first = reinterpret_cast<int*>(sc + o_first);
+    const DsmGroupScratch lay(n);
+    IM_GROW(ctx, ctx->grow(ctx->scratch.dsm, lay.bytes, "dsm.scratch"), -71, "im_dsm_group_mean: out of device memory");
+    void* const sc = ctx->scratch.dsm.p;
+    long long* starts = lay.starts.at(sc);
+    int* first = lay.first.at(sc);
     IM_HIP(ctx, hipMemsetAsync(first, 0x7f, 2 * sizeof(int), s));
-    IM_LAUNCH(ctx, "dsm_zero_first", s, launch(dsm_zero_first_kernel, blocks_of(n, 256), s, d_xr, d_yr,
-                                                            d_perm_b, (int)n, first));
+    IM_LAUNCH(ctx, "dsm_zero_first", s, launch(dsm_zero_first_kernel, blocks_of(n, 256), 256, 0, s, d_xr, d_yr, d_perm_b, (int)n, first));
     const GroupScan gs{d_xykey, d_perm_c, n, starts};
-    IM_LAUNCH(ctx, "dsm_group_scan", s, launch_scan(gs, n, sums, d_n_groups, s));
-    IM_LAUNCH(ctx, "dsm_group_mean", s, launch(dsm_group_mean_kernel, blocks_of(n, 256), s, d_pts, d_xr,
+    IM_LAUNCH(ctx, "dsm_group_scan", s, launch_scan(gs, n, lay.sums.at(sc), d_n_groups, s));
+    IM_LAUNCH(ctx, "dsm_group_mean", s, launch(dsm_group_mean_kernel, blocks_of(n, 256), 256, 0, s, d_pts, d_xr,
                                                             d_yr, d_perm_b, d_perm_c, (const int*)first, (const long long*)starts,
                                                             (const long long*)d_n_groups, n, d_bx, d_by, d_bz));
     IM_GUARD_CHECK(ctx, s, "im_dsm_group_mean");
@@ -351,27 +342,23 @@ extern "C" int im_dsm_rasterize(im_ctx* ctx, const float* d_bx, const float* d_b
     if (!cells) return 0;
     hipStream_t s = (hipStream_t)stream;
     const TriGrid g{d_bx, d_by, d_simplices, d_transform, n_simplices, d_xq, d_yq, nx, ny, x0, dx, y0, dy};
-    const long long T = n_simplices, nb = blocks_of(std::max(T, 1LL), SCAN_THREADS);
-    const size_t o_win = 0, o_offs = up256(cells * sizeof(int)), o_sums = o_offs + up256(std::max(T, 1LL) * sizeof(long long));
-    const size_t o_total = o_sums + up256(nb * sizeof(long long));
-    IM_GROW(ctx, ctx->grow(ctx->scratch.dsm, o_total + 256, "dsm.scratch"), -71, "im_dsm_rasterize: out of device memory (%lld cells)", cells);
-    char* const sc = ctx->scratch.dsm.as<char>();
-    int* win = reinterpret_cast<int*>(sc + o_win);
-    long long* offs = reinterpret_cast<long long*>(sc + o_offs);
-    long long* sums = reinterpret_cast<long long*>(sc + o_sums);
-    long long* total = reinterpret_cast<long long*>(sc + o_total);
+    const long long T = n_simplices;
+    const DsmRasterScratch lay(cells, T);
+    IM_GROW(ctx, ctx->grow(ctx->scratch.dsm, lay.bytes, "dsm.scratch"), -71, "im_dsm_rasterize: out of device memory (%lld cells)", cells);
+    void* const sc = ctx->scratch.dsm.p;
+    int* win = lay.win.at(sc);
+    long long* offs = lay.offs.at(sc);
+    long long* total = lay.total.at(sc);
     IM_HIP(ctx, hipMemsetAsync(win, 0x7f, cells * sizeof(int), s));
     if (T > 0) {
         const RowScan rs{g, offs};
-        IM_LAUNCH(ctx, "dsm_span_scan", s, launch_scan(rs, T, sums, total, s));
-        int dev_cus = 256;
-        hipDeviceGetAttribute(&dev_cus, hipDeviceAttributeMultiprocessorCount, ctx->device);
-        IM_LAUNCH(ctx, "dsm_raster", s, launch(dsm_raster_kernel, (dev_cus * 16), s, g,
-                                                            (const long long*)offs, (const long long*)total, win));
+        IM_LAUNCH(ctx, "dsm_span_scan", s, launch_scan(rs, T, lay.sums.at(sc), total, s));
+        int dev_cus = 0;
+        IM_HIP(ctx, device_cu_count(&dev_cus));
+        IM_LAUNCH(ctx, "dsm_raster", s, launch(dsm_raster_kernel, (dev_cus * 16), 256, 0, s, g, (const long long*)offs, (const long long*)total, win));
     }
     const double4 bounds = make_double4(h_bounds[0], h_bounds[1], h_bounds[2], h_bounds[3]);
-    IM_LAUNCH(ctx, "dsm_eval", s, launch(dsm_eval_kernel, blocks_of(cells, 256), s, g, d_bz,
-                                                      (const int*)win, bounds, fill, d_z));
+    IM_LAUNCH(ctx, "dsm_eval", s, launch(dsm_eval_kernel, blocks_of(cells, 256), 256, 0, s, g, d_bz, (const int*)win, bounds, fill, d_z));
     IM_GUARD_CHECK(ctx, s, "im_dsm_rasterize");
     return 0;
 }
@@ -398,7 +385,7 @@ extern "C" int im_project_colors(im_ctx* ctx, const double* d_x, long long sxr, 
     const long long n = (long long)rows * cols;
     if (!n) return 0;
     hipStream_t s = (hipStream_t)stream;
-    IM_LAUNCH(ctx, "proj_color", s, launch(proj_color_kernel, blocks_of(n, 256), s, a, p));
+    IM_LAUNCH(ctx, "proj_color", s, launch(proj_color_kernel, blocks_of(n, 256), 256, 0, s, a, p));
     IM_GUARD_CHECK(ctx, s, "im_project_colors");
     return 0;
 }

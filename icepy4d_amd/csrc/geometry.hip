@@ -246,23 +246,29 @@ __global__ __launch_bounds__(1024) void ransac_select_kernel(const float* __rest
         mask[i] = cbest > 0 && sampson_inlier(F, p0[2 * i], p0[2 * i + 1], p1[2 * i], p1[2 * i + 1], thr2) ? 1 : 0;
 }
 
+// a temporary of one call in the stream's order: hipMallocAsync here, hipFreeAsync when the call returns, whichever way it does
+template <typename T> struct StreamTemp {
+    T* p = nullptr; hipStream_t s;
+    explicit StreamTemp(hipStream_t stream) : s(stream) {}
+    StreamTemp(const StreamTemp&) = delete;      // one owner
+    ~StreamTemp() { if (p) hipFreeAsync(p, s); }
+    hipError_t alloc(size_t count) { return hipMallocAsync((void**)&p, sizeof(T) * count, s); }
+};
+
 static int ransac_entry(im_ctx* ctx, const char* who, int essential, const float* d_p0, const float* d_p1, int n, int n_hyp, double threshold,
                         unsigned int seed, double* d_F, uint8_t* d_mask, int32_t* d_info, void* stream) {
     IM_CHECK_CTX(ctx);
     if (n < 8 || n_hyp < 1) return ctx->fail(-70, "%s: needs >= 8 correspondences and >= 1 hypothesis", who);
     hipStream_t s = (hipStream_t)stream;
-    int* counts = nullptr;
-    double* Fs = nullptr;
-    IM_HIP(ctx, hipMallocAsync((void**)&counts, sizeof(int) * n_hyp, s));
-    IM_HIP(ctx, hipMallocAsync((void**)&Fs, sizeof(double) * 9 * n_hyp, s));
-    hipLaunchKernelGGL(ransac_hypotheses_kernel, dim3((n_hyp + 63) / 64), dim3(64), 0, s, d_p0, d_p1, n, n_hyp, seed,
-                       threshold * threshold, counts, Fs, essential);
-    hipLaunchKernelGGL(ransac_select_kernel, dim3(1), dim3(1024), 0, s, d_p0, d_p1, n, n_hyp, threshold * threshold, counts, Fs, d_F,
-                       d_mask, d_info);
-    hipError_t e = hipGetLastError();
-    hipFreeAsync(counts, s);
-    hipFreeAsync(Fs, s);
-    IM_HIP(ctx, e);
+    StreamTemp<int> counts(s);
+    StreamTemp<double> Fs(s);
+    IM_HIP(ctx, counts.alloc(n_hyp));
+    IM_HIP(ctx, Fs.alloc(9 * (size_t)n_hyp));
+    IM_LAUNCH(ctx, "ransac_hypotheses", s, launch(ransac_hypotheses_kernel, blocks_of(n_hyp, 64), 64, 0, s, d_p0, d_p1, n, n_hyp, seed,
+                                                  threshold * threshold, counts.p, Fs.p, essential));
+    IM_LAUNCH(ctx, "ransac_select", s, launch(ransac_select_kernel, 1, 1024, 0, s, d_p0, d_p1, n, n_hyp, threshold * threshold,
+                                              (const int*)counts.p, (const double*)Fs.p, d_F, d_mask, d_info));
+    IM_GUARD_CHECK(ctx, s, who);
     return 0;
 }
 
@@ -305,13 +311,15 @@ __device__ void smallest_right_singular_vector(double a[N][N], double out[N]) {
 // of its smallest singular value, normalised to X[3] = 1. (Until round 5 this kernel solved the four cross-product rows x (P X) = 0 instead:
 // the same point on exact correspondences, another least-squares problem on noisy ones - found when the outputs were first compared with the
 // reference's own, tests/golden/g10_triangulation.npz.)
-__global__ __launch_bounds__(64) void triangulate_linear_kernel(const double* __restrict__ P, const double* __restrict__ x0,
-                                                                const double* __restrict__ x1, int n, double* __restrict__ X) {
+struct ProjPair { double P[2][12]; };      // the two 3 x 4 projection matrices, row-major: a kernel argument
+
+__global__ __launch_bounds__(64) void triangulate_linear_kernel(ProjPair P, const double* __restrict__ x0, const double* __restrict__ x1, int n,
+                                                                double* __restrict__ X) {
     const int i = blockIdx.x * 64 + threadIdx.x;
     if (i >= n) return;
     double M[6][6];
     for (int v = 0; v < 2; ++v) {
-        const double* p = P + 12 * v;
+        const double* p = P.P[v];
         const double* x = (v == 0 ? x0 : x1) + 3 * (long)i;
         for (int r = 0; r < 3; ++r) {
             for (int j = 0; j < 4; ++j) M[3 * v + r][j] = p[4 * r + j];
@@ -345,15 +353,9 @@ extern "C" int im_triangulate_linear(im_ctx* ctx, const double* h_P0, const doub
     if (n == 0) return 0;                     // empty device tensors may hand over null pointers
     if (!d_x0 || !d_x1 || !d_X) return ctx->fail(-71, "im_triangulate_linear: null argument");
     hipStream_t s = (hipStream_t)stream;
-    double hP[24];
-    for (int j = 0; j < 12; ++j) { hP[j] = h_P0[j]; hP[12 + j] = h_P1[j]; }
-    double* dP = nullptr;
-    IM_HIP(ctx, hipMallocAsync((void**)&dP, sizeof(hP), s));
-    IM_HIP(ctx, hipMemcpyAsync(dP, hP, sizeof(hP), hipMemcpyHostToDevice, s));
-    IM_HIP(ctx, hipStreamSynchronize(s));     // hP lives on this stack frame
-    hipLaunchKernelGGL(triangulate_linear_kernel, dim3((n + 63) / 64), dim3(64), 0, s, dP, d_x0, d_x1, n, d_X);
-    hipError_t e = hipGetLastError();
-    hipFreeAsync(dP, s);
-    IM_HIP(ctx, e);
+    ProjPair P;
+    for (int j = 0; j < 12; ++j) { P.P[0][j] = h_P0[j]; P.P[1][j] = h_P1[j]; }
+    IM_LAUNCH(ctx, "triangulate_linear", s, launch(triangulate_linear_kernel, blocks_of(n, 64), 64, 0, s, P, d_x0, d_x1, n, d_X));
+    IM_GUARD_CHECK(ctx, s, "im_triangulate_linear");
     return 0;
 }

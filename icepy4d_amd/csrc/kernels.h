@@ -8,6 +8,7 @@
 #include <cstdlib>
 #include <vector>
 
+#include "carve.h"
 #include "common.h"
 
 namespace im {
@@ -60,6 +61,13 @@ template <auto Kernel, typename... Args>
 hipError_t launch_dyn_lds(dim3 grid, dim3 block, size_t lds_bytes, hipStream_t s, const Args&... args) {
     if (hipError_t e = optin_dyn_lds<Kernel>(lds_bytes); e != hipSuccess) return e;
     hipLaunchKernelGGL(Kernel, grid, block, lds_bytes, s, args...);
+    return hipGetLastError();
+}
+
+// launch(kernel, blocks, threads, lds_bytes, stream, kernel arguments...), launch error; `blocks` a count (1-D) or a dim3
+template <typename K, typename... Args>
+hipError_t launch(K kernel, dim3 blocks, int threads, size_t lds_bytes, hipStream_t s, Args... args) {
+    hipLaunchKernelGGL(kernel, blocks, dim3(threads), lds_bytes, s, args...);
     return hipGetLastError();
 }
 

@@ -23,6 +23,7 @@
 
 #include "common.h"
 #include "ctx.h"
+#include "stage_scratch.h"
 #include "knn_point.h"
 
 namespace im {
@@ -31,8 +32,6 @@ namespace {
 constexpr long long KNN_MAX_CELLS = 1LL << 24;
 constexpr int KNN_WAVES = 4;          // waves (queries) per block
 constexpr int KNN_MIN_STEPS = 1024;   // steps (64 rows looked up, or 64 candidates read) every ring search may take, whatever the cloud's size
-
-inline size_t up256(size_t b) { return (b + 255) & ~size_t(255); }
 
 __global__ __launch_bounds__(256) void knn_cells_kernel(KnnGrid g, const double* __restrict__ pts, long long n, long long* __restrict__ key) {
     const long long i = blockIdx.x * 256LL + threadIdx.x;
@@ -225,14 +224,7 @@ const char* bad_grid(const double* h_grid, int nx, int ny, int nz, KnnGrid& g) {
     return nullptr;
 }
 
-inline long long blocks_of(long long n, int per) { return (n + per - 1) / per; }
-
-template <typename K, typename... A>
-hipError_t launch(K kernel, long long blocks, hipStream_t s, A... args) {
-    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(256), 0, s, args...);
-    return hipGetLastError();
-}
-static_assert(IM_WAVE * KNN_WAVES == 256, "launch() starts blocks of 256 threads");
+static_assert(IM_WAVE * KNN_WAVES == 256, "knn_self_kernel takes the block of the file's other kernels: 256 threads");
 
 }  // namespace
 }  // namespace im
@@ -251,7 +243,7 @@ int im_knn_cells(im_ctx* ctx, const double* d_pts, long long n, const double* h_
     if (const char* why = bad_grid(h_grid, nx, ny, nz, g)) return ctx->fail(-75, "im_knn_cells: %s", why);
     if (n == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
-    IM_LAUNCH(ctx, "knn_cells", s, launch(knn_cells_kernel, blocks_of(n, 256), s, g, d_pts, n, d_key));
+    IM_LAUNCH(ctx, "knn_cells", s, launch(knn_cells_kernel, blocks_of(n, 256), 256, 0, s, g, d_pts, n, d_key));
     IM_GUARD_CHECK(ctx, s, "im_knn_cells");
     return 0;
 }
@@ -263,7 +255,7 @@ int im_knn_cell_ranges(im_ctx* ctx, const long long* d_sorted_keys, long long n,
     if (cells < 1 || cells > KNN_MAX_CELLS) return ctx->fail(-75, "im_knn_cell_ranges: cells must be 1..im_knn_max_cells()");
     if (n == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
-    IM_LAUNCH(ctx, "knn_ranges", s, launch(knn_ranges_kernel, blocks_of(cells + 1, 256), s, d_sorted_keys, n, cells, d_start));
+    IM_LAUNCH(ctx, "knn_ranges", s, launch(knn_ranges_kernel, blocks_of(cells + 1, 256), 256, 0, s, d_sorted_keys, n, cells, d_start));
     IM_GUARD_CHECK(ctx, s, "im_knn_cell_ranges");
     return 0;
 }
@@ -279,15 +271,15 @@ int im_knn_self(im_ctx* ctx, const double* d_pts, const long long* d_perm, const
     if (const char* why = bad_grid(h_grid, nx, ny, nz, a.g)) return ctx->fail(-75, "im_knn_self: %s", why);
     if (!(radius2 >= 0.0)) return ctx->fail(-75, "im_knn_self: radius2 must be >= 0 (+inf: no radius)");
     if (n == 0) return 0;
-    const size_t plane = up256((size_t)n * sizeof(double));
-    IM_GROW(ctx, ctx->grow(ctx->scratch.knn, 3 * plane + up256((size_t)n * sizeof(int)), "knn_sorted"), -22, "im_knn_self: allocation failed");
-    char* base = ctx->scratch.knn.as<char>();
-    a.s.x = (double*)base; a.s.y = (double*)(base + plane); a.s.z = (double*)(base + 2 * plane); a.s.idx = (int*)(base + 3 * plane);
+    const KnnSortedScratch lay(n);
+    IM_GROW(ctx, ctx->grow(ctx->scratch.knn, lay.bytes, "knn_sorted"), -22, "im_knn_self: allocation failed");
+    void* const base = ctx->scratch.knn.p;
+    a.s.x = lay.x.at(base); a.s.y = lay.y.at(base); a.s.z = lay.z.at(base); a.s.idx = lay.idx.at(base);
     a.pts = d_pts; a.start = d_start; a.n = (int)n; a.k = k; a.radius2 = radius2;
     a.count = d_count; a.idx = d_idx; a.d2 = d_d2; a.mean = d_mean; a.normal = d_normal; a.rings = d_rings;
     hipStream_t s = (hipStream_t)stream;
-    IM_LAUNCH(ctx, "knn_gather", s, launch(knn_gather_kernel, blocks_of(n, 256), s, d_pts, d_perm, n, a.s));
-    IM_LAUNCH(ctx, "knn_self", s, launch(knn_self_kernel, blocks_of(n, KNN_WAVES), s, a));
+    IM_LAUNCH(ctx, "knn_gather", s, launch(knn_gather_kernel, blocks_of(n, 256), 256, 0, s, d_pts, d_perm, n, a.s));
+    IM_LAUNCH(ctx, "knn_self", s, launch(knn_self_kernel, blocks_of(n, KNN_WAVES), IM_WAVE * KNN_WAVES, 0, s, a));
     IM_GUARD_CHECK(ctx, s, "im_knn_self");
     return 0;
 }

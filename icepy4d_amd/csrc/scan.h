@@ -3,10 +3,9 @@
 //   __device__ long long count(long long j) const;          the count of item j (0 beyond the end)
 //   __device__ void write(long long j, long long pos) const; receives the exclusive prefix of item j
 // launch_scan runs three kernels: block sums, one block over them, block-local scan + write. Integer sums only: the result does not depend
-// on the order of execution. Include inside `namespace im { namespace {` of the translation unit that instantiates the kernels.
+// on the order of execution. Include inside `namespace im { namespace {` of the translation unit that instantiates the kernels, behind
+// ctx.h and stage_scratch.h (SCAN_THREADS, and carve.h's blocks_of).
 #pragma once
-
-constexpr int SCAN_THREADS = 256;
 
 __device__ __forceinline__ long long block_excl_scan(long long v, long long& total) {
     __shared__ long long ws[SCAN_THREADS / IM_WAVE];
@@ -56,9 +55,6 @@ __global__ __launch_bounds__(SCAN_THREADS) void scan_write_kernel(S s, const lon
     const long long e = block_excl_scan(s.count(j), tot);
     s.write(j, sums[blockIdx.x] + e);
 }
-
-inline long long blocks_of(long long n, int t) { return (n + t - 1) / t; }
-inline size_t up256(size_t b) { return (b + 255) & ~size_t(255); }
 
 // sums: [max(1, blocks_of(n, SCAN_THREADS))] scratch; *total receives the sum of all counts
 template <typename S>

@@ -155,14 +155,6 @@ __global__ __launch_bounds__(SFM_THREADS) void triangulate_table_kernel(const in
     }
 }
 
-long long blocks_of(long long n) { return (n + SFM_THREADS - 1) / SFM_THREADS; }
-
-template <typename K, typename... A>
-hipError_t launch(K kernel, long long blocks, size_t lds_bytes, hipStream_t s, A... args) {
-    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(SFM_THREADS), lds_bytes, s, args...);
-    return hipGetLastError();
-}
-
 void fill_cam(CamParam& c, const double* h_P, const double* h_cam) {
     for (int j = 0; j < 12; ++j) c.P[j] = h_P ? h_P[j] : 0.0;
     for (int j = 0; j < 4; ++j) c.in[j] = h_cam ? h_cam[j] : 1.0;
@@ -185,7 +177,7 @@ extern "C" int im_undistort_points(im_ctx* ctx, const float* d_pts, long long n,
     CamParam c;
     fill_cam(c, nullptr, h_cam);
     hipStream_t s = (hipStream_t)stream;
-    IM_LAUNCH(ctx, "undistort_points", s, launch(undistort_points_kernel, blocks_of(n), 0, s, d_pts, n, c, d_out));
+    IM_LAUNCH(ctx, "undistort_points", s, launch(undistort_points_kernel, blocks_of(n, SFM_THREADS), SFM_THREADS, 0, s, d_pts, n, c, d_out));
     IM_GUARD_CHECK(ctx, s, "im_undistort_points");
     return 0;
 }
@@ -208,11 +200,11 @@ extern "C" int im_triangulate_iterative(im_ctx* ctx, const void* d_u1, const voi
     fill_cam(c.c[1], h_P2, h_cam2);
     hipStream_t s = (hipStream_t)stream;
     if (f64) {
-        IM_LAUNCH(ctx, "triangulate_iterative", s, launch(triangulate_iterative_kernel<double>, blocks_of(n), 0, s, (const double*)d_u1,
+        IM_LAUNCH(ctx, "triangulate_iterative", s, launch(triangulate_iterative_kernel<double>, blocks_of(n, SFM_THREADS), SFM_THREADS, 0, s, (const double*)d_u1,
                                                           (const double*)d_u2, n, c, 0, tolerance, max_solves, d_X, d_status,
                                                           (float*)nullptr, (float*)nullptr));
     } else {
-        IM_LAUNCH(ctx, "triangulate_iterative", s, launch(triangulate_iterative_kernel<float>, blocks_of(n), 0, s, (const float*)d_u1,
+        IM_LAUNCH(ctx, "triangulate_iterative", s, launch(triangulate_iterative_kernel<float>, blocks_of(n, SFM_THREADS), SFM_THREADS, 0, s, (const float*)d_u1,
                                                           (const float*)d_u2, n, c, undistort ? 1 : 0, tolerance, max_solves, d_X, d_status,
                                                           d_und1, d_und2));
     }
@@ -233,7 +225,7 @@ extern "C" int im_triangulate_table(im_ctx* ctx, const int32_t* d_table, int n_r
     if (m_cap && (!d_X || !d_status)) return ctx->fail(-73, "im_triangulate_table: null output");
     hipStream_t s = (hipStream_t)stream;
     const long long W = 8 + 6LL * max_kpts;
-    IM_LAUNCH(ctx, "table_offsets", s, launch(table_offsets_kernel, 1, 0, s, d_table, n_records, W, d_offsets));
+    IM_LAUNCH(ctx, "table_offsets", s, launch(table_offsets_kernel, 1, SFM_THREADS, 0, s, d_table, n_records, W, d_offsets));
     if (n_records && m_cap) {
         // K ints of dynamic LDS next to the 16 static bytes of wave_cnt: above 64 KB from K = 16381 on, hence the opt-in (kernels.h)
         IM_LAUNCH(ctx, "triangulate_table", s, launch_dyn_lds<triangulate_table_kernel>(

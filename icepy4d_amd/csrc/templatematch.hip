@@ -294,7 +294,7 @@ __global__ __launch_bounds__(256) void tm_peak_kernel(const double* __restrict__
 }
 
 hipError_t launch_forient(const void* img, int dtype, int n, int h, int w, float* out, hipStream_t s) {
-    hipLaunchKernelGGL(forient_kernel, dim3((w + 255) / 256, n, h), dim3(256), 0, s, img, dtype, h, w, reinterpret_cast<float2*>(out));
+    hipLaunchKernelGGL(forient_kernel, dim3((unsigned)blocks_of(w, 256), n, h), dim3(256), 0, s, img, dtype, h, w, reinterpret_cast<float2*>(out));
     return hipGetLastError();
 }
 
@@ -307,7 +307,7 @@ hipError_t launch_corr(const TmPlan& p, long blocks, const float2* A, int ha, in
 
 hipError_t launch_peak(const double* pairs, const int32_t* bidx, int n_b, long pair0, long nb, int T, int S, int ha, int wa, int hb, int wb,
                        const float* C, long n_pairs, double* out, hipStream_t s) {
-    hipLaunchKernelGGL(tm_peak_kernel, dim3((unsigned)((nb + 3) / 4)), dim3(256), 0, s, pairs, bidx, n_b, pair0, nb, T, S, ha, wa, hb, wb, C,
+    hipLaunchKernelGGL(tm_peak_kernel, dim3((unsigned)blocks_of(nb, 4)), dim3(256), 0, s, pairs, bidx, n_b, pair0, nb, T, S, ha, wa, hb, wb, C,
                        n_pairs, out);
     return hipGetLastError();
 }

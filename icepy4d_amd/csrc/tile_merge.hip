@@ -142,9 +142,9 @@ int im_merge_tile_matches(im_ctx* ctx, int n_pairs, int max_kpts, const int32_t*
     hipStream_t s = (hipStream_t)stream;
     const float4 org = make_float4(h_origin[0], h_origin[1], h_origin[2], h_origin[3]);
     IM_HIP(ctx, launch_zero_words(count, 4, s));
-    hipLaunchKernelGGL(tm_collect_kernel, dim3((max_kpts + 255) / 256, n_pairs), dim3(256), 0, s, max_kpts, d_matches, d_slots, d_off, org,
+    hipLaunchKernelGGL(tm_collect_kernel, dim3((unsigned)blocks_of(max_kpts, 256), n_pairs), dim3(256), 0, s, max_kpts, d_matches, d_slots, d_off, org,
                        d_kp_bank, d_n_bank, key, seq, count);
-    const unsigned nb = (unsigned)((cap + RK_T - 1) / RK_T);
+    const unsigned nb = (unsigned)blocks_of(cap, RK_T);
     hipLaunchKernelGGL(tm_first_kernel, dim3(nb), dim3(RK_N), 0, s, key, seq, count, skey);
     hipLaunchKernelGGL(tm_rank_kernel, dim3(nb), dim3(RK_N), 0, s, skey, seq, count, max_kpts, d_matches, d_slots, d_off, org, d_kp_bank,
                        d_idx0, d_idx1, d_kp0, d_kp1);
@@ -160,7 +160,7 @@ int im_gather_rows(im_ctx* ctx, const float* d_src, int row_floats, const int32_
     if (row_floats < 1 || !d_src || !d_idx || !d_dst) return ctx->fail(-72, "im_gather_rows: bad arguments");
     const int lanes = row_floats >= 256 ? 64 : (row_floats >= 4 ? (row_floats / 4 > 0 ? row_floats / 4 : 1) : 1);
     const int per_block = 256 / lanes;
-    hipLaunchKernelGGL(gather_rows_generic_kernel, dim3((n + per_block - 1) / per_block), dim3(256), 0, (hipStream_t)stream, d_src, row_floats, d_idx,
+    hipLaunchKernelGGL(gather_rows_generic_kernel, dim3((unsigned)blocks_of(n, per_block)), dim3(256), 0, (hipStream_t)stream, d_src, row_floats, d_idx,
                        n, d_dst);
     IM_HIP(ctx, hipGetLastError());
     return 0;

@@ -53,6 +53,9 @@ static const char* bad_images(const void* d_src, const void* d_dst, int n_images
     return nullptr;
 }
 
+// the instantiation for `channels` (1..4, checked by bad_images) out of the four: the one place that switches on the channel count
+template <typename K> K by_channels(int channels, K k1, K k2, K k3, K k4) { return channels == 1 ? k1 : channels == 2 ? k2 : channels == 3 ? k3 : k4; }
+
 }  // namespace im
 
 using namespace im;
@@ -68,15 +71,11 @@ int im_undistort_image(im_ctx* ctx, const uint8_t* d_src, int n_images, int h, i
     for (int i = 0; i < 9; ++i) cam.ir[i] = h_cam[i];
     for (int i = 0; i < 4; ++i) cam.in[i] = h_cam[9 + i];
     for (int i = 0; i < 8; ++i) cam.k[i] = h_cam[13 + i];
-    const dim3 grid((w + 255) / 256, h, n_images), block(256);
+    const dim3 grid((unsigned)blocks_of(w, 256), h, n_images);
     hipStream_t s = (hipStream_t)stream;
-    switch (channels) {
-        case 1: hipLaunchKernelGGL(undistort_image_kernel<1>, grid, block, 0, s, d_src, d_dst, cam, h, w); break;
-        case 2: hipLaunchKernelGGL(undistort_image_kernel<2>, grid, block, 0, s, d_src, d_dst, cam, h, w); break;
-        case 3: hipLaunchKernelGGL(undistort_image_kernel<3>, grid, block, 0, s, d_src, d_dst, cam, h, w); break;
-        default: hipLaunchKernelGGL(undistort_image_kernel<4>, grid, block, 0, s, d_src, d_dst, cam, h, w); break;
-    }
-    IM_HIP(ctx, hipGetLastError());
+    const auto kernel = by_channels(channels, undistort_image_kernel<1>, undistort_image_kernel<2>, undistort_image_kernel<3>, undistort_image_kernel<4>);
+    IM_LAUNCH(ctx, "undistort_image", s, launch(kernel, grid, 256, 0, s, d_src, d_dst, cam, h, w));
+    IM_GUARD_CHECK(ctx, s, "im_undistort_image");
     return 0;
 }
 
@@ -85,15 +84,11 @@ int im_warp_perspective(im_ctx* ctx, const uint8_t* d_src, int n_images, int h, 
     IM_CHECK_CTX(ctx);
     if (!d_minv) return ctx->fail(-74, "im_warp_perspective: null matrices");
     if (const char* why = bad_images(d_src, d_dst, n_images, h, w, channels, oh, ow)) return ctx->fail(-74, "im_warp_perspective: %s", why);
-    const dim3 grid((ow + 255) / 256, oh, n_images), block(256);
+    const dim3 grid((unsigned)blocks_of(ow, 256), oh, n_images);
     hipStream_t s = (hipStream_t)stream;
-    switch (channels) {
-        case 1: hipLaunchKernelGGL(warp_perspective_kernel<1>, grid, block, 0, s, d_src, d_dst, d_minv, h, w, oh, ow); break;
-        case 2: hipLaunchKernelGGL(warp_perspective_kernel<2>, grid, block, 0, s, d_src, d_dst, d_minv, h, w, oh, ow); break;
-        case 3: hipLaunchKernelGGL(warp_perspective_kernel<3>, grid, block, 0, s, d_src, d_dst, d_minv, h, w, oh, ow); break;
-        default: hipLaunchKernelGGL(warp_perspective_kernel<4>, grid, block, 0, s, d_src, d_dst, d_minv, h, w, oh, ow); break;
-    }
-    IM_HIP(ctx, hipGetLastError());
+    const auto kernel = by_channels(channels, warp_perspective_kernel<1>, warp_perspective_kernel<2>, warp_perspective_kernel<3>, warp_perspective_kernel<4>);
+    IM_LAUNCH(ctx, "warp_perspective", s, launch(kernel, grid, 256, 0, s, d_src, d_dst, d_minv, h, w, oh, ow));
+    IM_GUARD_CHECK(ctx, s, "im_warp_perspective");
     return 0;
 }
 

@@ -252,3 +252,43 @@ class Engine:
 
     def close(self):
         self.ctx.close()
+
+
+_ENGINES: Dict[int, list] = {}
+
+
+def get_engine(device: int = 0, state_dicts: Optional[Dict[str, dict]] = None, private: bool = False) -> Engine:
+    """An engine (context + device weights + workspace) on `device` whose weights are, or can become, exactly
+    `state_dicts` ({model: state dict}). Matcher objects with EQUAL weights share one engine (the reference builds a fresh
+    matcher per epoch, `main_dev.py:115-132`: here that costs one fingerprint, no upload, and the captured HIP graph stays
+    valid); a matcher with different weights gets a context of its own, so no object ever runs with another object's weights
+    or replays a graph that points at freed weight buffers."""
+    fps = {m: state_dict_fingerprint(sd) for m, sd in (state_dicts or {}).items()}
+    pool = _ENGINES.setdefault(device, [])
+    for eng in ([] if private else pool):
+        if all(eng.holds(m, fp) for m, fp in fps.items()):
+            break
+    else:
+        eng = Engine(device)
+        if not private:     # opt["private_engine"]: a context (weights + workspace) no other matcher object will ever use
+            pool.append(eng)
+    for m, sd in (state_dicts or {}).items():
+        eng.load_state_dict(m, sd)
+    return eng
+
+
+def default_engine(engine: Optional[Engine]) -> Engine:
+    """The engine a stage function runs on: the caller's, or the shared one of device 0. No host fallback."""
+    return engine if engine is not None else get_engine(0)
+
+
+def host_array(array, dtype=None) -> np.ndarray:
+    """The host half of `to_device`: `array` as a C-contiguous numpy array (of `dtype` when given) that torch may wrap - a read-only
+    array (a memory map, a broadcast view, `np.frombuffer`) is copied, since `torch.from_numpy` warns about memory it could write through."""
+    a = np.ascontiguousarray(array, dtype=dtype)
+    return a if a.flags.writeable else a.copy()
+
+
+def to_device(array, device, dtype=None) -> torch.Tensor:
+    """Uploads a numpy array (or anything numpy can wrap) to `device`, C-contiguous, converted to `dtype` when given."""
+    return torch.from_numpy(host_array(array, dtype)).to(device)

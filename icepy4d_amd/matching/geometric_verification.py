@@ -23,7 +23,10 @@ import logging
 from typing import Tuple
 
 import numpy as np
+import torch
 
+from .._lib import ptr
+from ..engine import to_device
 from .enums import GeometricVerification
 
 logger = logging.getLogger(__name__)
@@ -255,11 +258,8 @@ def _finish(p0, p1, best_mask, thr2, method, n, degeneracy_check=True, seed=0):
 
 def _ransac_on_device(engine, mkpts0: np.ndarray, mkpts1: np.ndarray, threshold: float, n_hyp: int, seed: int) -> np.ndarray:
     """All hypotheses in one launch pair (`im_ransac_fundamental`); returns the inlier mask of the best one."""
-    import torch
-    from .._lib import ptr
     dev = engine.device
-    d0 = torch.from_numpy(np.ascontiguousarray(mkpts0, dtype=np.float32)).to(dev)
-    d1 = torch.from_numpy(np.ascontiguousarray(mkpts1, dtype=np.float32)).to(dev)
+    d0, d1 = to_device(mkpts0, dev, np.float32), to_device(mkpts1, dev, np.float32)
     n = d0.shape[0]
     dF = torch.empty(9, dtype=torch.float64, device=dev)
     dmask = torch.empty(n, dtype=torch.uint8, device=dev)

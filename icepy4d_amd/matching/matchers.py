@@ -29,12 +29,13 @@ from copy import deepcopy
 from dataclasses import dataclass
 from itertools import product
 from pathlib import Path
-from typing import Dict, List, Optional, Tuple, Union
+from typing import Dict, List, Tuple, Union
 
 import numpy as np
 import torch
 
 from .._lib import IcematchError
+from ..engine import get_engine      # re-exported: matchers.get_engine is where user code finds it
 from ..utils import AverageTimer, timeit
 from .enums import GeometricVerification, Quality, TileSelection
 from .geometric_verification import geometric_verification
@@ -44,29 +45,6 @@ from .tiling import Tiler
 logger = logging.getLogger(__name__)
 
 MIN_MATCHES_PER_TILE = 5
-
-_ENGINES: Dict[int, list] = {}
-
-
-def get_engine(device: int = 0, state_dicts: Optional[Dict[str, dict]] = None, private: bool = False):
-    """An engine (context + device weights + workspace) on `device` whose weights are, or can become, exactly
-    `state_dicts` ({model: state dict}). Matcher objects with EQUAL weights share one engine (the reference builds a fresh
-    matcher per epoch, `main_dev.py:115-132`: here that costs one fingerprint, no upload, and the captured HIP graph stays
-    valid); a matcher with different weights gets a context of its own, so no object ever runs with another object's weights
-    or replays a graph that points at freed weight buffers."""
-    from ..engine import Engine, state_dict_fingerprint
-    fps = {m: state_dict_fingerprint(sd) for m, sd in (state_dicts or {}).items()}
-    pool = _ENGINES.setdefault(device, [])
-    for eng in ([] if private else pool):
-        if all(eng.holds(m, fp) for m, fp in fps.items()):
-            break
-    else:
-        eng = Engine(device)
-        if not private:     # opt["private_engine"]: a context (weights + workspace) no other matcher object will ever use
-            pool.append(eng)
-    for m, sd in (state_dicts or {}).items():
-        eng.load_state_dict(m, sd)
-    return eng
 
 
 def _on_engine_device(method):

@@ -5,6 +5,7 @@ import numpy as np
 import torch
 
 from .. import _lib
+from ..engine import to_device
 
 
 def _levels(engine, image: np.ndarray, levels: int, device_image=None) -> np.ndarray:
@@ -16,7 +17,7 @@ def _levels(engine, image: np.ndarray, levels: int, device_image=None) -> np.nda
     c = 1 if image.ndim == 2 else image.shape[2]
     h, w = image.shape[:2]
     with torch.cuda.device(engine.device):
-        cur = device_image if device_image is not None else torch.from_numpy(np.ascontiguousarray(image)).to(engine.device)
+        cur = device_image if device_image is not None else to_device(image, engine.device)
         assert cur.dtype == torch.uint8 and cur.is_contiguous() and tuple(cur.shape[:2]) == (h, w), "pyramid: device image of another shape"
         for _ in range(abs(levels)):
             if levels > 0:

@@ -10,6 +10,10 @@ complex64 FFTs, so peak / mean correlations agree to ~1e-7 T^2 and du / dv to ~1
 from typing import List, Tuple
 
 import numpy as np
+import torch
+
+from .._lib import ptr
+from ..engine import default_engine, to_device
 
 
 class MatchResult:
@@ -22,13 +26,6 @@ class MatchResult:
         self.meanAbsCorr = meanAbsCorr
         self.snr = peakCorr / meanAbsCorr
         self.method = method
-
-
-def _engine(engine):
-    if engine is not None:
-        return engine
-    from .matchers import get_engine
-    return get_engine(0)
 
 
 def _image_dtype(img: np.ndarray) -> Tuple[np.ndarray, int]:
@@ -47,8 +44,6 @@ def _is_complex_map(x) -> bool:
 def _device_maps(eng, images: List[np.ndarray], as_maps: bool):
     """[n][h][w] complex64 maps on the device of equally shaped images: orientation maps of real images through ONE im_forient
     launch, or (as_maps) the inputs themselves as complex64."""
-    import torch
-    from .._lib import ptr
     h, w = images[0].shape
     out = torch.empty((len(images), h, w, 2), dtype=torch.float32, device=eng.device)
     if as_maps:
@@ -60,7 +55,7 @@ def _device_maps(eng, images: List[np.ndarray], as_maps: bool):
     conv = [_image_dtype(np.real(im)) for im in images]
     dtype = 0 if all(d == 0 for _, d in conv) else 1
     host = np.stack([c if dtype == 0 else c.astype(np.float32) for c, _ in conv])
-    d_img = torch.from_numpy(host).to(eng.device)
+    d_img = to_device(host, eng.device)
     eng.ctx.call("im_forient", ptr(d_img), dtype, len(images), h, w, ptr(out), eng.stream_ptr())
     return out
 
@@ -69,8 +64,6 @@ def match_many(A, Bs: List[np.ndarray], pu, pv, TemplateWidth: int = 128, Search
                engine=None):
     """`OC(A, B, pu, pv, ...)` for every B of `Bs` (equal shapes), all (point, B) pairs in one correlation launch. pu / pv are not
     modified. Returns a dict of arrays [len(Bs)][*pu.shape]: pu, pv, du, dv, peakCorr, meanAbsCorr."""
-    import torch
-    from .._lib import ptr
     T, S = int(TemplateWidth), int(SearchWidth)
     if not 1 <= T < S:
         raise ValueError(f"template width {T} must be at least 1 and smaller than search width {S}")
@@ -84,7 +77,7 @@ def match_many(A, Bs: List[np.ndarray], pu, pv, TemplateWidth: int = 128, Search
     pv = np.broadcast_to(np.asarray(pv, dtype=np.float64), pu.shape)
     idu = np.zeros(pu.shape) + Initialdu
     idv = np.zeros(pu.shape) + Initialdv
-    eng = _engine(engine)
+    eng = default_engine(engine)
     as_maps = _is_complex_map(A)
     dA, dB = _device_maps(eng, [A], as_maps), _device_maps(eng, Bs, as_maps)
     # `B = np.conj(B)` when B holds a complex value (`:217-218`); an orientation map that is entirely real has Bi = 0, so the sign
@@ -92,10 +85,8 @@ def match_many(A, Bs: List[np.ndarray], pu, pv, TemplateWidth: int = 128, Search
     conj_b = 1 if not as_maps else int(any(_is_complex_map(b) for b in Bs))
     n_pts, n_b = pu.size, len(Bs)
     pts = np.stack([pu.ravel(), pv.ravel(), idu.ravel(), idv.ravel()], 1)
-    pairs = np.ascontiguousarray(np.tile(pts, (n_b, 1)))
-    bidx = np.repeat(np.arange(n_b, dtype=np.int32), n_pts)
-    d_pairs = torch.from_numpy(pairs).to(eng.device)
-    d_bidx = torch.from_numpy(bidx).to(eng.device)
+    d_pairs = to_device(np.tile(pts, (n_b, 1)), eng.device)
+    d_bidx = to_device(np.repeat(np.arange(n_b, dtype=np.int32), n_pts), eng.device)
     n = n_pts * n_b
     d_out = torch.empty((6, max(n, 1)), dtype=torch.float64, device=eng.device)
     ha, wa = A.shape
@@ -130,7 +121,7 @@ def forient(img, engine=None) -> np.ndarray:
     img = np.asarray(img)
     if img.ndim != 2:
         raise ValueError("forient expects a 2-D image")
-    eng = _engine(engine)
+    eng = default_engine(engine)
     if not img.size:
         return np.zeros(img.shape, np.complex64)
     return np.ascontiguousarray(_device_maps(eng, [img], False)[0].cpu().numpy()).view(np.complex64)[..., 0]

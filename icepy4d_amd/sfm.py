@@ -14,7 +14,11 @@ import logging
 from typing import NamedTuple, Optional, Tuple
 
 import numpy as np
+import torch
 
+from .core.camera import _camera_params, _channel_map
+from ._lib import ptr
+from .engine import default_engine, to_device
 from .matching.enums import GeometricVerification
 from .matching.geometric_verification import geometric_verification
 
@@ -55,11 +59,8 @@ def triangulate_points_linear(P1, P2, x1, x2, engine=None) -> np.ndarray:
         raise ValueError("Number of points don't match.")
     P1, P2 = np.asarray(P1, np.float64), np.asarray(P2, np.float64)
     if engine is not None:
-        import torch
-        from ._lib import ptr
         n = len(x1)
-        d1 = torch.from_numpy(np.ascontiguousarray(x1)).to(engine.device)
-        d2 = torch.from_numpy(np.ascontiguousarray(x2)).to(engine.device)
+        d1, d2 = to_device(x1, engine.device), to_device(x2, engine.device)
         dX = torch.empty((n, 4), dtype=torch.float64, device=engine.device)
         p1, p2 = np.ascontiguousarray(P1.reshape(12)), np.ascontiguousarray(P2.reshape(12))
         engine.ctx.call("im_triangulate_linear", p1.ctypes.data, p2.ctypes.data, ptr(d1), ptr(d2), n, ptr(dX), engine.stream_ptr())
@@ -172,12 +173,9 @@ def _essential_ransac_on_device(engine, x0: np.ndarray, x1: np.ndarray, threshol
     """RANSAC over essential-matrix hypotheses generated and scored on the device (`im_ransac_essential`), in batches of 1024
     until the confidence criterion holds for the best inlier ratio; then one refit on the inliers of the winner (8-point on all
     of them, projected onto the essential manifold) that is kept if it does not lose inliers. Returns (E, inlier mask)."""
-    import torch
-    from ._lib import ptr
     from .matching.geometric_verification import DEVICE_BATCH, _eight_point, _needed, _sampson
     dev = engine.device
-    d0 = torch.from_numpy(np.ascontiguousarray(x0, dtype=np.float32)).to(dev)
-    d1 = torch.from_numpy(np.ascontiguousarray(x1, dtype=np.float32)).to(dev)
+    d0, d1 = to_device(x0, dev, np.float32), to_device(x1, dev, np.float32)
     n = len(x0)
     dE = torch.empty(9, dtype=torch.float64, device=dev)
     dmask = torch.empty(n, dtype=torch.uint8, device=dev)
@@ -263,39 +261,6 @@ def estimate_pose(kpts0: np.ndarray, kpts1: np.ndarray, K0: np.ndarray, K1: np.n
 
 
 # ---- projection and point colours (`sfm/geometry.py:79-100`, `sfm/interpolate_colors.py:13-92`): csrc/dsm.hip `im_project_colors`
-def _engine(engine):
-    if engine is not None:
-        return engine
-    from .matching.matchers import get_engine
-    return get_engine(0)
-
-
-def _camera_params(camera) -> np.ndarray:
-    """[28] float64 for `im_project_colors`: fx, fy, cx, cy, R (row-major), t, k1 k2 p1 p2 k3 k4 k5 k6 s1..s4. Reads only `.K`, `.dist`,
-    `.R` and `.t`, as the reference does. Distortion vectors of length 0, 4, 5 or 8 (OpenCV's forms without thin prism / tilt terms)."""
-    K = np.asarray(camera.K, np.float64).reshape(3, 3)
-    R = np.asarray(camera.R, np.float64).reshape(9)
-    t = np.asarray(camera.t, np.float64).reshape(3)
-    dist = np.zeros(0) if camera.dist is None else np.asarray(camera.dist, np.float64).ravel()
-    if len(dist) not in (0, 4, 5, 8):
-        raise ValueError(f"project_points: distortion vectors of length 0, 4, 5 or 8 are supported (got {len(dist)})")
-    k = np.zeros(12)
-    k[:len(dist)] = dist
-    return np.ascontiguousarray(np.concatenate([[K[0, 0], K[1, 1], K[0, 2], K[1, 2]], R, t, k]))
-
-
-def _channel_map(image: np.ndarray, convert_BRG2RGB: bool) -> np.ndarray:
-    """Output channel -> image channel: cv2.cvtColor(BGR2RGB) keeps B, G, R reversed (and drops a fourth channel)."""
-    c = image.shape[2]
-    if convert_BRG2RGB:
-        if c not in (3, 4):
-            raise ValueError(f"interpolate_point_colors: BGR to RGB needs a 3- or 4-channel image (got {c})")
-        return np.array([2, 1, 0], np.int32)
-    if not 1 <= c <= 4:
-        raise ValueError(f"interpolate_point_colors: 1 to 4 channels are supported (got {c})")
-    return np.arange(c, dtype=np.int32)
-
-
 def _points(points3d) -> np.ndarray:
     p = np.ascontiguousarray(points3d, dtype=np.float64)
     if p.ndim != 2 or p.shape[1] != 3:
@@ -304,16 +269,13 @@ def _points(points3d) -> np.ndarray:
 
 
 def _project_colors(engine, points: np.ndarray, cam: np.ndarray, image=None, chmap=None, want_proj=True):
-    import torch
-    proj, col = _project_colors_device(engine, torch.from_numpy(points).to(engine.device), cam, image, chmap, want_proj)
+    proj, col = _project_colors_device(engine, to_device(points, engine.device), cam, image, chmap, want_proj)
     return (None if proj is None else proj.cpu().numpy()), (None if col is None else col.cpu().numpy())
 
 
 def _project_colors_device(engine, dp, cam: np.ndarray, image=None, chmap=None, want_proj=True):
     """`im_project_colors` on [n, 3] float64 points that are on the device already (`Triangulate`, `triangulate_table`: the points never
     visit the host between the triangulation and the colouring); `image` a host uint8 array or a device tensor. Device tensors out."""
-    import torch
-    from ._lib import ptr
     dev = engine.device
     n = len(dp)
     proj = torch.empty((n, 2), dtype=torch.float32, device=dev) if want_proj else None
@@ -322,7 +284,7 @@ def _project_colors_device(engine, dp, cam: np.ndarray, image=None, chmap=None, 
     if image is not None:
         h, w, cin = image.shape
         cout = len(chmap)
-        img = image if torch.is_tensor(image) else torch.from_numpy(np.ascontiguousarray(image)).to(dev)
+        img = image if torch.is_tensor(image) else to_device(image, dev)
         col = torch.empty((n, cout), dtype=torch.float64, device=dev)
     base = ptr(dp)
     engine.ctx.call("im_project_colors", base, 0, 3, base + 8, 0, 3, base + 16, 0, 3, 1 if n else 0, n, 0, cam.ctypes.data,
@@ -336,7 +298,7 @@ def project_points(points3d, camera, engine=None) -> np.ndarray:
     k1 k2 p1 p2 [k3 [k4 k5 k6]] rational distortion, fx x + cx) and cast to float32. R is used as given (no Rodrigues round trip)."""
     cam = _camera_params(camera)
     p = _points(points3d)
-    return _project_colors(_engine(engine), p, cam)[0]
+    return _project_colors(default_engine(engine), p, cam)[0]
 
 
 def interpolate_point_colors(points3d, image, camera, convert_BRG2RGB=True, engine=None) -> np.ndarray:
@@ -350,11 +312,11 @@ def interpolate_point_colors(points3d, image, camera, convert_BRG2RGB=True, engi
     chmap = _channel_map(image, convert_BRG2RGB)
     cam = _camera_params(camera)
     p = _points(points3d)
-    return _project_colors(_engine(engine), p, cam, image, chmap, want_proj=False)[1]
+    return _project_colors(default_engine(engine), p, cam, image, chmap, want_proj=False)[1]
 
 
 # ---- undistortion and least-squares triangulation of matched points (`sfm/geometry.py:103-118`, `thirdparty/triangulation.py:10-177`,
-# `sfm/triangulation.py:42-148`, `sfm/two_view_geometry.py:38-197`): csrc/sfm.hip. No host fallback: `_engine(engine)`.
+# `sfm/triangulation.py:42-148`, `sfm/two_view_geometry.py:38-197`): csrc/sfm.hip. No host fallback: `default_engine(engine)`.
 DEFAULT_TOLERANCE = 3.0e-5      # depth convergence tolerance of `iterative_LS_triangulation`, absolute
 MAX_SOLVES = 10                 # "Hartley suggests 10 iterations at most"
 
@@ -402,10 +364,8 @@ def undistort_points(pts, camera, engine=None) -> np.ndarray:
     leave about 1e-6 px of the inverse undone on a 24 MP frame: that is the reference's result, not an error of this port."""
     cam = _intrinsics(camera)
     p = _image_points(pts)
-    import torch
-    from ._lib import ptr
-    eng = _engine(engine)
-    d = torch.from_numpy(p).to(eng.device)
+    eng = default_engine(engine)
+    d = to_device(p, eng.device)
     out = torch.empty_like(d)
     eng.ctx.call("im_undistort_points", ptr(d), len(p), cam.ctypes.data, ptr(out), eng.stream_ptr())
     return out.cpu().numpy()
@@ -422,8 +382,6 @@ def undistort_image(image, camera, out_path=None, engine=None):
 
 def _triangulate_device(eng, u1, u2, P1, P2, cam1=None, cam2=None, tolerance=DEFAULT_TOLERANCE, max_solves=MAX_SOLVES, want_und=False):
     """`im_triangulate_iterative` on host point arrays: device tensors (X [n, 3] float64, status [n] int32, und1, und2 [n, 2] float32 or None)."""
-    import torch
-    from ._lib import ptr
     f64 = cam1 is None and (np.asarray(u1).dtype == np.float64 or np.asarray(u2).dtype == np.float64)
     u1, u2 = _image_points(u1, np.float64 if f64 else np.float32), _image_points(u2, np.float64 if f64 else np.float32)
     if len(u1) != len(u2):
@@ -431,7 +389,7 @@ def _triangulate_device(eng, u1, u2, P1, P2, cam1=None, cam2=None, tolerance=DEF
     if not (float(tolerance) >= 0.0):
         raise ValueError(f"the tolerance must be >= 0 (got {tolerance})")
     n, dev = len(u1), eng.device
-    d1, d2 = torch.from_numpy(u1).to(dev), torch.from_numpy(u2).to(dev)
+    d1, d2 = to_device(u1, dev), to_device(u2, dev)
     dX = torch.empty((n, 3), dtype=torch.float64, device=dev)
     dst = torch.empty(n, dtype=torch.int32, device=dev)
     und1 = torch.empty((n, 2), dtype=torch.float32, device=dev) if want_und else None
@@ -452,7 +410,7 @@ def iterative_LS_triangulation(u1, P1, u2, P2, tolerance=DEFAULT_TOLERANCE, engi
     Status: 1 in front of both cameras, -1 only in front of the second, -2 only in front of the first, -3 behind both. The reference
     documents 0 for "not converged, in front of both", but its loop index never reaches 10, so the ten-solve exit is not flagged: a
     point that used all ten solves has status 1 like one that converged (0 only appears for a NaN depth). Kept as it is."""
-    eng = _engine(engine)
+    eng = default_engine(engine)
     dX, dst, _, _ = _triangulate_device(eng, u1, u2, _projection(np.asarray(P1)), _projection(np.asarray(P2)), tolerance=tolerance)
     return dX.cpu().numpy(), dst.cpu().numpy().astype(np.int64)
 
@@ -460,7 +418,7 @@ def iterative_LS_triangulation(u1, P1, u2, P2, tolerance=DEFAULT_TOLERANCE, engi
 def linear_LS_triangulation(u1, P1, u2, P2, engine=None) -> Tuple[np.ndarray, np.ndarray]:
     """`linear_LS_triangulation` of the reference (`thirdparty/triangulation.py:10-76`): the first solve of the iterative form (the same
     kernel with one solve); (points [n, 3] float64, status [n] bool, all True)."""
-    eng = _engine(engine)
+    eng = default_engine(engine)
     dX, _, _, _ = _triangulate_device(eng, u1, u2, _projection(np.asarray(P1)), _projection(np.asarray(P2)), max_solves=1)
     X = dX.cpu().numpy()
     return X, np.ones(len(X), dtype=bool)
@@ -490,7 +448,7 @@ class Triangulate:
         if approach == "iterative_LS_triangulation":
             if compute_colors:
                 assert image is not None and type(image) == np.ndarray, "Invalid input image for interpolating point colors"
-            eng = _engine(self.engine)
+            eng = default_engine(self.engine)
             dX, dst, _, _ = _triangulate_device(eng, self.image_points[i0], self.image_points[i1], _projection(c0), _projection(c1),
                                                 _intrinsics(c0), _intrinsics(c1))
             self.points3d = dX.cpu().numpy()
@@ -500,7 +458,7 @@ class Triangulate:
                 self.colors = _colors_of_device_points(eng, dX, image, self.cameras[cam_id], True)
             return self.points3d
         if approach == "linear_triangulation":
-            eng = _engine(self.engine)
+            eng = default_engine(self.engine)
             p0 = undistort_points(self.image_points[i0], c0, engine=eng).astype(np.float64)
             p1 = undistort_points(self.image_points[i1], c1, engine=eng).astype(np.float64)
             X = triangulate_points_linear(_projection(c0).reshape(3, 4), _projection(c1).reshape(3, 4), np.c_[p0, np.ones(len(p0))],
@@ -566,10 +524,8 @@ def triangulate_table(table, max_kpts: int, cameras, engine=None, undistort: boo
     launch over all records; a failed record (n_matches = -1) and an empty one give zero points. `image` (uint8 [h, w, c], or a list of
     E of them) adds the colours seen by camera `cam_id` of the epoch's pair, read from the points on the device.
     Returns per-epoch views of points3d [n_e, 3] float64, status [n_e] int64, colors [n_e, channels] float64 (or None), and offsets [E + 1]."""
-    import torch
-    from ._lib import ptr
     from .sequence import record_words
-    eng = _engine(engine)
+    eng = default_engine(engine)
     dev = eng.device
     K = int(max_kpts)
     t = table if torch.is_tensor(table) else torch.from_numpy(np.ascontiguousarray(table, dtype=np.int32))
@@ -586,7 +542,7 @@ def triangulate_table(table, max_kpts: int, cameras, engine=None, undistort: boo
     cams = _camera_table(cameras, E) if E else np.zeros((1, 2, 24))
     if images is not None and len(images) == 1 and len(cams) != 1 and E > 1:
         raise ValueError("triangulate_table: one image needs one camera pair (with a camera pair per record give an image per record)")
-    dcams = torch.from_numpy(cams).to(dev)
+    dcams = to_device(cams, dev)
     M = int(t[:, 3].clamp(min=0).sum().item()) if E else 0
     doff = torch.empty(E + 1, dtype=torch.int64, device=dev)
     dX = torch.empty((M, 3), dtype=torch.float64, device=dev)
@@ -626,7 +582,7 @@ class RelativeOrientation:
         assert self.cameras[0].extrinsics is not None, \
             "Extrinsics matrix is not available for camera 0. Please, compute it before running RelativeOrientation estimation."
         ret = estimate_pose(self.features[0], self.features[1], self.cameras[0].K, self.cameras[1].K, thresh=threshold, conf=confidence,
-                            engine=_engine(self.engine))
+                            engine=default_engine(self.engine))
         if ret is None:
             raise ValueError("RelativeOrientation.estimate_pose: at least 5 matches are needed")
         R, t, valid = ret
@@ -650,7 +606,7 @@ class RelativeOrientation:
         accepted and not used); `features` keep the inliers only, as in the reference."""
         self.F, self.inlMask = geometric_verification(self.features[0], self.features[1], GeometricVerification.PYDEGENSAC,
                                                       threshold=threshold, confidence=confidence, max_iters=max_iters,
-                                                      engine=_engine(self.engine))
+                                                      engine=default_engine(self.engine))
         self.features[0] = self.features[0][self.inlMask]
         self.features[1] = self.features[1][self.inlMask]
         return self.F, self.inlMask

@@ -10,6 +10,10 @@ numbers (numpy's default argsort leaves the sign of a zero tie in scipy's min / 
 import warnings
 
 import numpy as np
+import torch
+
+from .._lib import ptr
+from ..engine import default_engine, to_device
 
 STATISTICS = ("count", "sum", "mean", "std", "min", "max", "median")      # the order of `im_binned_stats`' h_slots
 
@@ -52,10 +56,7 @@ def _check_statistic(statistic):
 
 
 def _device_f64(x, dev):
-    import torch
-    if isinstance(x, torch.Tensor):
-        return x.to(device=dev, dtype=torch.float64).contiguous()
-    return torch.from_numpy(np.ascontiguousarray(x, dtype=np.float64)).to(dev)
+    return x.to(device=dev, dtype=torch.float64).contiguous() if isinstance(x, torch.Tensor) else to_device(x, dev, np.float64)
 
 
 def binned_statistics(points, values, statistics, edges, offsets=None, engine=None):
@@ -63,8 +64,6 @@ def binned_statistics(points, values, statistics, edges, offsets=None, engine=No
     tuple of names out of count, sum, mean, std, min, max, median, `edges` the D ascending edge arrays, `offsets` [E + 1] the rows of E
     point sets that share the edges (default: one set). Returns {name: float64 [E, V, n0, n1(, n2)]}, n_d = len(edges[d]) - 1, in scipy's
     axis order. Inputs may be device tensors (they are then not copied to the host and back)."""
-    import torch
-    from .._lib import ptr
     statistics = (statistics,) if isinstance(statistics, str) or callable(statistics) else tuple(statistics)
     for s in statistics:
         _check_statistic(s)
@@ -84,8 +83,7 @@ def binned_statistics(points, values, statistics, edges, offsets=None, engine=No
         decimal = int(-np.log10(dmin)) + 6
         scale.append(10.0 ** abs(decimal))
         mode.append(int(np.sign(decimal)))
-    from ..sfm import _engine      # not at import time: sfm imports matching, which imports this package
-    eng = _engine(engine)
+    eng = default_engine(engine)
     dev = eng.device
     if not isinstance(points, torch.Tensor) and not isinstance(points, np.ndarray):
         points = np.stack([np.asarray(c, np.float64).ravel() for c in points], 1)
@@ -105,8 +103,7 @@ def binned_statistics(points, values, statistics, edges, offsets=None, engine=No
     nb = [len(e) - 1 for e in edges]
     C = int(np.prod(nb))
     st = eng.stream_ptr()
-    d_edges = torch.from_numpy(np.concatenate(edges)).to(dev)
-    d_offs = torch.from_numpy(offs).to(dev)
+    d_edges, d_offs = to_device(np.concatenate(edges), dev), to_device(offs, dev)
     key = torch.empty(N, dtype=torch.int64, device=dev)
     n_edges = np.array([len(e) for e in edges], np.int32)
     h_scale, h_mode = np.array(scale, np.float64), np.array(mode, np.int32)

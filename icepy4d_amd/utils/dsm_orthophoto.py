@@ -12,8 +12,11 @@ Orthophotos from the same DSM are bit-identical."""
 from pathlib import Path
 
 import numpy as np
+import torch
 
-from ..sfm import _camera_params, _channel_map, _engine
+from ..core.camera import _camera_params, _channel_map
+from .._lib import ptr
+from ..engine import default_engine, to_device
 
 
 class DSM:
@@ -61,10 +64,8 @@ class _DeviceDSM(DSM):
 
 def _bin_on_device(eng, pts: np.ndarray, step: float):
     """Rounding, the reference's lexsort, grouping and Kahan means: (x, y, z) float32 of the groups on the device and on the host."""
-    import torch
-    from .._lib import ptr
     dev, n = eng.device, len(pts)
-    dp = torch.from_numpy(pts).to(dev)
+    dp = to_device(pts, dev)
     xr = torch.empty(n, dtype=torch.float32, device=dev)
     yr = torch.empty_like(xr)
     xykey, ykey, zkey = (torch.empty(n, dtype=torch.int64, device=dev) for _ in range(3))
@@ -84,18 +85,16 @@ def _bin_on_device(eng, pts: np.ndarray, step: float):
 
 def _rasterize(eng, dev_b, host_b, xq, yq, step, fill):
     """qhull on the host (scipy's Delaunay, what `LinearNDInterpolator` builds), the per-cell triangle and z on the device."""
-    import torch
     from scipy.spatial import Delaunay
-    from .._lib import ptr
     bx, by, bz = host_b
     tri = Delaunay(np.ascontiguousarray(np.stack([bx, by], 1), dtype=np.float64))   # raises QhullError as the reference does
     simp = np.ascontiguousarray(tri.simplices, dtype=np.int32)
     trans = np.ascontiguousarray(tri.transform, dtype=np.float64)
     dev = eng.device
     dz = torch.empty((len(yq), len(xq)), dtype=torch.float64, device=dev)
-    dxq, dyq = torch.from_numpy(xq).to(dev), torch.from_numpy(yq).to(dev)
+    dxq, dyq = to_device(xq, dev), to_device(yq, dev)
     if dz.numel():
-        ds, dt = torch.from_numpy(simp).to(dev), torch.from_numpy(trans).to(dev)
+        ds, dt = to_device(simp, dev), to_device(trans, dev)
         bounds = np.ascontiguousarray(np.r_[tri.min_bound, tri.max_bound], dtype=np.float64)
         eng.ctx.call("im_dsm_rasterize", ptr(dev_b[0]), ptr(dev_b[1]), ptr(dev_b[2]), ptr(ds), ptr(dt), len(simp), bounds.ctypes.data,
                      ptr(dxq), len(xq), ptr(dyq), len(yq), float(xq[0]), abs(float(step)), float(yq[0]), abs(float(step)), float(fill),
@@ -131,7 +130,7 @@ def build_dsm(points3d, dsm_step=1, xlim=None, ylim=None, interp_method="linear"
     xq = np.arange(xlim[0], xlim[1], dsm_step)
     yq = np.arange(ylim[0], ylim[1], dsm_step)
 
-    eng = _engine(engine)
+    eng = default_engine(engine)
     dev_b, host_b = _bin_on_device(eng, pts, dsm_step)
     if isinstance(fill_value, str) and fill_value == "mean":
         fill_value = host_b[2].mean()
@@ -151,8 +150,6 @@ def generate_ortophoto(image, dsm, camera, xlim=None, ylim=None, res=None, save_
     """`generate_ortophoto` of the reference (`dsm_orthophoto.py:179-233`): every DSM cell with a z is projected into the oriented
     `image` (uint8, BGR as cv2 reads it) and coloured bilinearly; [rows, cols, 3] uint8 RGB, black where z is NaN. `camera` is any object
     with `.K`, `.dist`, `.R` and `.t`. A DSM from `build_dsm` is used from the device; any other `DSM` is uploaded."""
-    import torch
-    from .._lib import ptr
     if save_path is not None:
         import rasterio  # noqa: F401  (raises before any device work when it is missing)
     if res is None:
@@ -163,7 +160,7 @@ def generate_ortophoto(image, dsm, camera, xlim=None, ylim=None, res=None, save_
         raise ValueError(f"generate_ortophoto: a uint8 image is expected (got {image.dtype})")
     chmap = _channel_map(image, True)
     cam = _camera_params(camera)
-    eng = _engine(engine)
+    eng = default_engine(engine)
     dev = eng.device
     zz = dsm.z
     rows, cols = np.shape(zz)
@@ -171,11 +168,10 @@ def generate_ortophoto(image, dsm, camera, xlim=None, ylim=None, res=None, save_
         _, dxq, dyq, dz = dsm._device
         px, sx, py, sy, pz = ptr(dxq), (0, 1), ptr(dyq), (1, 0), ptr(dz)
     else:
-        tx, ty, tz = (torch.from_numpy(np.require(np.broadcast_to(np.asarray(a, np.float64), (rows, cols)), requirements="CW")).to(dev)
-                      for a in (dsm.x, dsm.y, zz))
+        tx, ty, tz = (to_device(np.broadcast_to(np.asarray(a, np.float64), (rows, cols)), dev) for a in (dsm.x, dsm.y, zz))
         px, sx, py, sy, pz = ptr(tx), (cols, 1), ptr(ty), (cols, 1), ptr(tz)
     h, w, cin = image.shape
-    img = torch.from_numpy(np.ascontiguousarray(image)).to(dev)
+    img = to_device(image, dev)
     out = torch.empty((rows, cols, 3), dtype=torch.uint8, device=dev)
     eng.ctx.call("im_project_colors", px, sx[0], sx[1], py, sy[0], sy[1], pz, cols, 1, rows, cols, 1, cam.ctypes.data, ptr(img), h, w, cin,
                  chmap.ctypes.data, 3, None, None, ptr(out), eng.stream_ptr())

@@ -11,6 +11,10 @@ from copy import deepcopy
 from pathlib import Path
 
 import numpy as np
+import torch
+
+from .._lib import ptr
+from ..engine import default_engine, to_device
 
 MAX_SIDE = 32766                 # the taps' coordinates are saturated to a short, as in OpenCV
 WORK_BYTES = 1 << 30             # `stabilise_sequence`: bound on its two working buffers (uploaded chunk, undistorted chunk) together
@@ -129,7 +133,6 @@ def _is_tensor(x) -> bool:
 def _check_image(image, batched: bool = False) -> tuple:
     """(h, w, c, had a channel axis) of a uint8 image H x W [x C] (with a leading n when `batched`), numpy or device tensor."""
     if _is_tensor(image):
-        import torch
         ok = image.dtype == torch.uint8
     else:
         ok = isinstance(image, np.ndarray) and image.dtype == np.uint8
@@ -144,19 +147,13 @@ def _check_image(image, batched: bool = False) -> tuple:
     return h, w, c, len(shape) == 3
 
 
-def _engine(engine):
-    from ..sfm import _engine as get
-    return get(engine)
-
-
-def _to_device(eng, image):
-    import torch
+def _on_engine(eng, image):
+    """The image as a contiguous tensor on the engine's device; a tensor that lives elsewhere is refused, not moved."""
     if _is_tensor(image):
         if image.device != eng.device:
             raise ValueError(f"the image is on {image.device}, the engine on {eng.device}")
         return image.contiguous()
-    a = np.ascontiguousarray(image)
-    return torch.from_numpy(a if a.flags.writeable else a.copy()).to(eng.device)
+    return to_device(image, eng.device)
 
 
 def _write(out_path, image) -> None:
@@ -171,8 +168,6 @@ def _write(out_path, image) -> None:
 # ---- the two launches ----------------------------------------------------------------------------------------------------------------
 def undistort_device(eng, d_src, h_cam: np.ndarray, d_dst=None):
     """`im_undistort_image` on a contiguous [n, h, w, c] uint8 device tensor: one camera for all images."""
-    import torch
-    from .._lib import ptr
     n, h, w, c = d_src.shape
     if d_dst is None:
         d_dst = torch.empty_like(d_src)
@@ -182,12 +177,9 @@ def undistort_device(eng, d_src, h_cam: np.ndarray, d_dst=None):
 
 def warp_device(eng, d_src, minv: np.ndarray, out_hw=None, d_dst=None):
     """`im_warp_perspective` on a contiguous [n, h, w, c] uint8 device tensor: minv [n, 9] float64 (host), one inverse per image."""
-    import torch
-    from .._lib import ptr
     n, h, w, c = d_src.shape
     oh, ow = (h, w) if out_hw is None else out_hw
-    minv = np.ascontiguousarray(minv, np.float64).reshape(n, 9)
-    d_minv = torch.from_numpy(minv).to(eng.device)
+    d_minv = to_device(np.asarray(minv, np.float64).reshape(n, 9), eng.device)
     if d_dst is None:
         d_dst = torch.empty((n, oh, ow, c), dtype=torch.uint8, device=eng.device)
     eng.ctx.call("im_warp_perspective", ptr(d_src), n, h, w, c, ptr(d_minv), oh, ow, ptr(d_dst), eng.stream_ptr())
@@ -205,8 +197,8 @@ def undistort_image(image, camera, out_path=None, engine=None):
     H x W [x C] numpy array or device tensor; returns the same kind."""
     h, w, c, had_c = _check_image(image)
     h_cam = undistort_params(camera)
-    eng = _engine(engine)
-    d_out = undistort_device(eng, _to_device(eng, image).reshape(1, h, w, c), h_cam)
+    eng = default_engine(engine)
+    d_out = undistort_device(eng, _on_engine(eng, image).reshape(1, h, w, c), h_cam)
     out = _like_input(image, d_out, had_c)
     if out_path is not None:
         _write(out_path, out)
@@ -220,8 +212,8 @@ def homography_warping(cam_0, cam_1, image, undistort: bool = False, out_path=No
     h, w, c, had_c = _check_image(image)
     minv = inverse_homography(homography(cam_0, cam_1))
     h_cam = undistort_params(cam_1) if undistort else None
-    eng = _engine(engine)
-    d = _to_device(eng, image).reshape(1, h, w, c)
+    eng = default_engine(engine)
+    d = _on_engine(eng, image).reshape(1, h, w, c)
     if undistort:
         d = undistort_device(eng, d, h_cam)
     out = _like_input(image, warp_device(eng, d, minv[None]), had_c)
@@ -236,7 +228,6 @@ def stabilise_sequence(cam_ref, cameras, images, undistort: bool = True, engine=
     [n, h, w, c] uint8 device tensor (numpy with `to_host`). The images go through in chunks whose two working buffers (the uploaded
     chunk of a host list, the undistorted chunk) hold at most WORK_BYTES together, or one image each; the result itself is not counted.
     One undistort launch takes one camera: epochs of a chunk whose K or dist differ are undistorted in runs of equal intrinsics."""
-    import torch
     cameras = list(cameras)
     if _is_tensor(images):
         if images.ndim != 4:
@@ -256,7 +247,7 @@ def stabilise_sequence(cam_ref, cameras, images, undistort: bool = True, engine=
         raise ValueError(f"{n} images for {len(cameras)} cameras")
     minv = np.stack([inverse_homography(homography(cam_ref, cam)) for cam in cameras])
     cams = [undistort_params(cam) for cam in cameras] if undistort else None
-    eng = _engine(engine)
+    eng = default_engine(engine)
     if _is_tensor(images) and images.device != eng.device:
         raise ValueError(f"the images are on {images.device}, the engine on {eng.device}")
     out = torch.empty((n, h, w, c), dtype=torch.uint8, device=eng.device)
@@ -266,7 +257,7 @@ def stabilise_sequence(cam_ref, cameras, images, undistort: bool = True, engine=
         if _is_tensor(images):
             d = images[a:b].contiguous()
         else:
-            d = torch.from_numpy(np.stack([np.asarray(im).reshape(h, w, c) for im in images[a:b]])).to(eng.device)
+            d = to_device(np.stack([np.asarray(im).reshape(h, w, c) for im in images[a:b]]), eng.device)
         if undistort:
             und = torch.empty_like(d)
             r = a

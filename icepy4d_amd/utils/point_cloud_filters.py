@@ -23,6 +23,10 @@ PARITY WITH AN OPEN3D BINARY IS UNPINNED. Open3D is not a dependency; its publis
 import math
 
 import numpy as np
+import torch
+
+from .._lib import ptr
+from ..engine import default_engine, to_device
 
 MAX_K = 64
 CELL_OCCUPANCY = 0.25      # tunable: the cell size is chosen so that an occupied cell holds about CELL_OCCUPANCY * k points
@@ -35,12 +39,7 @@ def max_cells() -> int:
 
 
 def _device_points(points, dev):
-    import torch
-    if isinstance(points, torch.Tensor):
-        pts = points.to(device=dev, dtype=torch.float64).contiguous()
-    else:
-        host = np.ascontiguousarray(points, dtype=np.float64)
-        pts = torch.from_numpy(host if host.flags.writeable else host.copy()).to(dev)
+    pts = points.to(device=dev, dtype=torch.float64).contiguous() if isinstance(points, torch.Tensor) else to_device(points, dev, np.float64)
     if pts.ndim != 2 or pts.shape[1] != 3:
         raise ValueError(f"points must be [n, 3] (got {tuple(pts.shape)})")
     if pts.shape[0] >= 2 ** 31:
@@ -69,8 +68,6 @@ def fit_cell_size(lo, hi, s, cap):
 
 
 def _occupied(eng, pts, lo, s, dims):
-    import torch
-    from .._lib import ptr
     key = torch.empty(pts.shape[0], dtype=torch.int64, device=pts.device)
     grid = np.array([lo[0], lo[1], lo[2], s], np.float64)
     eng.ctx.call("im_knn_cells", ptr(pts), pts.shape[0], grid.ctypes.data, dims[0], dims[1], dims[2], ptr(key), eng.stream_ptr())
@@ -101,9 +98,6 @@ def knn_self(points, k, radius=None, cell_size=None, want=("idx", "d2", "count")
     float64 (SOR's statistic), normal [n, 3] float64, rings [n] int32 (rings of cells the search visited, the query's cell counted; negated where
     the search spent its step budget and ended by a scan of the whole cloud),
     plus "cell_size" and "dims" (host values). All are addressed by the original point index."""
-    import torch
-    from .._lib import ptr
-    from ..sfm import _engine      # not at import time: sfm imports matching, which imports this package
     k = int(k)
     if not 1 <= k <= MAX_K:
         raise ValueError(f"k must be 1..{MAX_K} (got {k})")
@@ -114,7 +108,7 @@ def knn_self(points, k, radius=None, cell_size=None, want=("idx", "d2", "count")
     unknown = set(want) - {"idx", "d2", "count", "mean", "normal", "rings"}
     if unknown:
         raise ValueError(f"unknown outputs {sorted(unknown)}")
-    eng = _engine(engine)
+    eng = default_engine(engine)
     dev = eng.device
     pts = _device_points(points, dev)
     n = pts.shape[0]
@@ -174,7 +168,6 @@ def sor_indices(avg, count, std_ratio):
 def remove_statistical_outlier(points, nb_neighbors, std_ratio, engine=None, cell_size=None):
     """Statistical outlier removal as Open3D publishes it (module docstring; parity with an Open3D binary is unpinned):
     (kept_points [m, 3], ind [m] ascending). numpy in, numpy out; device tensors in, device tensors out."""
-    import torch
     if int(nb_neighbors) < 1 or not float(std_ratio) > 0.0:
         raise ValueError("remove_statistical_outlier: nb_neighbors must be >= 1 and std_ratio > 0")
     if int(nb_neighbors) > MAX_K:
@@ -183,7 +176,7 @@ def remove_statistical_outlier(points, nb_neighbors, std_ratio, engine=None, cel
     r = knn_self(points, int(nb_neighbors), cell_size=cell_size, want=("count", "mean"), engine=engine)
     ind, _ = sor_indices(r["mean"].cpu().numpy(), r["count"].cpu().numpy(), std_ratio)
     if is_tensor:
-        d_ind = torch.from_numpy(ind).to(points.device)
+        d_ind = to_device(ind, points.device)
         return points.reshape(-1, 3)[d_ind], d_ind
     return np.asarray(points).reshape(-1, 3)[ind], ind
 
@@ -191,6 +184,5 @@ def remove_statistical_outlier(points, nb_neighbors, std_ratio, engine=None, cel
 def estimate_normals(points, radius=1.0, max_nn=30, engine=None, cell_size=None):
     """Normals [n, 3] float64 of the hybrid neighbourhoods (d2 <= radius^2, at most max_nn, the point itself among them); `radius=None`
     is a plain k-nearest search. See the module docstring for what is and is not Open3D's. numpy in, numpy out; tensor in, tensor out."""
-    import torch
     r = knn_self(points, int(max_nn), radius=radius, cell_size=cell_size, want=("normal",), engine=engine)
     return r["normal"] if isinstance(points, torch.Tensor) else r["normal"].cpu().numpy()

@@ -7,6 +7,10 @@ from datetime import datetime
 from typing import NamedTuple
 
 import numpy as np
+import torch
+
+from .._lib import ptr
+from ..engine import default_engine, to_device
 
 INT_COLS = ("fid", "num_tracked_eps", "ep_ini", "ep_fin", "dt", "index")
 F64_COLS = ("X_ini", "Y_ini", "Z_ini", "X_fin", "Y_fin", "Z_fin", "dX", "dY", "dZ", "vX", "vY", "vZ", "V")
@@ -88,8 +92,6 @@ def tracked_points_table(track_ids, points3d, days, min_tracked_epoches=1, volum
     inclusive box of its minima and maxima). ini / fin are the first / last such epoch; d = fin - ini, dt = day_fin - day_ini,
     v = d / dt (inf / NaN for dt = 0, as pandas), V = |v|. Rows with dt >= `min_dt` and lo <= v < hi for every given `v*_lims` are
     kept. `image_points` {cam: per-epoch [n_e, 2]} adds x_{cam}_ini, y_{cam}_ini, x_{cam}_fin, y_{cam}_fin."""
-    import torch
-    from .._lib import ptr
     ids, xyz = _pack(track_ids, points3d)
     E = len(ids)
     days = np.ascontiguousarray(days, dtype=np.int64).ravel()
@@ -117,13 +119,11 @@ def tracked_points_table(track_ids, points3d, days, min_tracked_epoches=1, volum
             if np.isnan(lims[k]).any():
                 raise ValueError("tracked_points_table: velocity limits must be numbers")
     h_min_dt = None if min_dt is None else np.array([int(min_dt)], np.int64)
-    from ..sfm import _engine      # not at import time: sfm imports matching, which imports this package
-    eng = _engine(engine)
+    eng = default_engine(engine)
     dev = eng.device
-    d_ids = torch.from_numpy(np.concatenate(ids) if M else np.zeros(0, np.int64)).to(dev)
-    d_xyz = torch.from_numpy(np.concatenate(xyz) if M else np.zeros((0, 3))).to(dev)
-    d_img = torch.from_numpy(img).to(dev) if cams else None
-    d_offs, d_days = torch.from_numpy(offs).to(dev), torch.from_numpy(days).to(dev)
+    d_ids, d_xyz = to_device(np.concatenate(ids) if M else np.zeros(0, np.int64), dev), to_device(np.concatenate(xyz) if M else np.zeros((0, 3)), dev)
+    d_img = to_device(img, dev) if cams else None
+    d_offs, d_days = to_device(offs, dev), to_device(days, dev)
     sid, perm = torch.sort(d_ids, stable=True)             # rows are concatenated by epoch: stable by id = ordered by (id, epoch)
     n_f64 = len(F64_COLS) + 4 * len(cams)
     oi = torch.empty((len(INT_COLS), M), dtype=torch.int64, device=dev)

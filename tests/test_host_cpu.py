@@ -712,19 +712,12 @@ def test_kernels_keep_their_register_budget(tmp_path):
     waves until round 5 found WHY it fitted: the compiler reused one 4-register temporary for all 16 row loads of a group and waited for each
     load on its own - one kilobyte in flight per wave). So the listing is also checked for what the budget is for: in each sweep at least
     eight 16-byte row loads are issued back to back before the first wait."""
-    hipcc = "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("no hipcc")
-    out = tmp_path / "lg_misc.s"
-    r = subprocess.run([hipcc, "-O3", "-std=c++17", "--offload-arch=gfx950", "-S", "--cuda-device-only", "-I" + os.path.join(ROOT, "include"),
-                        os.path.join(ROOT, "icepy4d_amd", "csrc", "lg_misc.hip"), "-o", str(out)], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    seen = {}
-    for blk in re.split(r"\n  - \.agpr_count:", out.read_text())[1:]:
-        def field(k):
-            m = re.search(r"\." + k + r":\s+(\S+)", blk)
-            return m.group(1) if m else "0"
-        seen[field("name")] = (int(field("vgpr_count")), int(field("vgpr_spill_count")))
+    from toolchain import device_listing, kernel_body, kernel_resources
+
+    def budget(listing):        # (registers, spilled registers, scratch bytes) of every kernel
+        return {k: (f["vgpr_count"], f["vgpr_spill_count"], f["private_segment_fixed_size"]) for k, f in kernel_resources(listing).items()}
+    text = device_listing("lg_misc.hip", str(tmp_path))
+    seen = {k: v[:2] for k, v in budget(text).items()}
     assert len(seen) >= 20
     assert all(spill == 0 for _, spill in seen.values()), {k: v for k, v in seen.items() if v[1]}
     lse = [v for k, v in seen.items() if "lse_stats_kernelILb1" in k]
@@ -732,11 +725,9 @@ def test_kernels_keep_their_register_budget(tmp_path):
     assert lse and best
     assert all(v <= 168 for v, _ in lse), lse
     assert all(v <= 168 for v, _ in best), best
-    text = out.read_text()
     for sym in ("_ZN2im16lse_stats_kernelILb1EEEvNS_10AssignArgsE", "_ZN2im17best_sweep_kernelILi0ELb1EEEvNS_10AssignArgsE",
                 "_ZN2im22col_lse_combine_kernelENS_10AssignArgsE", "_ZN2im23col_best_combine_kernelENS_10AssignArgsE"):
-        body = text[text.index(sym + ":"):]
-        body = body[:body.index(".Lfunc_end")]
+        body = kernel_body(text, sym)
         mem = [l.strip() for l in body.split("\n") if l.strip().startswith(("global_load_dwordx4", "global_load_dwordx2", "s_waitcnt vmcnt"))]
         run = best_run = 0
         for l in mem:
@@ -744,25 +735,12 @@ def test_kernels_keep_their_register_budget(tmp_path):
             best_run = max(best_run, run)
         assert best_run >= 8, (sym, best_run)      # loads in flight together, not one at a time
     # the Winograd convolution: every instantiation at two waves per SIMD (<= 256 registers) without scratch
-    out2 = tmp_path / "conv_wino.s"
-    r = subprocess.run([hipcc, "-O3", "-std=c++17", "--offload-arch=gfx950", "-S", "--cuda-device-only", "-I" + os.path.join(ROOT, "include"),
-                        os.path.join(ROOT, "icepy4d_amd", "csrc", "conv_wino.hip"), "-o", str(out2)], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    conv = {}
-    for blk in re.split(r"\n  - \.agpr_count:", out2.read_text())[1:]:
-        def field2(k):
-            m = re.search(r"\." + k + r":\s+(\S+)", blk)
-            return m.group(1) if m else "0"
-        conv[field2("name")] = (int(field2("vgpr_count")), int(field2("vgpr_spill_count")), int(field2("private_segment_fixed_size")))
+    text = device_listing("conv_wino.hip", str(tmp_path))
+    conv = budget(text)
     # f32-input form: pool / plain x fused / plain x U through registers / LDS, minus the unpooled fused register form (7); BX (round 6, the
     # products on the bf16 matrix cores): plain, pooled, fused + pooled (3)
     assert len(conv) == 10, sorted(conv)
     assert all(v <= 256 and sp == 0 and scratch == 0 for v, sp, scratch in conv.values()), conv
-    text = out2.read_text()
-
-    def kernel_body(txt, sym):
-        body = txt[txt.index(sym + ":"):]
-        return body[:body.index(".Lfunc_end")]
 
     def hot_block(body, mfma):
         return max(re.split(r"\n\.LBB\d+_\d+:", body), key=lambda b: b.count(mfma))
@@ -802,17 +780,8 @@ def test_kernels_keep_their_register_budget(tmp_path):
     # barrier - 3 U pieces per wave and quarter (vmcnt(3): the quarter's own pieces may still fly), the wave's patch pieces of the next chunk (each
     # under its own predicate: blocks of their own) between quarters 3 and 4 (vmcnt(8) = 3 + 5 in quarters 4 and 1); nothing else in vector memory
     # inside the chunk loop, no scratch
-    out3 = tmp_path / "conv_wino_bx2.s"
-    r = subprocess.run([hipcc, "-O3", "-std=c++17", "--offload-arch=gfx950", "-S", "--cuda-device-only", "-I" + os.path.join(ROOT, "include"),
-                        os.path.join(ROOT, "icepy4d_amd", "csrc", "conv_wino_bx2.hip"), "-o", str(out3)], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    t3 = out3.read_text()
-    bx2 = {}
-    for blk in re.split(r"\n  - \.agpr_count:", t3)[1:]:
-        def field4(k):
-            m = re.search(r"\." + k + r":\s+(\S+)", blk)
-            return m.group(1) if m else "0"
-        bx2[field4("name")] = (int(field4("vgpr_count")), int(field4("vgpr_spill_count")), int(field4("private_segment_fixed_size")))
+    t3 = device_listing("conv_wino_bx2.hip", str(tmp_path))
+    bx2 = budget(t3)
     assert len(bx2) == 2 and all(v <= 256 and sp == 0 and scratch == 0 for v, sp, scratch in bx2.values()), bx2
     for sym in ("_ZN2im23conv3x3_wino_bx2_kernelILb0EEEvNS_8ConvArgsEi", "_ZN2im23conv3x3_wino_bx2_kernelILb1EEEvNS_8ConvArgsEi"):
         body = kernel_body(t3, sym)
@@ -830,25 +799,14 @@ def test_kernels_keep_their_register_budget(tmp_path):
     # bf16 MFMAs apart (the vector work of a tile is dealt over the MFMA slots by hand: at most two MFMAs back to back outside the last PV group),
     # and the product form stages by LDS-DMA (no ds_write in its loop)
     for name, n_kernels in (("attention_bx.hip", 4), ("ffn_fused.hip", 4), ("gemm.hip", 26)):
-        o = tmp_path / (name + ".s")
-        r = subprocess.run([hipcc, "-O3", "-std=c++17", "--offload-arch=gfx950", "-S", "--cuda-device-only", "-I" + os.path.join(ROOT, "include"),
-                            os.path.join(ROOT, "icepy4d_amd", "csrc", name), "-o", str(o)], capture_output=True, text=True)
-        assert r.returncode == 0, r.stderr[-2000:]
-        ks = {}
-        for blk in re.split(r"\n  - \.agpr_count:", o.read_text())[1:]:
-            def field3(k):
-                m = re.search(r"\." + k + r":\s+(\S+)", blk)
-                return m.group(1) if m else "0"
-            ks[field3("name")] = (int(field3("vgpr_count")), int(field3("vgpr_spill_count")), int(field3("private_segment_fixed_size")))
+        text = device_listing(name, str(tmp_path))
+        ks = budget(text)
         assert len(ks) == n_kernels, (name, sorted(ks))
         assert all(v <= 256 and sp == 0 and scratch == 0 for v, sp, scratch in ks.values()), (name, ks)
         if name == "ffn_fused.hip":      # the split form is there to have TWO blocks of 8 waves per CU: four waves per SIMD = 128 registers
             assert all(v <= 128 for k, (v, _, _) in ks.items() if "ffn_fused_split_kernel" in k) and sum("ffn_fused_split_kernel" in k for k in ks) == 2, ks
         if name == "attention_bx.hip":
-            text = o.read_text()
-            sym = "_ZN2im20flash_attn_bx_kernelILb1ELb1EEEvNS_8AttnArgsE"
-            body = text[text.index(sym + ":"):]
-            body = body[:body.index(".Lfunc_end")]
+            body = kernel_body(text, "_ZN2im20flash_attn_bx_kernelILb1ELb1EEEvNS_8AttnArgsE")
             assert body.count("v_mfma_f32_32x32x16_bf16") >= 48 and "v_mfma_f32_32x32x2_f32" not in body
             assert body.count("buffer_load_dwordx4") >= 6 and " lds" in body
             # the hand-dealt loop: the basic block with the most bf16 MFMAs holds the 48 of a step; count its longest run of adjacent MFMAs

@@ -13,7 +13,6 @@ must leave at most 1 % of a case's points under the eigenvalue gap of 1e-6 that 
 Jacobi vector must lie within 1e-8 of eigh's for the others (Davis-Kahan: a few hundred eps over a gap of 1e-6)."""
 import ctypes
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -23,6 +22,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import knn_cases as KC  # noqa: E402
 import knn_oracle as O  # noqa: E402
+import toolchain  # noqa: E402
 
 # 4099 x 4099 x rings in a scalar loop, and 2^24 rings for a lone point (the host search has no step budget): the device test covers them
 HOST_SKIP = {"n4099", "cell_cap_lone_z", "cell_cap_lone_y"}
@@ -38,17 +38,7 @@ def g16():
 @pytest.fixture(scope="module")
 def host_lib(tmp_path_factory):
     """tests/knn_host_harness.cpp + csrc/knn_point.h as a shared library, behind a stub <hip/hip_runtime.h>."""
-    cxx = "/opt/rocm/llvm/bin/clang++"
-    if not os.path.exists(cxx):
-        pytest.skip("no clang++")
-    d = tmp_path_factory.mktemp("knn_host")
-    (d / "hip").mkdir()
-    (d / "hip" / "hip_runtime.h").write_text("#pragma once\n#define __device__\n#define __forceinline__ inline\n")
-    so = d / "libknn_host.so"
-    r = subprocess.run([cxx, "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-I", str(d), "-I", os.path.join(ROOT, "icepy4d_amd", "csrc"),
-                        os.path.join(ROOT, "tests", "knn_host_harness.cpp"), "-o", str(so)], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    lib = ctypes.CDLL(str(so))
+    lib = toolchain.host_library(str(tmp_path_factory.mktemp("knn_host")), "knn_host_harness.cpp")
     P, I, L, D = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_double
     lib.knn_host_cells.argtypes = [P, L, P, P, P, P, P]
     lib.knn_host_d2.argtypes, lib.knn_host_d2.restype = [P, P], D

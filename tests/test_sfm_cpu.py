@@ -14,7 +14,6 @@ a lost `#pragma clang fp contract(off)` does not show here. That is seen on the 
 import ctypes
 import os
 import re
-import subprocess
 import sys
 
 import numpy as np
@@ -24,6 +23,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import sfm_cases as C  # noqa: E402
 import sfm_oracle as S  # noqa: E402
+import toolchain  # noqa: E402
 
 
 @pytest.fixture(scope="module")
@@ -205,19 +205,8 @@ def test_pack_table_layout():
 def test_sfm_kernels_stay_in_registers(tmp_path):
     """csrc/sfm.hip compiled to assembly for gfx950: every kernel without spills and without a private segment (the small matrices of the
     Jacobi solver are indexed with compile-time constants only, so none of them lands in scratch)."""
-    hipcc = "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("no hipcc")
-    out = tmp_path / "sfm.s"
-    r = subprocess.run([hipcc, "-O3", "-std=c++17", "--offload-arch=gfx950", "-S", "--cuda-device-only", "-I" + os.path.join(ROOT, "include"),
-                        os.path.join(ROOT, "icepy4d_amd", "csrc", "sfm.hip"), "-o", str(out)], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    seen = {}
-    for blk in re.split(r"\n  - \.agpr_count:", out.read_text())[1:]:
-        def field(k):
-            m = re.search(r"\." + k + r":\s+(\S+)", blk)
-            return m.group(1) if m else "0"
-        seen[field("name")] = (int(field("vgpr_spill_count")), int(field("sgpr_spill_count")), int(field("private_segment_fixed_size")))
+    seen = {k: (f["vgpr_spill_count"], f["sgpr_spill_count"], f["private_segment_fixed_size"])
+            for k, f in toolchain.kernel_resources(toolchain.device_listing("sfm.hip", str(tmp_path))).items()}
     names = " ".join(seen)
     for k in ("undistort_points_kernel", "triangulate_iterative_kernelIf", "triangulate_iterative_kernelId", "table_offsets_kernel",
               "triangulate_table_kernel"):
@@ -234,17 +223,7 @@ def bits(a):
 @pytest.fixture(scope="module")
 def host_lib(tmp_path_factory):
     """tests/sfm_host_harness.cpp + csrc/sfm_point.h as a shared library, behind a stub <hip/hip_runtime.h>."""
-    cxx = "/opt/rocm/llvm/bin/clang++"
-    if not os.path.exists(cxx):
-        pytest.skip("no clang++")
-    d = tmp_path_factory.mktemp("sfm_host")
-    (d / "hip").mkdir()
-    (d / "hip" / "hip_runtime.h").write_text("#define __device__\n#define __forceinline__ inline\n")
-    so = d / "libsfm_host.so"
-    r = subprocess.run([cxx, "-O2", "-std=c++17", "-shared", "-fPIC", "-I" + str(d), "-I" + os.path.join(ROOT, "icepy4d_amd", "csrc"),
-                        os.path.join(ROOT, "tests", "sfm_host_harness.cpp"), "-o", str(so)], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    lib = ctypes.CDLL(str(so))
+    lib = toolchain.host_library(str(tmp_path_factory.mktemp("sfm_host")), "sfm_host_harness.cpp")
     P, L = ctypes.c_void_p, ctypes.c_longlong
     lib.sfm_host_undistort.argtypes, lib.sfm_host_undistort.restype = [P, L, P, P], None
     lib.sfm_host_triangulate.argtypes, lib.sfm_host_triangulate.restype = [P, P, L, P, P, ctypes.c_double, ctypes.c_int, P, P], None

@@ -12,7 +12,6 @@ thresholds, not the contraction: the host build is for plain x86-64, which has n
 import ctypes
 import os
 import re
-import subprocess
 import sys
 import types
 
@@ -21,6 +20,7 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
+import toolchain  # noqa: E402
 import warp_oracle as W  # noqa: E402
 
 N = 7
@@ -268,17 +268,7 @@ def test_symbols_declared_in_header_and_binding():
 @pytest.fixture(scope="module")
 def host_lib(tmp_path_factory):
     """tests/warp_host_harness.cpp + csrc/warp_pixel.h as a shared library, behind a stub <hip/hip_runtime.h>."""
-    cxx = "/opt/rocm/llvm/bin/clang++"
-    if not os.path.exists(cxx):
-        pytest.skip("no clang++")
-    d = tmp_path_factory.mktemp("warp_host")
-    (d / "hip").mkdir()
-    (d / "hip" / "hip_runtime.h").write_text("#pragma once\n#define __device__\n#define __forceinline__ inline\n")
-    so = d / "libwarp_host.so"
-    r = subprocess.run([cxx, "-O2", "-std=c++17", "-shared", "-fPIC", "-I" + str(d), "-I" + os.path.join(ROOT, "icepy4d_amd", "csrc"),
-                        os.path.join(ROOT, "tests", "warp_host_harness.cpp"), "-o", str(so)], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    lib = ctypes.CDLL(str(so))
+    lib = toolchain.host_library(str(tmp_path_factory.mktemp("warp_host")), "warp_host_harness.cpp")
     P, I = ctypes.c_void_p, ctypes.c_int
     lib.warp_host_perspective.argtypes, lib.warp_host_perspective.restype = [P, I, I, I, I, P, I, I, P], None
     lib.warp_host_undistort.argtypes, lib.warp_host_undistort.restype = [P, I, I, I, I, P, P], None

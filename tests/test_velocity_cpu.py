@@ -127,12 +127,16 @@ def test_new_symbols_are_declared_bound_and_built():
     assert M.lds_cell_capacity() == lib.im_binned_lds_capacity() > 64
 
 
-@pytest.mark.parametrize("first", ["sfm", "utils.binned_stats"])
+@pytest.mark.parametrize("first", ["sfm", "utils.binned_stats", "utils.point_cloud_filters", "utils.homography", "utils.dsm_orthophoto",
+                                   "matching.templatematch"])
 def test_every_module_can_be_the_first_import(first):
-    """`sfm` imports `matching`, which imports `utils`, which imports the velocity modules: these must not need `sfm` at import time.
+    """`sfm` imports `matching`, which imports `utils`, which imports the velocity modules: these must not need `sfm` at import time, and
+    the stage modules do not need it at all (the engine they default to comes from `engine`, not through `sfm`).
     A fresh interpreter, because the order of the imports in this process is the suite's."""
     import subprocess
-    code = (f"import icepy4d_amd.{first}; from icepy4d_amd import sfm, utils; from icepy4d_amd.sfm import _engine; "
+    no_sfm = first in ("utils.point_cloud_filters", "utils.homography", "utils.dsm_orthophoto", "matching.templatematch")
+    code = (f"import sys, icepy4d_amd.{first}; assert not {no_sfm} or 'icepy4d_amd.sfm' not in sys.modules, 'imports sfm'; "
+            "from icepy4d_amd import sfm, utils; from icepy4d_amd.engine import default_engine; "
             "assert callable(utils.binned_stats.binned_statistics) and callable(utils.tracking_features_utils.tracked_points_table)")
     r = subprocess.run([sys.executable, "-c", code], cwd=ROOT, capture_output=True, text=True)
     assert r.returncode == 0, r.stderr[-2000:]
