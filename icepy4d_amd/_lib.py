@@ -101,6 +101,13 @@ SIGNATURES = {
     "im_knn_cells": [_P, _P, _L, _P, _I, _I, _I, _P, _P],
     "im_knn_cell_ranges": [_P, _P, _L, _L, _P, _P],
     "im_knn_self": [_P, _P, _P, _P, _L, _P, _I, _I, _I, _I, _D, _P, _P, _P, _P, _P, _P, _P],
+    "im_dod_chunk": [],
+    "im_dod_max_cells": [],
+    "im_dod_max_batch_cells": [],
+    "im_dod_bounds": [_P, _P, _P, _I, _I, _P, _P, _P],
+    "im_dod_keys": [_P, _P, _P, _I, _P, _I, _I, _D, _P, _P, _P, _P],
+    "im_dod_reduce": [_P, _P, _P, _I, _P, _I, _I, _D, _P, _P, _P, _P, _P, _P],
+    "im_crop_polygon": [_P, _P, _L, _I, _I, _P, _I, _I, _P, _P, _P, _P],
 }
 
 

@@ -1,5 +1,5 @@
 // What the stage entry points that carve one scratch buffer lay into it, apart from the kernels so that a host compiler reads it too:
-// tests/test_stage_plumbing_cpu.py pins every total. Each is a Carve whose pieces are members; their order of declaration is the layout.
+// tests/test_stage_plumbing_cpu.py pins every total (tests/test_dod_cpu.py those of dod.hip). Each is a Carve whose pieces are members; their order of declaration is the layout.
 #pragma once
 #include "carve.h"
 
@@ -30,6 +30,23 @@ struct TrackedPointsScratch : Carve { // im_tracked_points, M > 0 rows: starts [
 struct KnnSortedScratch : Carve {     // im_knn_self, n > 0 points: the cloud in cell order, x y z [n] each and the original indices [n]
     Piece<double> x, y, z; Piece<int> idx;
     explicit KnnSortedScratch(long long n) : x(take<double>(n)), y(take<double>(n)), z(take<double>(n)), idx(take<int>(n)) {}
+};
+// im_dod_bounds (P = cells = chunks = 0), im_dod_keys and im_dod_reduce, E clouds, P pairs, `cells` cells and `chunks` chunks over the batch:
+// table [E + 9 P + 5] (cloud offsets, per side the first item, segment and point, per pair w, h and the first chunk), gmin [2 P] (per pair
+// min_x, min_y), bkeys [4 E],
+// counts [2 cells], starts [2 cells + 1], sums [scan blocks], parts [3 chunks], ncnt [5 P], state [cells], H [own_h ? cells : 0]
+struct DodScratch : Carve {
+    Piece<long long> table; Piece<double> gmin; Piece<unsigned long long> bkeys; Piece<unsigned> counts; Piece<long long> starts, sums; Piece<double> parts;
+    Piece<unsigned long long> ncnt; Piece<unsigned char> state; Piece<double> H;
+    DodScratch(long long E, long long P, long long cells, long long chunks, bool own_h)
+        : table(take<long long>(E + 9 * P + 5)), gmin(take<double>(2 * P)), bkeys(take<unsigned long long>(4 * E)), counts(take<unsigned>(2 * cells)),
+          starts(take<long long>(2 * cells + 1)), sums(take<long long>(blocks_of(cells > 0 ? 2 * cells : 1, SCAN_THREADS))),
+          parts(take<double>(3 * chunks)), ncnt(take<unsigned long long>(5 * P)), state(take<unsigned char>(cells)),
+          H(take<double>(own_h ? cells : 0)) {}
+};
+struct CropScratch : Carve {          // im_crop_polygon, n > 0 points: the polygon [2 * 1024], sums [scan blocks]
+    Piece<double> poly; Piece<long long> sums;
+    explicit CropScratch(long long n) : poly(take<double>(2 * 1024)), sums(take<long long>(blocks_of(n, SCAN_THREADS))) {}
 };
 
 }  // namespace im

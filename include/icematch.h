@@ -404,6 +404,52 @@ int im_knn_self(im_ctx* ctx, const double* d_pts, const long long* d_perm, const
                 int ny, int nz, int k, double radius2, int32_t* d_count, int32_t* d_idx, double* d_d2, double* d_mean, double* d_normal,
                 int32_t* d_rings, void* stream);
 
+/* ---- volume variations (`scripts/pcd_postprocessing/volume_variations.py`; `post_processing/cloudcompare_fun.py`:
+ * `DemOfDifference.compute_volume` over CloudCompare's `ComputeVolume25D`; `post_processing/open3d_fun.py`: `filter_pcd_by_polyline`);
+ * csrc/dod.hip, csrc/dod_cell.h. The DEM of difference of P pairs (ground, ceil) over E clouds that lie one behind the other in d_pts
+ * [n][3] float64, DEVICE memory; h_offsets [E + 1] int64 in HOST memory = the first point of every cloud, h_offsets[0] = 0; h_pairs [P][2]
+ * int32 in HOST memory = cloud indices (ground, ceil). vert_dim d in 0..2: heights along d, the grid over X = (d + 1) % 3 and
+ * Y = (d + 2) % 3. A point with a non-finite coordinate is ignored. Per pair: min / max over the kept points of both clouds,
+ * w = 1 + floor((max_x - min_x) / step + 0.5), h likewise, a point in column floor((x - min_x) / step + 0.5), cell j w + i; per cloud
+ * and cell the mean of the d-coordinates summed in ascending point index from +0.0; H = mean_ceil - mean_ground where both clouds fill
+ * the cell, NaN elsewhere; a cell is valid when H is finite. No kept point: w = h = 0. float64, no fused operations
+ * (tests/dod_oracle.py: bit-identical; parity with a CloudCompare binary is not pinned).
+ * im_dod_chunk: B (1024). The three sums over cells run over chunks of B consecutive cells in ascending cell index from +0.0, the chunk
+ * partials are added in ascending chunk index: the order depends on nothing else.
+ * im_dod_max_cells: the largest w * h of a pair (2^24). im_dod_max_batch_cells: the most cells the pairs of one call hold together
+ * (2^26); they also hold fewer than 2^31 points (a cloud counts once per pair it is part of); E and P are at most 65535.
+ * im_dod_bounds: d_bounds [E][4] float64 = min_x, min_y, max_x, max_y of every cloud's kept points (+inf, +inf, -inf, -inf without one;
+ * of zeros of either sign the minimum is -0.0 and the maximum +0.0), d_dropped [E] int64 = its ignored points.
+ * im_dod_keys: h_bounds [E][4] = d_bounds downloaded; h_grids [P][4] float64 in HOST memory receives min_x, min_y, w, h of every pair;
+ * d_key [items] int64, items = the points of all pairs' clouds in the order pair, side, point: the segment of each (a dropped point:
+ * the number of segments, 2 * sum of w * h); d_key may be NULL: the grids alone, nothing is launched. The caller sorts the keys (stable) and hands the sorted keys and the permutation on.
+ * im_dod_reduce: d_H, may be NULL: the rasters [h][w] float64 of the pairs one behind the other; d_report [P][16] float64 = volume,
+ * addedVolume, removedVolume, surface, matchingPercent, groundNonMatchingPercent, ceilNonMatchingPercent, averageNeighborsPerCell,
+ * validCells, cellCount, gridWidth, gridHeight, min_x, min_y, step, step * step. With a = step * step: volume = a * sum H, added =
+ * a * sum of H > 0, removed = a * (0 - sum of H < 0), surface = a * validCells, the percents (100 * count) / cellCount with cellCount the
+ * cells either cloud fills, averageNeighborsPerCell = (valid cells among the 8 in-grid neighbours, summed over valid cells) /
+ * validCells. Without a valid cell the first nine are +0.0.
+ * im_crop_polygon: d_mask [n] uint8 = 1 where point (p[axis_x], p[axis_y]) is inside (inside != 0) or outside the closed polygon h_poly
+ * [n_verts][2] float64 in HOST memory, by the even-odd rule: for every edge (x0, y0) -> (x1, y1), from the last vertex to the first and
+ * then in order, toggle if (y0 > y) != (y1 > y) and x < (x1 - x0) * (y - y0) / (y1 - y0) + x0; a non-finite coordinate is not
+ * inside. d_index [n] int64 receives the kept indices in ascending order, d_count [1] int64 their number.
+ * The calls wait for the upload of their tables, then enqueue. All return -76, without launching, for a null required pointer, a step
+ * that is not finite or not > 0, vert_dim outside 0..2, a pair naming a cloud outside 0..E-1, offsets that do not start at 0 or
+ * descend (a negative count), a NaN bound, a pair whose w * h exceeds im_dod_max_cells(), a batch over the limits above; the crop for
+ * axes that are not two of 0..2, n outside 0..2^31-1, n_verts outside 3..1024, a non-finite vertex. P == 0 returns 0 and launches nothing. */
+int im_dod_chunk(void);
+int im_dod_max_cells(void);
+int im_dod_max_batch_cells(void);
+int im_dod_bounds(im_ctx* ctx, const double* d_pts, const long long* h_offsets, int n_clouds, int vert_dim, double* d_bounds, long long* d_dropped,
+                  void* stream);
+int im_dod_keys(im_ctx* ctx, const double* d_pts, const long long* h_offsets, int n_clouds, const int32_t* h_pairs, int n_pairs, int vert_dim,
+                double step, const double* h_bounds, double* h_grids, long long* d_key, void* stream);
+int im_dod_reduce(im_ctx* ctx, const double* d_pts, const long long* h_offsets, int n_clouds, const int32_t* h_pairs, int n_pairs, int vert_dim,
+                  double step, const double* h_bounds, const long long* d_sorted_keys, const long long* d_perm, double* d_H, double* d_report,
+                  void* stream);
+int im_crop_polygon(im_ctx* ctx, const double* d_pts, long long n, int axis_x, int axis_y, const double* h_poly, int n_verts, int inside,
+                    unsigned char* d_mask, long long* d_index, long long* d_count, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
