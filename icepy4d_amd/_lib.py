@@ -72,6 +72,7 @@ SIGNATURES = {
     "im_conv3x3": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
     "im_conv3x3_winograd": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
     "im_flash_attn": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _P],
+    "im_block_proj_attn": [_P, _I, _P, _P, _P, _P, _P, _F, _P, _P, _I, _I, _P, _P, _P, _P, _P, _F, _P],
     "im_nms": [_P, _P, _P, _I, _I, _I, _I, _P],
     "im_select_topk": [_P, _P, _I, _I, _I, _I, _F, _I, _P, _P, _P, _P],
     "im_sample_descriptors": [_P, _P, _I, _I, _I, _P, _P, _P, _P],

@@ -6,21 +6,28 @@
 
 namespace im {
 
-int launch_block_proj(im_ctx* ctx, hipStream_t s, const char* name, const GemmArgs& g, const float* wp_layers, int layer) {
+int launch_block_proj(im_ctx* ctx, hipStream_t s, const char* name, const GemmArgs& g, const float* wp_layers, int layer, const AttnArgs& at,
+                      bool* planes_done) {
+    *planes_done = false;
     if (env_is_1("IM_PROJ_TILED")) {
         IM_LAUNCH(ctx, name, s, launch_gemm(g, s));
         return 0;
     }
     GemmArgs r = g;
     r.wp = reinterpret_cast<const unsigned char*>(wp_layers) + (size_t)layer * g.N * 256 * 6;   // three bf16 planes: 6 bytes per weight
-    IM_LAUNCH(ctx, name, s, launch_proj_rows(r, s));
+    if (env_is_1("IM_PROJ_ROWS32") || !at.planes || attn_f32_form(at)) {
+        IM_LAUNCH(ctx, name, s, launch_proj_rows(r, s));
+        return 0;
+    }
+    IM_LAUNCH(ctx, name, s, launch_proj_planes(r, at.planes, s));
+    *planes_done = true;
     return 0;
 }
 
-int launch_block_tail(im_ctx* ctx, hipStream_t s, const AttnArgs& at, const BlockFfn& f, const GemmArgs& base, float* x) {
+int launch_block_tail(im_ctx* ctx, hipStream_t s, const AttnArgs& at, bool planes_done, const BlockFfn& f, const GemmArgs& base, float* x) {
     Workspace* ws = ctx->ws;
     const long xb = (long)base.m_max * 256, hb = (long)base.m_max * 512;
-    IM_LAUNCH(ctx, "attn_kv_planes", s, launch_attn_planes(at, s));
+    if (!planes_done) IM_LAUNCH(ctx, "attn_kv_planes", s, launch_attn_planes(at, s));
     IM_LAUNCH(ctx, at.cross ? "flash_attn_cross" : "flash_attn_self", s, launch_flash_attn(at, s));
     // A/B switch: IM_FFN_UNFUSED=1 keeps the launch-per-layer form
     static const bool unfused = env_is_1("IM_FFN_UNFUSED");

@@ -1,6 +1,7 @@
 // extern "C" boundary of libicematch (see include/icematch.h): context, workspace (im_ctx_reserve), profiler, debug reads / clock probe
 // and the stage entry points. The model forwards live in superpoint.hip / lightglue.hip / superglue.hip, weights in weights.hip,
 // the IM_DEBUG_GUARDS entry points in guards.hip.
+#include "block.h"
 #include "ctx.h"
 #include "lg_misc.h"
 #include "sp_post.h"
@@ -335,6 +336,40 @@ int im_flash_attn(im_ctx* ctx, const float* d_q, const float* d_k, const float* 
     IM_HIP(ctx, launch_attn_planes(a, (hipStream_t)stream));
     IM_HIP(ctx, launch_flash_attn(a, (hipStream_t)stream));
     IM_GUARD_CHECK(ctx, (hipStream_t)stream, "im_flash_attn");
+    return 0;
+}
+
+int im_block_proj_attn(im_ctx* ctx, int cross, const float* d_x, const float* h_w, const float* h_bias, const float* d_cs, const float* d_sn, float alpha,
+                       const int32_t* d_n, const int32_t* d_active, int n_pairs, int n_max, float* d_q, float* d_k, float* d_v, void* d_planes,
+                       float* d_att, float scale, void* stream) {
+    IM_CHECK_CTX(ctx);
+    if (n_pairs < 1 || n_max < 1 || !d_x || !h_w || !h_bias || !d_q || !d_k || !d_v || !d_planes) return ctx->fail(-12, "im_block_proj_attn: bad arguments");
+    const int N = cross ? 512 : 768, NI = 2 * n_pairs;
+    const std::vector<float> packed = pack_frag_weights(h_w, N, 256);
+    const size_t sizes[3] = {(size_t)N * 256, packed.size(), (size_t)N};
+    const float* src[3] = {h_w, packed.data(), h_bias};
+    hipStream_t st = (hipStream_t)stream;
+    int rc = 0;
+    IM_HIP(ctx, with_uploads(src, sizes, st, [&](float* const* d) {
+        GemmArgs g;       // as lg_block builds them (lightglue.hip)
+        g.m_max = n_max; g.m_ptr = d_n; g.active = d_active; g.pstride = 2; g.batch = NI; g.bx = 1; g.big_tile = NI >= 4;
+        g.A = d_x; g.a_bstride = (long)n_max * 256; g.lda = 256; g.ldw = 256; g.K = 256; g.W = d[0]; g.bias = d[2]; g.N = N;
+        g.q = d_q; g.v = d_v; g.head_bstride = (long)n_max * 256; g.head_stride = (long)n_max * 64;
+        if (!cross) { g.epi = EPI_QKV_ROPE; g.k = d_k; g.cs = d_cs; g.sn = d_sn; g.enc_bstride = (long)n_max * 32; }
+        else { g.epi = EPI_HEADS_QV; g.alpha = alpha; }
+        AttnArgs at;
+        at.q = d_q; at.k = cross ? d_q : d_k; at.v = d_v; at.hstride = (long)n_max * 64; at.bstride = (long)n_max * 256;
+        at.out = d_att; at.out_bstride = (long)n_max * 256; at.ldo = 256; at.n_ptr = d_n; at.pstride = 2; at.n_max = n_max; at.batch = NI; at.heads = 4;
+        at.cross = cross ? 1 : 0; at.active = d_active; at.planes = d_planes; at.scale = scale;
+        bool planes_done = false;
+        rc = launch_block_proj(ctx, st, "block_proj", g, d[1], 0, at, &planes_done);
+        if (rc) return hipSuccess;
+        if (!planes_done)
+            if (hipError_t e = launch_attn_planes(at, st); e != hipSuccess) return e;
+        return d_att ? launch_flash_attn(at, st) : hipSuccess;
+    }));
+    if (rc) return rc;
+    IM_GUARD_CHECK(ctx, st, "im_block_proj_attn");
     return 0;
 }
 

@@ -16,6 +16,7 @@
 #include "bf16x3.h"
 #include "common.h"
 #include "kernels.h"
+#include "proj_rows.h"
 
 namespace im {
 
@@ -272,13 +273,7 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel(GemmArgs a) {
 // weights), one barrier per block. Wave w owns the column tiles w, w + 8, (w + 16): one of q / k / v each, sixteen steps of six MFMAs per tile, then that tile's
 // epilogue (the tiled kernel's, statement for statement: bias, rotary on q / k, head-major stores). The products and their order per accumulator are those of
 // the tiled kernel (x planes as A, W planes as B, k ascending, h l | l h | m m | h m | m h | h h): bit-identical outputs (profiles/r06_proj_rows.txt).
-namespace pr {
-constexpr int BM = 32, NT = 512;
-constexpr int PS = 528;              // bytes per row of a plane: 256 x 2 + 16 (132 dwords = 4 mod 64: conflict-free 16-byte row reads)
-constexpr int PLANE = BM * PS;       // 16,896
-constexpr int LDS_BYTES = 3 * PLANE; // 50,688
-constexpr unsigned TILE_BYTES = (256 / 16) * 3 * 1024;   // one packed 32-column tile at K = 256: 16 k chunks x 3 planes x 1 KiB
-}  // namespace pr
+// (proj_rows.h: the LDS layout, the weight fragment ring PR_LOAD and the six products PR_SIX, shared with proj_planes.hip)
 
 #ifdef IM_PSTAMP   // diagnostic build only (tools/proj_stamps.py): shader-clock stamps of wave 0 of every block, never read by the kernel
 __device__ unsigned long long g_pstamp[4096 * 16];
@@ -307,16 +302,8 @@ __global__ __launch_bounds__(pr::NT, 4) void proj_rows_kernel(GemmArgs a) {
     const __amdgpu_buffer_rsrc_t rW = make_rsrc(a.wp, (unsigned)a.N * 256u * 6u);
 
     P_STAMP(0)
-    // weight steps (one 16-deep k chunk of one column tile = three 1 KB loads) run THREE steps ahead through four register buffers: the step index s = 16 j + kc
-    // walks this wave's tiles j * 8 + wave; steps past the last tile are out of the descriptor's range by their lane offset (zeros, no traffic, no branch)
+    // weight steps run THREE steps ahead through four register buffers (proj_rows.h PR_LOAD)
     u32x4 b0[3], b1[3], b2[3], b3[3];
-#define PR_LOAD(b_, s_)                                                                                                          \
-    {                                                                                                                            \
-        const bool in_ = (s_) < TILES * 16;                                                                                      \
-        const unsigned so_ = in_ ? (unsigned)((((s_) >> 4) * 8 + wave)) * TILE_BYTES + (unsigned)(((s_) & 15) * 3) * 1024u : 0u;   \
-        const unsigned vo_ = in_ ? lane * 16u : 0x80000000u;    /* out of range by the LANE offset: a scalar offset beyond num_records would wrap the range check */ \
-        _Pragma("unroll") for (int g = 0; g < 3; ++g) b_[g] = __builtin_amdgcn_raw_buffer_load_b128(rW, vo_, so_ + (unsigned)g * 1024u, 0); \
-    }
     PR_LOAD(b0, 0)
     PR_LOAD(b1, 1)
     PR_LOAD(b2, 2)
@@ -342,19 +329,6 @@ __global__ __launch_bounds__(pr::NT, 4) void proj_rows_kernel(GemmArgs a) {
     __syncthreads();
     P_STAMP(1)
 
-    // the products are bf16x3.h's six(), spelled out: as a call two register quads of this kernel swap names (not yet A/B-timed)
-#define PR_SIX(b_, kc_)                                                                                              \
-    {                                                                                                                \
-        const unsigned char* ap = psm + c * PS + ((kc_) * 16 + hh * 8) * 2;                                          \
-        const u32x4 ah = *reinterpret_cast<const u32x4*>(ap), am = *reinterpret_cast<const u32x4*>(ap + PLANE),   \
-                     al = *reinterpret_cast<const u32x4*>(ap + 2 * PLANE);                                          \
-        acc = mfma_bf(ah, b_[2], acc);                                                                              \
-        acc = mfma_bf(al, b_[0], acc);                                                                              \
-        acc = mfma_bf(am, b_[1], acc);                                                                              \
-        acc = mfma_bf(ah, b_[1], acc);                                                                              \
-        acc = mfma_bf(am, b_[0], acc);                                                                              \
-        acc = mfma_bf(ah, b_[0], acc);                                                                              \
-    }
 #pragma unroll 1
     for (int j = 0; j < TILES; ++j) {
         const int tile = j * 8 + wave;                       // wave-uniform: columns [32 tile, 32 tile + 32)
@@ -367,19 +341,19 @@ __global__ __launch_bounds__(pr::NT, 4) void proj_rows_kernel(GemmArgs a) {
             // a scheduling fence per step: left alone the machine scheduler sinks every load to its use (one step of latency hiding instead of three)
             PR_LOAD(b3, s_ + 3)
             __builtin_amdgcn_sched_barrier(0);
-            PR_SIX(b0, kc)
+            PR_SIX(acc, psm, b0, kc)
             __builtin_amdgcn_sched_barrier(0);
             PR_LOAD(b0, s_ + 4)
             __builtin_amdgcn_sched_barrier(0);
-            PR_SIX(b1, kc + 1)
+            PR_SIX(acc, psm, b1, kc + 1)
             __builtin_amdgcn_sched_barrier(0);
             PR_LOAD(b1, s_ + 5)
             __builtin_amdgcn_sched_barrier(0);
-            PR_SIX(b2, kc + 2)
+            PR_SIX(acc, psm, b2, kc + 2)
             __builtin_amdgcn_sched_barrier(0);
             PR_LOAD(b2, s_ + 6)
             __builtin_amdgcn_sched_barrier(0);
-            PR_SIX(b3, kc + 3)
+            PR_SIX(acc, psm, b3, kc + 3)
             __builtin_amdgcn_sched_barrier(0);
         }
         P_STAMP(2 + 2 * j)
@@ -420,8 +394,6 @@ __global__ __launch_bounds__(pr::NT, 4) void proj_rows_kernel(GemmArgs a) {
         }
         P_STAMP(3 + 2 * j)
     }
-#undef PR_LOAD
-#undef PR_SIX
 }
 
 template <int EPI, int TILES>

@@ -111,6 +111,9 @@ struct GemmArgs {
 };
 hipError_t launch_gemm(const GemmArgs& a, hipStream_t s);
 hipError_t launch_proj_rows(const GemmArgs& a, hipStream_t s);   // gemm.hip: the K = 256 projections of a LightGlue block as row blocks (same bits as launch_gemm with bx)
+// proj_planes.hip: the same projections as 64-row blocks; q as fp32 (same bits), k and v (EPI_HEADS_QV: the scaled qk and v) NOT as fp32 but as the bf16 planes
+// of the attention launch that follows (AttnArgs::planes for n_max = a.m_max, batch = a.batch, 4 heads: what launch_attn_planes would write, same bits)
+hipError_t launch_proj_planes(const GemmArgs& a, void* planes, hipStream_t s);
 
 // ------------------------------------------------------------------ ffn_fused.hip
 struct FfnArgs {

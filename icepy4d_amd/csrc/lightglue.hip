@@ -21,18 +21,19 @@ static int lg_block(im_ctx* ctx, hipStream_t s, int NI, int layer, bool cross, f
     at.q = ws->q; at.k = cross ? ws->q : ws->k; at.v = ws->v; at.hstride = (long)K * 64; at.bstride = (long)K * 256;
     at.out = ws->att; at.out_bstride = xb; at.ldo = 256; at.n_ptr = n_ptr; at.pstride = ST_INTS; at.n_max = K; at.batch = NI; at.heads = 4;
     at.cross = cross ? 1 : 0; at.active = active; at.part = ws->attn_part; at.counters = ws->attn_cnt; at.planes = ws->attn_planes; at.clock = ctx->clock_of(0);
+    bool planes_done = false;
     GemmArgs g = base;
     g.A = x; g.a_bstride = xb; g.lda = 256; g.ldw = 256; g.K = 256;
     g.q = ws->q; g.v = ws->v; g.head_bstride = (long)K * 256; g.head_stride = (long)K * 64; g.big_tile = NI >= 4;
     if (!cross) {
         g.W = W.qkv_w + (long)layer * 768 * 256; g.bias = W.qkv_b + (long)layer * 768; g.N = 768; g.epi = EPI_QKV_ROPE;
         g.k = ws->k; g.cs = cs; g.sn = sn; g.enc_bstride = (long)K * 32;
-        if (int rc = launch_block_proj(ctx, s, "lg_qkv_rope_gemm", g, W.qkv_wp, layer)) return rc;
+        if (int rc = launch_block_proj(ctx, s, "lg_qkv_rope_gemm", g, W.qkv_wp, layer, at, &planes_done)) return rc;
         at.scale = 0.125f;  // SDPA default 1/sqrt(64) (`lightglue.py:120-123`)
     } else {   // [to_qk ; to_v]
         g.W = W.cqv_w + (long)layer * 512 * 256; g.bias = W.cqv_b + (long)layer * 512; g.N = 512; g.epi = EPI_HEADS_QV;
         g.alpha = (float)0.35355339059327373;  // scale**0.5 = 64**-0.25 on to_qk (`lightglue.py:201`); to_v unscaled
-        if (int rc = launch_block_proj(ctx, s, "lg_proj_gemm", g, W.cqv_wp, layer)) return rc;
+        if (int rc = launch_block_proj(ctx, s, "lg_proj_gemm", g, W.cqv_wp, layer, at, &planes_done)) return rc;
         at.scale = 1.f;
     }
     // ffn.0 on cat([x, att]) (out_proj / to_out folded into the weights), LayerNorm, GELU, ffn.3, residual
@@ -42,7 +43,7 @@ static int lg_block(im_ctx* ctx, hipStream_t s, int NI, int layer, bool cross, f
     f.ln_g = F.ln_g + (long)layer * 512; f.ln_b = F.ln_b + (long)layer * 512;
     f.w3 = F.w3 + (long)layer * 256 * 512; f.w3p = F.w3p + (long)layer * 256 * 512 * 3 / 2; f.b3 = F.b3 + (long)layer * 256;
     f.name_fused = "lg_ffn_fused"; f.name_ffn0 = "lg_ffn0_gemm"; f.name_ffn3 = "lg_ffn3_gemm";
-    return launch_block_tail(ctx, s, at, f, base, x);
+    return launch_block_tail(ctx, s, at, planes_done, f, base, x);
 }
 
 static int lightglue_forward(im_ctx* ctx, int n_pairs, const float* d_kpts, const float* d_desc, const int32_t* d_n, const float* h_size,

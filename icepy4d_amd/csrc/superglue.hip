@@ -508,20 +508,21 @@ int im_superglue_forward(im_ctx* ctx, const float* d_kpts, const float* d_scores
         g.A = x; g.a_bstride = xb; g.lda = 256; g.W = W.proj_w + (long)l * 768 * 256; g.ldw = 256;
         g.bias = W.proj_b + (long)l * 768; g.N = 768; g.K = 256; g.epi = EPI_QKV_ROPE;  // no rotary tables => plain q/k/v
         g.q = ws->q; g.k = ws->k; g.v = ws->v; g.head_bstride = (long)K * 256; g.head_stride = (long)K * 64;
-        if (int rc = launch_block_proj(ctx, s, "sg_qkv_gemm", g, W.proj_wp, l)) return rc;
         AttnArgs at;
         at.q = ws->q; at.k = ws->k; at.v = ws->v; at.hstride = (long)K * 64; at.bstride = (long)K * 256;
         at.out = ws->att; at.out_bstride = xb; at.ldo = 256; at.n_ptr = st->n; at.n_max = K; at.batch = 2; at.heads = 4;
         at.cross = l & 1;  // ['self', 'cross'] * 9 (`superglue.py:215`)
         at.scale = 0.125f;  // / dim ** .5, dim = 64 (`superglue.py:91`)
         at.part = ws->attn_part; at.counters = ws->attn_cnt; at.planes = ws->attn_planes; at.clock = ctx->clock_of(0);
+        bool planes_done = false;
+        if (int rc = launch_block_proj(ctx, s, "sg_qkv_gemm", g, W.proj_wp, l, at, &planes_done)) return rc;
         // x += mlp.3(relu(bn(mlp.0([x | att])))) with merge and BatchNorm folded into mlp.0 (weights.hip)
         BlockFfn f;
         f.act = 1;
         f.w0 = W.mlp0_w + (long)l * 512 * 512; f.w0p = W.mlp0_wp + (long)l * 512 * 512 * 3 / 2; f.b0 = W.mlp0_b + (long)l * 512;
         f.w3 = W.mlp3_w + (long)l * 256 * 512; f.w3p = W.mlp3_wp + (long)l * 256 * 512 * 3 / 2; f.b3 = W.mlp3_b + (long)l * 256;
         f.name_fused = "sg_mlp_fused"; f.name_ffn0 = "sg_mlp0_gemm"; f.name_ffn3 = "sg_mlp3_gemm";
-        if (int rc = launch_block_tail(ctx, s, at, f, base, x)) return rc;
+        if (int rc = launch_block_tail(ctx, s, at, planes_done, f, base, x)) return rc;
     }
     {
         GemmArgs g = base;

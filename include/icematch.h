@@ -170,6 +170,17 @@ int im_conv3x3_winograd(im_ctx* ctx, const float* d_in, const float* h_weight, c
  * (the form for callers without the plane workspace) instead of reading the planes of its first launch */
 int im_flash_attn(im_ctx* ctx, const float* d_q, const float* d_k, const float* d_v, float* d_out,
                   const int32_t* d_n, int n_max, int batch, int heads, int cross, float scale, void* stream);
+/* The head of one LightGlue block as the forward pass launches it: the K = 256 projection of d_x [2 n_pairs][n_max][256], the K / V planes of the
+ * attention, and - d_att not NULL - the attention into d_att [2 n_pairs][n_max][256]. cross 0: h_w [768][256] = Wqkv, rotary with d_cs / d_sn
+ * [2 n_pairs][n_max][32] (NULL: none), q / k / v; cross 1: h_w [512][256] = [to_qk ; to_v], d_q = alpha * qk (query of its own image, key of the
+ * other one), d_v. d_q / d_k / d_v: [2 n_pairs][4][n_max][64] fp32; d_planes: 2 * 2 n_pairs * 4 * n_max * 384 bytes,
+ * [K | V][image][head][row][3 planes][64] bf16. By default the projection writes q and the planes and leaves d_k (and d_v) alone; with
+ * IM_PROJ_ROWS32=1 / IM_PROJ_TILED=1 it writes fp32 q / k / v and a pass of its own cuts the planes: same bits. d_n [n_pairs][2]: live rows per
+ * image; d_active (NULL: all) [n_pairs][2]: a pair whose first int is 0 is skipped. Rows at or past the live count are never written. Weights
+ * on the HOST (packed + uploaded inside; synchronises). */
+int im_block_proj_attn(im_ctx* ctx, int cross, const float* d_x, const float* h_w, const float* h_bias, const float* d_cs, const float* d_sn,
+                       float alpha, const int32_t* d_n, const int32_t* d_active, int n_pairs, int n_max, float* d_q, float* d_k, float* d_v,
+                       void* d_planes, float* d_att, float scale, void* stream);
 /* `simple_nms` (`lightglue/superpoint.py:50-65`): d_scores, d_out [n_images][h][w] */
 int im_nms(im_ctx* ctx, const float* d_scores, float* d_out, int n_images, int h, int w, int radius, void* stream);
 /* border / threshold / row-major compaction / top-k (`lightglue/superpoint.py:177-200`) on an NMS map */
