@@ -102,6 +102,7 @@ SIGNATURES = {
     "im_knn_cells": [_P, _P, _L, _P, _I, _I, _I, _P, _P],
     "im_knn_cell_ranges": [_P, _P, _L, _L, _P, _P],
     "im_knn_self": [_P, _P, _P, _P, _L, _P, _I, _I, _I, _I, _D, _P, _P, _P, _P, _P, _P, _P],
+    "im_ball_features": [_P, _P, _P, _P, _L, _P, _I, _I, _I, _D, _P, _I, _P, _P, _P, _P, _P, _P, _P],
     "im_dod_chunk": [],
     "im_dod_max_cells": [],
     "im_dod_max_batch_cells": [],

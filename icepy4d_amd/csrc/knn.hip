@@ -7,7 +7,8 @@
 //   knn_cells_kernel    one thread per point: the key (iz * ny + iy) * nx + ix of its cell in a uniform grid (knn_point.h)
 //   knn_ranges_kernel   one thread per cell: the first position of the cell in the key-sorted order (binary search; the stable sort by
 //                       key between the two is torch's, plumbing)
-//   knn_gather_kernel   the cloud in cell order as three coordinate planes plus the original indices (scratch of the context)
+//   knn_gather_kernel   (knn_sorted.h, shared with ballfeat.hip) the cloud in cell order as three coordinate planes plus the original
+//                       indices (scratch of the context)
 //   knn_self_kernel     one wave per query, queries in cell order so that neighbouring waves read the same cells. The wave visits the
 //                       query's cell, then the shells of cells at Chebyshev ring 1, 2, ... clipped to the grid; a shell is walked as its six
 //                       faces (only those inside the grid), inside a face every run of cells along x is one contiguous range of the
@@ -24,14 +25,10 @@
 #include "common.h"
 #include "ctx.h"
 #include "stage_scratch.h"
-#include "knn_point.h"
+#include "knn_sorted.h"
 
 namespace im {
 namespace {
-
-constexpr long long KNN_MAX_CELLS = 1LL << 24;
-constexpr int KNN_WAVES = 4;          // waves (queries) per block
-constexpr int KNN_MIN_STEPS = 1024;   // steps (64 rows looked up, or 64 candidates read) every ring search may take, whatever the cloud's size
 
 __global__ __launch_bounds__(256) void knn_cells_kernel(KnnGrid g, const double* __restrict__ pts, long long n, long long* __restrict__ key) {
     const long long i = blockIdx.x * 256LL + threadIdx.x;
@@ -52,18 +49,6 @@ __global__ __launch_bounds__(256) void knn_ranges_kernel(const long long* __rest
         if (skey[mid] < c) lo = mid + 1; else hi = mid;
     }
     start[c] = (int)lo;
-}
-
-struct KnnSorted { double* x; double* y; double* z; int* idx; };
-
-// an index outside the cloud (a permutation that is none) is clamped: the result is then meaningless, but every access stays inside
-__global__ __launch_bounds__(256) void knn_gather_kernel(const double* __restrict__ pts, const long long* __restrict__ perm, long long n, KnnSorted s) {
-    const long long j = blockIdx.x * 256LL + threadIdx.x;
-    if (j >= n) return;
-    long long i = perm[j];
-    i = i < 0 ? 0 : (i >= n ? n - 1 : i);
-    s.x[j] = pts[3 * i]; s.y[j] = pts[3 * i + 1]; s.z[j] = pts[3 * i + 2];
-    s.idx[j] = (int)i;
 }
 
 struct KnnArgs {
@@ -112,15 +97,6 @@ __device__ __forceinline__ void knn_scan(const KnnArgs& a, KnnList& L, int lane,
     }
 }
 
-// the sorted positions [b, e) of the cells ix0..ix1 of row (iy, iz): one contiguous range of the sorted cloud
-__device__ __forceinline__ void knn_row_range(const KnnArgs& a, int ix0, int ix1, int iy, int iz, int& b, int& e) {
-    const long long k0 = knn_key(a.g, ix0, iy, iz), k1 = knn_key(a.g, ix1, iy, iz) + 1;
-    b = a.start[k0];
-    e = a.start[k1];
-    b = b < 0 ? 0 : b;
-    e = e > a.n ? a.n : e;          // offsets that are none read nothing outside the cloud
-}
-
 // One strip of a shell: the rows (iy, iz) with iy in ya..yb and iz in za..zb, of each the cells xa..xb (one contiguous range of the
 // sorted cloud). 64 rows per step, one per lane: every lane looks its range up, a ballot keeps the ranges that hold points, and those are
 // scanned one after the other. An empty strip (ya > yb or za > zb) costs nothing. Returns the steps taken, the measure of the search's work.
@@ -132,7 +108,7 @@ __device__ __forceinline__ int knn_strip(const KnnArgs& a, KnnList& L, int lane,
     for (int base = 0; base < rows; base += IM_WAVE) {
         const int row = base + lane;
         int b = 0, e = 0;
-        if (row < rows) knn_row_range(a, xa, xb, ya + row % wy, za + row / wy, b, e);
+        if (row < rows) knn_row_range(a.g, a.start, a.n, xa, xb, ya + row % wy, za + row / wy, b, e);
         unsigned long long m = __ballot(e > b);
         ++steps;
         while (m) {
@@ -145,10 +121,6 @@ __device__ __forceinline__ int knn_strip(const KnnArgs& a, KnnList& L, int lane,
     }
     return steps;
 }
-
-// The steps a ring search may take before it is given up for one scan of the whole cloud, which takes n / 64 of them: a query far from
-// everything (the lone outlier of a cloud whose grid is long and thin, a line of 2^24 cells) would otherwise walk up to 2^24 empty rings.
-__device__ __forceinline__ long long knn_step_budget(int n) { return KNN_MIN_STEPS + n / (IM_WAVE / 2); }
 
 __global__ __launch_bounds__(IM_WAVE * KNN_WAVES) void knn_self_kernel(KnnArgs a) {
     const int lane = threadIdx.x & (IM_WAVE - 1);
@@ -207,21 +179,6 @@ __global__ __launch_bounds__(IM_WAVE * KNN_WAVES) void knn_self_kernel(KnnArgs a
         knn_normal([&](int j, double& x, double& y, double& z) { x = __shfl(px, j); y = __shfl(py, j); z = __shfl(pz, j); }, count, nrm);
         if (lane == 0) { a.normal[3LL * qi] = nrm[0]; a.normal[3LL * qi + 1] = nrm[1]; a.normal[3LL * qi + 2] = nrm[2]; }
     }
-}
-
-// what the three entry points refuse about the grid; nullptr when it is fine
-const char* bad_grid(const double* h_grid, int nx, int ny, int nz, KnnGrid& g) {
-    if (!h_grid) return "null grid";
-    const double s = h_grid[3];
-    if (!(s > 0.0) || std::isinf(s)) return "the cell size must be finite and positive";
-    for (int a = 0; a < 3; ++a)
-        if (!std::isfinite(h_grid[a])) return "the origin must be finite";
-    if (nx < 1 || ny < 1 || nz < 1) return "a grid dimension is below 1";
-    if ((long long)nx * ny > KNN_MAX_CELLS || (long long)nx * ny * nz > KNN_MAX_CELLS) return "more cells than im_knn_max_cells()";
-    g.o[0] = h_grid[0]; g.o[1] = h_grid[1]; g.o[2] = h_grid[2];
-    g.s = s;
-    g.n[0] = nx; g.n[1] = ny; g.n[2] = nz;
-    return nullptr;
 }
 
 static_assert(IM_WAVE * KNN_WAVES == 256, "knn_self_kernel takes the block of the file's other kernels: 256 threads");

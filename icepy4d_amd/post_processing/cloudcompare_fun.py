@@ -1,7 +1,12 @@
 """`DemOfDifference` with the reference's names (`src/icepy4d/post_processing/cloudcompare_fun.py`), on the device: the reference goes
 through CloudComPy (`cc.ComputeVolume25D`), which is not a dependency; the 2.5D volume has a definition of its own here
 (`icepy4d_amd/volume_variations.py`, DESIGN §4, csrc/dod.hip). PARITY WITH A CLOUDCOMPARE BINARY IS UNPINNED. A series of pairs is served
-faster by `volume_variations.dod_series`, which uploads every cloud once."""
+faster by `volume_variations.dod_series`, which uploads every cloud once.
+
+`GeomFeature`, `compute_feature` and `filter_by_sf_value` stand in for CloudComPy's `GeomFeature`, `computeFeature` and `filterBySFValue`
+as `scripts/pcd_postprocessing/top_border.py` uses them (`icepy4d_amd/top_border.py`); the features are those of
+`utils/point_cloud_filters.ball_features` (csrc/ballfeat.hip), with the same caveat about a CloudCompare binary."""
+import enum
 from pathlib import Path
 from typing import Union
 
@@ -13,6 +18,41 @@ from .open3d_fun import crop_indices, read_polyline, select_by_index
 
 ALLOWED_PCD_EXT = [".asc", ".las", ".E57", ".ply", ".pcd", ".bin"]
 HEADER = "pcd0,pcd1,volume,addedVolume,removedVolume,surface,matchingPercent,averageNeighborsPerCell\n"
+
+
+class GeomFeature(enum.Enum):
+    """CloudCompare's geometric features by its member names (the numbering is CCCoreLib's as recalled, from 1; nothing here depends on
+    it). `NumberOfNeighbors` is CloudCompare's neighbour count at the same radius, listed with them."""
+    EigenValuesSum = 1
+    Omnivariance = 2
+    EigenEntropy = 3
+    Anisotropy = 4
+    Planarity = 5
+    Linearity = 6
+    PCA1 = 7
+    PCA2 = 8
+    SurfaceVariation = 9
+    Sphericity = 10
+    Verticality = 11
+    EigenValue1 = 12
+    EigenValue2 = 13
+    EigenValue3 = 14
+    NumberOfNeighbors = 15
+
+
+def compute_feature(feature, radius: float, pcd, engine=None) -> np.ndarray:
+    """One feature ([n] float64, NaN where the ball defines none) of every point of `pcd` (a `.ply` path, a `core.PointCloud` or an
+    [n, 3] array) over the ball of `radius`, on the device. `feature`: a `GeomFeature` or its name."""
+    from ..utils.point_cloud_filters import ball_features
+    name = feature.name if isinstance(feature, GeomFeature) else GeomFeature[str(feature)].name
+    return ball_features(_as_cloud(pcd).points, radius, features=(name,), engine=engine)[name]
+
+
+def filter_by_sf_value(values, lo: float, hi: float) -> np.ndarray:
+    """The ascending indices (int64) of the values with lo <= v <= hi; NaN is dropped, as is everything when a limit is NaN."""
+    v = np.asarray(values, np.float64).reshape(-1)
+    with np.errstate(invalid="ignore"):
+        return np.nonzero((v >= lo) & (v <= hi))[0].astype(np.int64)
 
 
 def _as_cloud(pcd) -> PointCloud:

@@ -19,7 +19,15 @@ PARITY WITH AN OPEN3D BINARY IS UNPINNED. Open3D is not a dependency; its publis
   - estimate_normals: the eigenvector of the smallest eigenvalue of the two-pass covariance of the neighbours with d2 <= radius^2, at most
     max_nn of them, by cyclic Jacobi; fewer than three neighbours give (0, 0, 1). Open3D's closed-form eigen solver and its sign are not
     reproduced: ours makes the first non-zero of (n_z, n_y, n_x) positive. What could differ: the sign, and the direction where two
-    eigenvalues nearly coincide."""
+    eigenvalues nearly coincide.
+
+`ball_features` (csrc/ballfeat.hip, `im_ball_features`) serves the reference's `scripts/pcd_postprocessing/top_border.py`, which asks
+CloudCompare for `computeFeature(Linearity, 2.0)` and `computeFeature(Verticality, 0.15)`: the eigen-decomposition of the covariance of ALL
+points within a radius of each point, hundreds to thousands of them, which the 64-slot list above cannot hold. CloudCompare is not a
+dependency and the features have a definition of their own: offsets quantised to r * 2^-18 and summed exactly in int64, so
+that the result is a function of the input alone, bit-identical to tests/ball_oracle.py for any cell size. PARITY WITH A CLOUDCOMPARE
+BINARY IS UNPINNED: what could differ is its float32 storage of coordinates, its eigen solver and, at the scale of the quantisation step
+(7.6 um at r = 2 m), which points lie in a ball."""
 import math
 
 import numpy as np
@@ -29,6 +37,11 @@ from .._lib import ptr
 from ..engine import default_engine, to_device
 
 MAX_K = 64
+MAX_BALL_POINTS = 2 ** 26
+# the kind codes of include/icematch.h (im_ball_kind), CloudCompare's member names
+BALL_KINDS = {"EigenValuesSum": 0, "PCA1": 1, "PCA2": 2, "SurfaceVariation": 3, "Linearity": 4, "Planarity": 5, "Anisotropy": 6,
+              "Sphericity": 7, "Verticality": 8, "EigenValue1": 9, "EigenValue2": 10, "EigenValue3": 11, "NumberOfNeighbors": 12}
+BALL_DERIVED = ("Omnivariance", "EigenEntropy")      # from `eig` with torch on the device: cbrt and log are not bit-pinned
 CELL_OCCUPANCY = 0.25      # tunable: the cell size is chosen so that an occupied cell holds about CELL_OCCUPANCY * k points
 
 
@@ -93,6 +106,27 @@ def choose_cell_size(eng, pts, lo, hi, k, occupancy=None):
     return s if (s > 0.0 and math.isfinite(s)) else ext
 
 
+def _bounds(pts):
+    return pts.min(0).values.cpu().numpy(), pts.max(0).values.cpu().numpy()
+
+
+def _binned(eng, pts, lo, hi, s):
+    """The cloud binned into the grid of cell size s (enlarged to fit the cell cap) over [lo, hi]: (s, dims, h_grid, perm, start), what
+    `im_knn_self` and `im_ball_features` take: keys by `im_knn_cells`, one stable sort, cell ranges by `im_knn_cell_ranges`."""
+    n, dev = pts.shape[0], pts.device
+    s = fit_cell_size(lo, hi, s, max_cells())
+    dims = grid_dims(lo, hi, s)
+    cells = dims[0] * dims[1] * dims[2]
+    st = eng.stream_ptr()
+    grid = np.array([lo[0], lo[1], lo[2], s], np.float64)
+    key = torch.empty(n, dtype=torch.int64, device=dev)
+    eng.ctx.call("im_knn_cells", ptr(pts), n, grid.ctypes.data, dims[0], dims[1], dims[2], ptr(key), st)
+    skey, perm = torch.sort(key, stable=True)
+    start = torch.empty(cells + 1, dtype=torch.int32, device=dev)
+    eng.ctx.call("im_knn_cell_ranges", ptr(skey), n, cells, ptr(start), st)
+    return s, dims, grid, perm, start
+
+
 def knn_self(points, k, radius=None, cell_size=None, want=("idx", "d2", "count"), occupancy=None, engine=None):
     """The primitive: {name: device tensor} for the names in `want` out of idx [n, k] int32, d2 [n, k] float64, count [n] int32, mean [n]
     float64 (SOR's statistic), normal [n, 3] float64, rings [n] int32 (rings of cells the search visited, the query's cell counted; negated where
@@ -118,18 +152,10 @@ def knn_self(points, k, radius=None, cell_size=None, want=("idx", "d2", "count")
     if n == 0:
         out["cell_size"], out["dims"] = 1.0 if cell_size is None else float(cell_size), [1, 1, 1]
         return out
-    lo, hi = pts.min(0).values.cpu().numpy(), pts.max(0).values.cpu().numpy()
+    lo, hi = _bounds(pts)
     s = choose_cell_size(eng, pts, lo, hi, k, occupancy) if cell_size is None else float(cell_size)
-    s = fit_cell_size(lo, hi, s, max_cells())
-    dims = grid_dims(lo, hi, s)
-    cells = dims[0] * dims[1] * dims[2]
+    s, dims, grid, perm, start = _binned(eng, pts, lo, hi, s)
     st = eng.stream_ptr()
-    grid = np.array([lo[0], lo[1], lo[2], s], np.float64)
-    key = torch.empty(n, dtype=torch.int64, device=dev)
-    eng.ctx.call("im_knn_cells", ptr(pts), n, grid.ctypes.data, dims[0], dims[1], dims[2], ptr(key), st)
-    skey, perm = torch.sort(key, stable=True)
-    start = torch.empty(cells + 1, dtype=torch.int32, device=dev)
-    eng.ctx.call("im_knn_cell_ranges", ptr(skey), n, cells, ptr(start), st)
     r2 = math.inf if radius is None else float(radius) * float(radius)
     eng.ctx.call("im_knn_self", ptr(pts), ptr(perm), ptr(start), n, grid.ctypes.data, dims[0], dims[1], dims[2], k, r2,
                  ptr(out.get("count")), ptr(out.get("idx")), ptr(out.get("d2")), ptr(out.get("mean")), ptr(out.get("normal")),
@@ -186,3 +212,63 @@ def estimate_normals(points, radius=1.0, max_nn=30, engine=None, cell_size=None)
     is a plain k-nearest search. See the module docstring for what is and is not Open3D's. numpy in, numpy out; tensor in, tensor out."""
     r = knn_self(points, int(max_nn), radius=radius, cell_size=cell_size, want=("normal",), engine=engine)
     return r["normal"] if isinstance(points, torch.Tensor) else r["normal"].cpu().numpy()
+
+
+def _cbrt(x):
+    """Cube root of x >= 0 (torch has none): pow with the rounded exponent 1 / 3, then one Newton step, which leaves about an ulp."""
+    y = torch.pow(x, 1.0 / 3.0)
+    return torch.where(y > 0.0, y - (y * y * y - x) / (3.0 * y * y), y)
+
+
+def ball_features(points, radius, features=("Linearity",), cell_size=None, engine=None, want=()):
+    """Geometric features of the ball of `radius` around every point (module docstring): {name: [n] float64} for the names in
+    `features` (CloudCompare's: the keys of BALL_KINDS, plus "Omnivariance" = cbrt(l1 l2 l3) and "EigenEntropy" = -sum l ln l, a zero term
+    counting 0), plus any of `want`: count [n] int32, sums [n, 10] int64, eig [n, 3] float64 (descending, m^2), normal [n, 3] float64,
+    steps [n] int32 (the query's work; negative where it scanned the whole cloud). A ball of fewer than three points or without extent gives
+    NaN. Several features of one radius cost one launch. `cell_size` (default radius / 2, enlarged to fit the cell cap) is a tunable: the
+    result does not depend on it. numpy in, numpy out; tensor in, tensors out."""
+    radius = float(radius)
+    if not (radius > 0.0 and math.isfinite(radius)) or radius * 2.0 ** -18 < 2.2250738585072014e-308:
+        raise ValueError(f"radius must be finite and positive, and radius * 2^-18 a normal number (got {radius})")
+    if cell_size is not None and not (float(cell_size) > 0.0 and math.isfinite(float(cell_size))):
+        raise ValueError(f"cell_size must be finite and positive (got {cell_size})")
+    features = (features,) if isinstance(features, str) else tuple(features)
+    unknown = [f for f in features if f not in BALL_KINDS and f not in BALL_DERIVED]
+    if unknown:
+        raise ValueError(f"unknown features {unknown}")
+    unknown = set(want) - {"count", "sums", "eig", "normal", "steps"}
+    if unknown:
+        raise ValueError(f"unknown outputs {sorted(unknown)}")
+    eng = default_engine(engine)
+    dev = eng.device
+    pts = _device_points(points, dev)
+    n = pts.shape[0]
+    if n > MAX_BALL_POINTS:
+        raise ValueError("at most 2^26 points")
+    kinds = sorted({BALL_KINDS[f] for f in features if f in BALL_KINDS})
+    derived = any(f in BALL_DERIVED for f in features)
+    shapes = {"count": ((n,), torch.int32), "sums": ((n, 10), torch.int64), "eig": ((n, 3), torch.float64), "normal": ((n, 3), torch.float64),
+              "steps": ((n,), torch.int32)}
+    raw = {name: torch.empty(shapes[name][0], dtype=shapes[name][1], device=dev) for name in set(want) | ({"eig"} if derived else set())}
+    feat = torch.empty((n, len(kinds)), dtype=torch.float64, device=dev) if kinds else None
+    if n > 0:
+        lo, hi = _bounds(pts)
+        _, dims, grid, perm, start = _binned(eng, pts, lo, hi, radius / 2.0 if cell_size is None else float(cell_size))
+        h_kinds = np.array(kinds, np.int32)
+        eng.ctx.call("im_ball_features", ptr(pts), ptr(perm), ptr(start), n, grid.ctypes.data, dims[0], dims[1], dims[2], radius,
+                     h_kinds.ctypes.data if kinds else None, len(kinds), ptr(raw.get("count")), ptr(raw.get("sums")), ptr(raw.get("eig")),
+                     ptr(raw.get("normal")), ptr(feat), ptr(raw.get("steps")), eng.stream_ptr())
+    out = {}
+    for f in features:
+        if f in BALL_KINDS:
+            out[f] = feat[:, kinds.index(BALL_KINDS[f])].contiguous()
+        elif f == "Omnivariance":
+            e = raw["eig"]
+            out[f] = _cbrt(e[:, 0] * e[:, 1] * e[:, 2])
+        else:
+            e = raw["eig"]
+            terms = torch.where(e == 0.0, torch.zeros_like(e), e * torch.log(e))
+            out[f] = -((terms[:, 0] + terms[:, 1]) + terms[:, 2])
+    for name in want:
+        out[name] = raw[name]
+    return out if isinstance(points, torch.Tensor) else {k: v.cpu().numpy() for k, v in out.items()}

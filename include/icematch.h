@@ -415,6 +415,44 @@ int im_knn_self(im_ctx* ctx, const double* d_pts, const long long* d_perm, const
                 int ny, int nz, int k, double radius2, int32_t* d_count, int32_t* d_idx, double* d_d2, double* d_mean, double* d_normal,
                 int32_t* d_rings, void* stream);
 
+/* ---- geometric features of the ball around every point (`scripts/pcd_postprocessing/top_border.py`: CloudCompare's
+ * `computeFeature(Linearity, 2.0)` and `computeFeature(Verticality, 0.15)`); csrc/ballfeat.hip, csrc/ball_point.h. CloudCompare is not a
+ * dependency: the features have a definition of their own (tests/ball_oracle.py: bit-identical); PARITY WITH A CLOUDCOMPARE
+ * BINARY IS UNPINNED. The grid, d_perm and d_start are those of the k-NN above (the same three calls prepare them).
+ * The neighbours of point q are the points p of the cloud, q included, with d2(q, p) <= fl(radius * radius). Each offset component
+ * fl(p - q) is quantised to the integer rint(u / h), h = radius * 2^-18, clamped to +-(2^18 + 1); ten exact int64 sums per query
+ * (count, Sx Sy Sz, Sxx Sxy Sxz Syy Syz Szz) are therefore a function of the input alone, whatever the grid and the order of accumulation.
+ * Covariance in quantised units in float64 (m_a = S_a / count, c_ab = S_ab / count - m_a m_b, no fused operations), eigenvalues by cyclic
+ * Jacobi, descending, negative ones 0.0, scaled by h * h to squared metres; the normal is the unit eigenvector of the smallest one with the
+ * first non-zero of (n_z, n_y, n_x) positive. count < 3 or the largest eigenvalue 0 gives NaN for eig, normal and every feature.
+ * Outputs, each may be NULL, all addressed by ORIGINAL point index: d_count [n] int32, d_sums [n][10] int64, d_eig [n][3] float64,
+ * d_normal [n][3] float64, d_feat [n][n_kinds] float64 (column j = the feature h_kinds[j], HOST memory, codes below; d_feat may be NULL only
+ * with n_kinds 0 or as an unwanted output), d_steps [n] int32 = the steps of 64 rows looked up or 64 candidates read that the query took,
+ * negated where the box of cells would have cost more row lookups than 1024 + n / 32 and the whole sorted cloud was scanned instead.
+ * One wave per query; the cloud in cell order lives in scratch of the context (shared with im_knn_self). Enqueue only.
+ * Returns -75, without launching, for a null required pointer (d_pts, d_perm, d_start, h_grid; h_kinds when n_kinds > 0), n < 0 or
+ * n > 2^26, a radius that is not finite and positive or whose h is not a normal number, a grid im_knn_self refuses, n_kinds outside 0..16,
+ * an unknown kind. n == 0 returns 0 and launches nothing. */
+enum im_ball_kind {
+    IM_BALL_EIGENVALUES_SUM = 0,      /* (l1 + l2) + l3 */
+    IM_BALL_PCA1 = 1,                 /* l1 / sum */
+    IM_BALL_PCA2 = 2,                 /* l2 / sum */
+    IM_BALL_SURFACE_VARIATION = 3,    /* l3 / sum */
+    IM_BALL_LINEARITY = 4,            /* (l1 - l2) / l1 */
+    IM_BALL_PLANARITY = 5,            /* (l2 - l3) / l1 */
+    IM_BALL_ANISOTROPY = 6,           /* (l1 - l3) / l1 */
+    IM_BALL_SPHERICITY = 7,           /* l3 / l1 */
+    IM_BALL_VERTICALITY = 8,          /* 1 - |n_z| */
+    IM_BALL_EIGENVALUE1 = 9,
+    IM_BALL_EIGENVALUE2 = 10,
+    IM_BALL_EIGENVALUE3 = 11,
+    IM_BALL_NUMBER_OF_NEIGHBORS = 12, /* (double)count */
+    IM_BALL_KINDS = 13
+};
+int im_ball_features(im_ctx* ctx, const double* d_pts, const long long* d_perm, const int32_t* d_start, long long n, const double* h_grid,
+                     int nx, int ny, int nz, double radius, const int32_t* h_kinds, int n_kinds, int32_t* d_count, long long* d_sums,
+                     double* d_eig, double* d_normal, double* d_feat, int32_t* d_steps, void* stream);
+
 /* ---- volume variations (`scripts/pcd_postprocessing/volume_variations.py`; `post_processing/cloudcompare_fun.py`:
  * `DemOfDifference.compute_volume` over CloudCompare's `ComputeVolume25D`; `post_processing/open3d_fun.py`: `filter_pcd_by_polyline`);
  * csrc/dod.hip, csrc/dod_cell.h. The DEM of difference of P pairs (ground, ceil) over E clouds that lie one behind the other in d_pts
