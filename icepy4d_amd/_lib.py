@@ -110,6 +110,12 @@ SIGNATURES = {
     "im_dod_keys": [_P, _P, _P, _I, _P, _I, _I, _D, _P, _P, _P, _P],
     "im_dod_reduce": [_P, _P, _P, _I, _P, _I, _I, _D, _P, _P, _P, _P, _P, _P],
     "im_crop_polygon": [_P, _P, _L, _I, _I, _P, _I, _I, _P, _P, _P, _P],
+    "im_voxel_max_points": [],
+    "im_voxel_bounds": [_P, _P, _P, _I, _P, _P],
+    "im_voxel_keys": [_P, _P, _P, _I, _P, _I, _P, _P, _P],
+    "im_voxel_reduce": [_P, _P, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
+    "im_voxel_mesh_corners": [_P, _P, _P, _L, _P, _P],
+    "im_voxel_mesh": [_P, _P, _L, _P, _P, _P, _P, _P, _P, _P, _P],
 }
 
 

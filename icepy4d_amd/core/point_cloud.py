@@ -1,5 +1,5 @@
 """`PointCloud` with the reference's names (`src/icepy4d/core/point_cloud.py`), numpy-backed: the reference wraps an Open3D point cloud,
-which is not a dependency here. `sor_filter` and `estimate_normals` run on the device (`utils/point_cloud_filters.py`, csrc/knn.hip);
+which is not a dependency here. `sor_filter` and `estimate_normals` run on the device (`utils/point_cloud_filters.py`, csrc/knn.hip), `voxel_down_sample` too (csrc/voxel.hip);
 parity of either with an Open3D binary is unpinned (see that module).
 
 PLY files are `binary_little_endian 1.0` with `double x y z`, then `uchar red green blue` when colours exist (round(c * 255) clipped to
@@ -143,6 +143,15 @@ class PointCloud:
         from ..utils.point_cloud_filters import estimate_normals
         self.normals = estimate_normals(self.points, radius=radius, max_nn=max_nn, engine=engine)
         return self.normals
+
+    def voxel_down_sample(self, voxel_size: float, engine=None) -> "PointCloud":
+        """A new cloud with one point per filled voxel: the mean of the voxel's points, colours and normals (`utils/point_cloud_filters.py`,
+        csrc/voxel.hip), in ascending voxel key."""
+        from ..utils.point_cloud_filters import voxel_down_sample
+        points, colors, normals, _, _ = voxel_down_sample(self.points, voxel_size, self.colors, self.normals, engine=engine)
+        out = PointCloud(points3d=points, points_col=colors, verbose=self._verbose)
+        out.normals = normals
+        return out
 
     def write_ply(self, path: Union[str, Path]) -> bool:
         """Write point cloud to disk as .ply format (module docstring)."""

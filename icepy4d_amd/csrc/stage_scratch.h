@@ -49,4 +49,20 @@ struct CropScratch : Carve {          // im_crop_polygon, n > 0 points: the poly
     explicit CropScratch(long long n) : poly(take<double>(2 * 1024)), sums(take<long long>(blocks_of(n, SCAN_THREADS))) {}
 };
 
+// im_voxel_bounds, im_voxel_keys and im_voxel_reduce, E clouds under G grids (1 or E), n points: table [2 (E + 1) + 3 G] (cloud offsets, the
+// first key of every cloud, n_x n_y n_z per grid), grids [7 G], bkeys [6 E], seg [n + 1] (first sorted position of every voxel, then the end),
+// sums [scan blocks of n + 1], total [1] (the number of voxels)
+struct VoxelScratch : Carve {
+    Piece<long long> table; Piece<double> grids; Piece<unsigned long long> bkeys; Piece<int> seg; Piece<long long> sums, total;
+    VoxelScratch(long long E, long long G, long long n)
+        : table(take<long long>(2 * (E + 1) + 3 * G)), grids(take<double>(7 * G)), bkeys(take<unsigned long long>(6 * E)), seg(take<int>(n + 1)),
+          sums(take<long long>(blocks_of(n + 1, SCAN_THREADS))), total(take<long long>(1)) {}
+};
+// im_voxel_mesh, `items` = 8 V > 0 corner items: vstart [items + 1] (first sorted item of every vertex, then the end), vertex [items] (the
+// vertex of local corner l of voxel v at 8 v + l), sums [scan blocks of items + 1]
+struct VoxelMeshScratch : Carve {
+    Piece<int> vstart, vertex; Piece<long long> sums;
+    explicit VoxelMeshScratch(long long items) : vstart(take<int>(items + 1)), vertex(take<int>(items)), sums(take<long long>(blocks_of(items + 1, SCAN_THREADS))) {}
+};
+
 }  // namespace im

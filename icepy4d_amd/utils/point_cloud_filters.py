@@ -27,7 +27,11 @@ points within a radius of each point, hundreds to thousands of them, which the 6
 dependency and the features have a definition of their own: offsets quantised to r * 2^-18 and summed exactly in int64, so
 that the result is a function of the input alone, bit-identical to tests/ball_oracle.py for any cell size. PARITY WITH A CLOUDCOMPARE
 BINARY IS UNPINNED: what could differ is its float32 storage of coordinates, its eigen solver and, at the scale of the quantisation step
-(7.6 um at r = 2 m), which points lie in a ball."""
+(7.6 um at r = 2 m), which points lie in a ball.
+
+`voxel_down_sample` (csrc/voxel.hip) thins a cloud before any of the above: one output point per filled voxel of the grid of
+`post_processing/voxel_grid.py`, the mean of the voxel's points (the reference: `scripts/tracking_experimental.py:462,602`). Bit-identical
+to tests/voxel_oracle.py; parity with an Open3D binary is unpinned (its output order is a hash map's, ours ascending voxel key)."""
 import math
 
 import numpy as np
@@ -272,3 +276,16 @@ def ball_features(points, radius, features=("Linearity",), cell_size=None, engin
     for name in want:
         out[name] = raw[name]
     return out if isinstance(points, torch.Tensor) else {k: v.cpu().numpy() for k, v in out.items()}
+
+
+def voxel_down_sample(points, voxel_size, colors=None, normals=None, engine=None):
+    """(points [V, 3], colors [V, 3] or None, normals [V, 3] or None, counts [V] int32, first_index [V] int32): per filled voxel of the grid
+    min(points) - 0.5 voxel_size .. max(points) + 0.5 voxel_size the mean of its points, of their colours and of their normals (not
+    renormalised), each column summed in ascending point index; the voxels in ascending key. `counts` and `first_index` (the voxel's first
+    input point) let a caller carry other per-point fields along. Points with a non-finite coordinate are ignored."""
+    from ..post_processing.voxel_grid import cloud_arrays, device_pass, make_grid
+    make_grid((0, 0, 0), (0, 0, 0), voxel_size)                      # a bad voxel_size raises before any device work
+    cloud = cloud_arrays(points, colors, normals)
+    results, _ = device_pass(default_engine(engine), [cloud], None, voxel_size, want_points=True)
+    r = results[0]
+    return r["points"], r["colors"], r["normals"], r["counts"], r["first"]

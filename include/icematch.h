@@ -499,6 +499,52 @@ int im_dod_reduce(im_ctx* ctx, const double* d_pts, const long long* h_offsets, 
 int im_crop_polygon(im_ctx* ctx, const double* d_pts, long long n, int axis_x, int axis_y, const double* h_poly, int n_verts, int inside,
                     unsigned char* d_mask, long long* d_index, long long* d_count, void* stream);
 
+/* Voxel grids, voxel down-sampling and voxel box meshes (csrc/voxel.hip; definition in DESIGN §4, restated in tests/voxel_oracle.py and
+ * csrc/voxel_cell.h). Open3D's `VoxelGrid.create_from_point_cloud_within_bounds`, `create_from_point_cloud`, `voxel_down_sample` and the
+ * cube mesh of the reference's `scripts/pcd_postprocessing/voxelization.py`; parity with an Open3D binary is unpinned. float64, contraction off.
+ * One call serves n_clouds = E clouds in one buffer d_pts [n][3] float64, cloud e = points h_offsets[e] .. h_offsets[e + 1] - 1 (h_offsets
+ * [E + 1] int64 in HOST memory, starting at 0). h_grids [G][7] float64 in HOST memory = origin = min_bound [3], max_bound [3], voxel_size
+ * s per grid: G = 1 grid for all clouds (per_cloud == 0) or G = E, one per cloud. n_a = floor((max_a - min_a) / s) + 1 voxels per axis.
+ * A point is kept iff every coordinate is finite and min_a <= p_a <= max_a on every axis; its index is i_a = floor((p_a - min_a) / s), a
+ * true division; its voxel key (i_x n_y + i_y) n_z + i_z.
+ * im_voxel_max_points: the most points of one call (2^26).
+ * im_voxel_bounds: d_bounds [E][6] float64 = min x y z, max x y z of every cloud's points with three finite coordinates (+inf x 3, -inf x 3
+ *   without one).
+ * im_voxel_keys: d_key [n] int64 = the first key of the point's cloud (the voxels of the grids before it: e * n_x n_y n_z under one grid,
+ *   the prefix sum of the per-cloud products otherwise) + the voxel key, or 2^63 - 1 for a point that is not kept; d_dropped [E] int64 =
+ *   the points of every cloud that are not kept. The caller sorts the keys (stable, ascending as signed integers).
+ * im_voxel_reduce: d_sorted_keys, d_perm [n] int64 = the sorted keys and the permutation (sorted position -> point). d_nvox [E + 1] int64
+ *   receives the first voxel of every cloud and, at [E], the number of voxels V. The voxels of all clouds are listed one cloud behind the
+ *   other in ascending key. Every other output is sized [n] rows by the caller, receives V rows and may be NULL (then it is not
+ *   written): d_grid_index [.][3] int32, d_count [.] int32, d_first [.] int32 = the voxel's first point, counted from its cloud's first
+ *   point, d_mean_pts / d_mean_colors / d_mean_normals [.][3] float64 = sum / count of the voxel's rows of d_pts / d_colors / d_normals
+ *   ([n][3] float64, each may be NULL: then its mean is not written), every column summed in ascending point index from +0.0.
+ * im_voxel_mesh_corners: one grid h_grid [7], d_grid_index [V][3] int32 in ascending voxel key; d_corner_keys [8 V] int64 = for voxel v
+ *   and local corner l at 8 v + l the key (c_x (n_y + 1) + c_y)(n_z + 1) + c_z of c = grid_index + d(l), d(l) = (l & 1, (l >> 2) & 1,
+ *   (l >> 1) & 1). The caller sorts them (stable).
+ * im_voxel_mesh: d_sorted_keys, d_perm [8 V] int64 of that sort; d_n_vertices [1] int64 = the number of unique corners U; d_vertices
+ *   [8 V][3] float64 receives U rows origin + c * s in ascending corner key; d_vertex_colors [8 V][3] float64 (written only when it and
+ *   d_colors [V][3] float64 are given) the mean of the colours of the at most 8 voxels that share the corner, summed in ascending voxel
+ *   from +0.0; d_triangles [12 V][3] int32 = per voxel the triangles (4,7,5) (4,6,7) (0,2,4) (2,6,4) (0,1,2) (1,3,2) (1,5,7) (1,7,3)
+ *   (2,3,7) (2,7,6) (0,4,1) (1,4,5) of its local corners, as vertex numbers.
+ * Keys, permutations and grid indices that are none give meaningless figures but no access outside a buffer.
+ * The calls wait for the upload of their tables, then enqueue. All return -77, without launching and with the outputs untouched, for a
+ * null required pointer, a voxel size that is not finite or not > 0, a bound that is not finite, max < min, offsets that do not start
+ * at 0 or descend, more than 2^26 points, E outside 0..65535, grids that hold more than 2^62 voxels together (under one grid: n_x n_y n_z
+ * E), a mesh grid with more than 2^62 corner keys, V < 0 or 8 V > 2^27. E == 0 (V == 0) returns 0 and launches nothing; so does n == 0,
+ * which zeroes d_dropped and d_nvox. */
+int im_voxel_max_points(void);
+int im_voxel_bounds(im_ctx* ctx, const double* d_pts, const long long* h_offsets, int n_clouds, double* d_bounds, void* stream);
+int im_voxel_keys(im_ctx* ctx, const double* d_pts, const long long* h_offsets, int n_clouds, const double* h_grids, int per_cloud, long long* d_key,
+                  long long* d_dropped, void* stream);
+int im_voxel_reduce(im_ctx* ctx, const long long* h_offsets, int n_clouds, const double* h_grids, int per_cloud, const long long* d_sorted_keys,
+                    const long long* d_perm, const double* d_pts, const double* d_colors, const double* d_normals, long long* d_nvox,
+                    int32_t* d_grid_index, int32_t* d_count, int32_t* d_first, double* d_mean_pts, double* d_mean_colors, double* d_mean_normals,
+                    void* stream);
+int im_voxel_mesh_corners(im_ctx* ctx, const double* h_grid, const int32_t* d_grid_index, long long n_voxels, long long* d_corner_keys, void* stream);
+int im_voxel_mesh(im_ctx* ctx, const double* h_grid, long long n_voxels, const double* d_colors, const long long* d_sorted_keys, const long long* d_perm,
+                  long long* d_n_vertices, double* d_vertices, double* d_vertex_colors, int32_t* d_triangles, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
