@@ -116,6 +116,17 @@ SIGNATURES = {
     "im_voxel_reduce": [_P, _P, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
     "im_voxel_mesh_corners": [_P, _P, _P, _L, _P, _P],
     "im_voxel_mesh": [_P, _P, _L, _P, _P, _P, _P, _P, _P, _P, _P],
+    "im_mesh_max_items": [],
+    "im_mesh_hull_chunk": [],
+    "im_mesh_select": [_P, _P, _L, _P, _L, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P],
+    "im_mesh_triangle_keys": [_P, _P, _L, _P, _P, _P],
+    "im_mesh_vertex_keys": [_P, _P, _L, _P, _P, _P, _P],
+    "im_mesh_edge_keys": [_P, _P, _L, _P, _P],
+    "im_mesh_first_of_segment": [_P, _L, _P, _P, _P, _P, _P, _P, _P],
+    "im_mesh_edge_census": [_P, _P, _L, _P, _P],
+    "im_mesh_in_hull": [_P, _P, _L, _P, _I, _P, _P],
+    "im_mesh_sample_table": [_P, _P, _L, _P, _L, _L, _P, _P, _P, _P],
+    "im_mesh_sample": [_P, _P, _L, _P, _L, _P, _L, _L, _P, _P, _P, _P, _P, _P, _P],
 }
 
 

@@ -65,4 +65,31 @@ struct VoxelMeshScratch : Carve {
     explicit VoxelMeshScratch(long long items) : vstart(take<int>(items + 1)), vertex(take<int>(items)), sums(take<long long>(blocks_of(items + 1, SCAN_THREADS))) {}
 };
 
+// im_mesh_select, V >= 0 vertices, T >= 0 triangles: tflag [T] (the triangle is kept), vflag [V] (the vertex is kept), ref [V] (a kept
+// triangle references the vertex), sums [scan blocks of max(V, T, 1)]
+struct MeshSelectScratch : Carve {
+    Piece<unsigned char> tflag, vflag, ref; Piece<long long> sums;
+    MeshSelectScratch(long long V, long long T)
+        : tflag(take<unsigned char>(T)), vflag(take<unsigned char>(V)), ref(take<unsigned char>(V)),
+          sums(take<long long>(blocks_of(V > T ? (V > 1 ? V : 1) : (T > 1 ? T : 1), SCAN_THREADS))) {}
+};
+// im_mesh_first_of_segment, n > 0 sorted items: head [n + 1] (the item at the first sorted position of every segment), segment [n] (the
+// segment of every sorted position), sums [scan blocks of n], total [1]
+struct MeshSegmentScratch : Carve {
+    Piece<int> head, segment; Piece<long long> sums, total;
+    explicit MeshSegmentScratch(long long n) : head(take<int>(n + 1)), segment(take<int>(n)), sums(take<long long>(blocks_of(n, SCAN_THREADS))), total(take<long long>(1)) {}
+};
+// im_mesh_in_hull, F > 0 facets: facets [4 F]
+struct MeshHullScratch : Carve {
+    Piece<double> facets;
+    explicit MeshHullScratch(long long F) : facets(take<double>(4 * F)) {}
+};
+// im_mesh_sample_table, T > 0 triangles: area [T], cum [T] (inclusive cumulative quantised areas), sums [scan blocks of T], amax [1] (the
+// bits of the largest area), total [1] (C)
+struct MeshSampleScratch : Carve {
+    Piece<double> area; Piece<long long> cum, sums; Piece<unsigned long long> amax; Piece<long long> total;
+    explicit MeshSampleScratch(long long T) : area(take<double>(T)), cum(take<long long>(T)), sums(take<long long>(blocks_of(T, SCAN_THREADS))),
+          amax(take<unsigned long long>(1)), total(take<long long>(1)) {}
+};
+
 }  // namespace im

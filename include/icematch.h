@@ -545,6 +545,60 @@ int im_voxel_mesh_corners(im_ctx* ctx, const double* h_grid, const int32_t* d_gr
 int im_voxel_mesh(im_ctx* ctx, const double* h_grid, long long n_voxels, const double* d_colors, const long long* d_sorted_keys, const long long* d_perm,
                   long long* d_n_vertices, double* d_vertices, double* d_vertex_colors, int32_t* d_triangles, void* stream);
 
+/* Triangle-mesh filters, the convex-hull crop and uniform mesh sampling (csrc/mesh.hip; definitions in DESIGN §4, restated in
+ * tests/mesh_oracle.py and csrc/mesh_tri.h): what the reference's `MeshingPoisson.run()` does behind the Poisson solve. Parity with an
+ * Open3D binary is unpinned. Vertices, colours, normals [V][3] float64; triangles [T][3] int32; float64 arithmetic with contraction off.
+ * im_mesh_max_items: the most vertices, triangles or samples of one call (2^26). im_mesh_hull_chunk: facets staged in LDS at a time (512).
+ * im_mesh_select: a triangle is kept iff d_triangle_keep [T] uint8 (NULL = all) allows it, each of its three indices lies in [0, V),
+ *   is - through d_vertex_merge [V] int32 (NULL = identity; vertex -> the vertex that stands for it) - again in [0, V) and allowed by
+ *   d_vertex_keep [V] uint8 (NULL = all), and, with drop_degenerate, the three are distinct. A vertex is kept iff d_vertex_keep allows it
+ *   and, with drop_unreferenced, a kept triangle references it. d_vertex_map [V] int32 = the new number of every vertex, -1 where dropped;
+ *   d_vertex_list [V] int32 = the kept vertices in ascending old index (the first d_counts [0] are written); d_triangles_out [T][3] int32
+ *   = the kept triangles in their old order, renumbered, and d_triangle_pos [T] int32 their old positions (the first d_counts [1]);
+ *   d_counts [2] int64. A triangle with an index outside [0, V) is skipped: it is dropped.
+ * im_mesh_triangle_keys: d_key0, d_key1 [T] int64 = a and b << 32 | c of the index triple rotated to smallest-index-first (orientation
+ *   counts). im_mesh_vertex_keys: d_key0..2 [V] int64 = the bits of x, y, z with -0.0 as +0.0; a vertex with a NaN coordinate gets
+ *   (0x7ff8000000000000, its index, 0) and equals nothing. im_mesh_edge_keys: d_keys [3 T] int64, item 3 t + e = min << 32 | max of
+ *   corners e and (e + 1) % 3 of triangle t. None of the three reads a vertex through an index.
+ * im_mesh_first_of_segment: d_key0 (and d_key1, d_key2 or NULL) [n] int64 in item order, d_perm [n] int64 = sorted position -> item of
+ *   successive stable sorts by the last key first. d_first [n] int32 = per item the first item (lowest index) of the run of equal keys
+ *   it lies in, d_keep [n] uint8 = the item is that first one; either may be NULL.
+ * im_mesh_edge_census: d_sorted_keys [n] int64 (n <= 3 * 2^26); d_count [1] int64 = the keys that occur more than twice.
+ * im_mesh_in_hull: h_facets [F][4] float64 in HOST memory (n_x, n_y, n_z, d; scipy.spatial.ConvexHull.equations), 1 <= F <= 2^22;
+ *   d_inside [n] uint8 = max_f (((n_x x + n_y y) + n_z z) + d) <= 0, the maximum running in facet order from -inf; a NaN value sticks,
+ *   so a point with a NaN coordinate is outside.
+ * im_mesh_sample_table: area_t = 0.5 |(v1 - v0) x (v2 - v0)|, 0 when not finite or when an index lies outside [0, V) (the triangle is
+ *   skipped); q_t = floor(area_t / max area * 2^32) as int64, c_t their inclusive prefix sums (integers: exact in any order), C = c_T;
+ *   d_count_end [T] int64 = rint(c_t / C * N): sample i belongs to the first triangle with d_count_end > i. d_area [T] float64 (NULL =
+ *   not wanted) the areas, *h_total (HOST, NULL = not wanted) = C. The call waits for C before it writes an output.
+ * im_mesh_sample: d_points [N][3] = (a v0 + b v1) + c v2 with s = sqrt(r1), a = 1 - s, b = s (1 - r2), c = s r2; r1, r2 = the top 53
+ *   bits times 2^-53 of splitmix64's finaliser of seed + (2 i + 1) g and seed + (2 i + 2) g, g = 0x9E3779B97F4A7C15: a function of
+ *   (seed, i) alone. d_colors [N][3] (NULL, or no d_vertex_colors: not written) likewise; d_normals [N][3] (NULL = not wanted) the
+ *   same blend of d_vertex_normals, not renormalised, or without them the triangle's cross / |cross|; d_triangle_index [N] int32 (NULL =
+ *   not wanted). An index outside [0, V) of a triangle the table leads to is clamped.
+ * Keys that are not sorted, a permutation that is none, a table that is none give meaningless figures but no access outside a buffer.
+ * All return -78, without launching and with the outputs untouched, for a null required pointer, a negative count, V, T, n or N above
+ * 2^26, F outside 1..2^22, a facet that is not finite, samples (N > 0) of a mesh with no vertex or no triangle; im_mesh_sample_table
+ * returns -78 with the outputs untouched, after its area pass, when N > 0 and C == 0. Zero-size calls return 0 and launch nothing
+ * (im_mesh_select and im_mesh_edge_census zero their counts). */
+int im_mesh_max_items(void);
+int im_mesh_hull_chunk(void);
+int im_mesh_select(im_ctx* ctx, const unsigned char* d_vertex_keep, long long n_vertices, const int32_t* d_triangles, long long n_triangles,
+                   const int32_t* d_vertex_merge, const unsigned char* d_triangle_keep, int drop_degenerate, int drop_unreferenced, int32_t* d_vertex_map,
+                   int32_t* d_vertex_list, int32_t* d_triangles_out, int32_t* d_triangle_pos, long long* d_counts, void* stream);
+int im_mesh_triangle_keys(im_ctx* ctx, const int32_t* d_triangles, long long n_triangles, long long* d_key0, long long* d_key1, void* stream);
+int im_mesh_vertex_keys(im_ctx* ctx, const double* d_vertices, long long n_vertices, long long* d_key0, long long* d_key1, long long* d_key2, void* stream);
+int im_mesh_edge_keys(im_ctx* ctx, const int32_t* d_triangles, long long n_triangles, long long* d_keys, void* stream);
+int im_mesh_first_of_segment(im_ctx* ctx, long long n, const long long* d_key0, const long long* d_key1, const long long* d_key2, const long long* d_perm,
+                             int32_t* d_first, unsigned char* d_keep, void* stream);
+int im_mesh_edge_census(im_ctx* ctx, const long long* d_sorted_keys, long long n_items, long long* d_count, void* stream);
+int im_mesh_in_hull(im_ctx* ctx, const double* d_points, long long n_points, const double* h_facets, int n_facets, unsigned char* d_inside, void* stream);
+int im_mesh_sample_table(im_ctx* ctx, const double* d_vertices, long long n_vertices, const int32_t* d_triangles, long long n_triangles, long long n_samples,
+                         double* d_area, long long* d_count_end, long long* h_total, void* stream);
+int im_mesh_sample(im_ctx* ctx, const double* d_vertices, long long n_vertices, const int32_t* d_triangles, long long n_triangles, const long long* d_count_end,
+                   long long n_samples, long long seed, const double* d_vertex_colors, const double* d_vertex_normals, double* d_points, double* d_colors,
+                   double* d_normals, int32_t* d_triangle_index, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
