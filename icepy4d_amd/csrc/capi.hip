@@ -201,7 +201,11 @@ int im_profile_end(im_ctx* ctx, char* buf, size_t cap) {
 // Copies an internal buffer of the last forward to d_dst (stage-level parity tests). Names: "lg_x" (descriptors after the
 // last executed layer, [2][K][256]), "lg_cos" / "lg_sin" (rotary tables [2][K][32]), "sim" ([K][K] score matrix),
 // "md" (projected matching descriptors [2][K][256]), "sp_smap" / "sp_nms" (SuperPoint score map before / after simple_nms of
-// the last im_superpoint_forward, [n_images][H8][W8] densely packed for that call's size). Synchronises the stream.
+// the last im_superpoint_forward, [n_images][H8][W8] densely packed for that call's size). Of the last assignment stage, pair 0, as
+// raw 32-bit words: "rmax" / "rlog" / "cmax" / "clog" / "rval" (floats) and "ridx" (int32), one per row or column; "cbest" (the 64-bit
+// column keys f2ord(score) << 32 | ~row, two words per column, low word first); "lz" (log-sigmoid certainties [2][K]). Of SuperGlue's
+// Sinkhorn potentials: "u" (rows, then the dustbin), "v" (columns, then the dustbin; it starts (K + 4) & ~3 floats into the buffer)
+// and "norm" (one float). Synchronises the stream.
 int im_debug_read(im_ctx* ctx, const char* name, float* d_dst, size_t nfloats, void* stream) {
     IM_CHECK_CTX(ctx);
     Workspace* ws = ctx->ws;
@@ -217,6 +221,19 @@ int im_debug_read(im_ctx* ctx, const char* name, float* d_dst, size_t nfloats, v
     else if (nm == "md") { src = ws->md; avail = 2 * K * 256; }
     else if (nm == "sp_smap") { src = ws->smap; avail = ws->smap_floats; }
     else if (nm == "sp_nms") { src = ws->nms; avail = ws->smap_floats; }
+    else if (nm == "rmax") { src = ws->rmax; avail = ws->vec_ps; }
+    else if (nm == "rlog") { src = ws->rlog; avail = ws->vec_ps; }
+    else if (nm == "cmax") { src = ws->cmax; avail = ws->vec_ps; }
+    else if (nm == "clog") { src = ws->clog; avail = ws->vec_ps; }
+    else if (nm == "rval") { src = ws->rval; avail = ws->vec_ps; }
+    else if (nm == "ridx") { src = reinterpret_cast<const float*>(ws->ridx); avail = ws->vec_ps; }
+    else if (nm == "cbest") { src = reinterpret_cast<const float*>(ws->cbest); avail = 2 * ws->vec_ps; }
+    else if (nm == "lz") { src = ws->lz; avail = 2 * K; }
+    else if (nm == "u" || nm == "v" || nm == "norm") {
+        const size_t voff = (K + 4) & ~(size_t)3;      // as im_superglue_forward lays ws->uv out
+        src = ws->uv + (nm == "u" ? 0 : nm == "v" ? voff : 2 * voff);
+        avail = nm == "norm" ? 1 : K + 1;
+    }
     else return ctx->fail(-61, "im_debug_read: unknown buffer '%s'", name);
     if (nfloats > avail) return ctx->fail(-62, "im_debug_read: %zu floats requested, %zu available", nfloats, avail);
     IM_HIP(ctx, hipMemcpyAsync(d_dst, src, nfloats * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));

@@ -124,7 +124,10 @@ int im_pack_record(im_ctx* ctx, const int32_t* d_n, const int32_t* d_matches0, c
 int im_pack_records(im_ctx* ctx, int n_pairs, const int32_t* d_n, const int32_t* d_matches, const float* d_mscores,
                     const int32_t* d_info, int first_epoch, int32_t* d_records, const float* d_kpts, void* stream);
 /* Copies an internal buffer of the last forward ("lg_x", "lg_cos", "lg_sin", "sim", "md", "sp_smap", "sp_nms") for
- * stage-level parity tests. */
+ * stage-level parity tests. Of the last assignment stage (im_assign_from_sim, or pair 0 of a matcher forward), as raw 32-bit
+ * words counted in nfloats: "rmax", "rlog", "cmax", "clog", "rval" (float per row / column), "ridx" (int32 per row), "cbest"
+ * (uint64 key per column = two words, low word first: ordered score bits << 32 | ~row), "lz" (log-sigmoid certainties
+ * [2][max_kpts]); of im_superglue_forward's Sinkhorn potentials: "u" (m rows + dustbin), "v" (n columns + dustbin), "norm" (1). */
 int im_debug_read(im_ctx* ctx, const char* name, float* d_dst, size_t nfloats, void* stream);
 /* Measurement aid (no reference counterpart): the shader clock the two matrix-core kernel classes hold INSIDE their main loops. arm = 1: from
  * now on every attention launch (the matchers' self / cross blocks) and every Winograd convolution launch of this context has the first wave of
