@@ -144,6 +144,12 @@ class PointCloud:
         self.normals = estimate_normals(self.points, radius=radius, max_nn=max_nn, engine=engine)
         return self.normals
 
+    def compute_point_cloud_distance(self, target, engine=None) -> np.ndarray:
+        """For every point its distance to the nearest point of `target` (a `PointCloud` or [n, 3] array), [n] float64, on the device
+        (Open3D's name; `post_processing/cloud_distance.py`, whose definition it is: parity with an Open3D binary is unpinned)."""
+        from ..post_processing.cloud_distance import cloud_to_cloud_distance
+        return cloud_to_cloud_distance(self.points, target, engine=engine).distance
+
     def voxel_down_sample(self, voxel_size: float, engine=None) -> "PointCloud":
         """A new cloud with one point per filled voxel: the mean of the voxel's points, colours and normals (`utils/point_cloud_filters.py`,
         csrc/voxel.hip), in ascending voxel key."""

@@ -6,8 +6,8 @@
 //
 //   knn_gather_kernel    (knn_sorted.h) the cloud in cell order, into the scratch im_knn_self uses
 //   ball_features_kernel one wave per query, queries in cell order. The box of cells [c - R, c + R] (R = ball_rings, the k-NN's stop rule
-//                        without a k-th distance) clipped to the grid is walked as rows, each row one contiguous range of the sorted
-//                        cloud: the lanes look up the ranges of 64 rows at a time, a ballot keeps those that hold points, and those are
+//                        without a k-th distance) clipped to the grid is walked as rows (knn_list.h: knn_box_walk), each row one
+//                        contiguous range of the sorted cloud: the lanes look up the ranges of 64 rows at a time, a ballot keeps those that hold points, and those are
 //                        read 64 candidates at a time, coalesced. Each lane adds its own candidates to its own ten sums; one butterfly
 //                        per query merges them. No LDS, no barrier, no atomics, no per-thread array. A box whose row lookups alone would
 //                        cost more than knn_step_budget is given up for one scan of the whole sorted cloud before it starts.
@@ -17,7 +17,9 @@
 #include "ctx.h"
 #include "stage_scratch.h"
 #include "knn_sorted.h"
+#include "knn_list.h"
 #include "ball_point.h"
+#include "ball_wave.h"
 
 namespace im {
 namespace {
@@ -33,7 +35,7 @@ struct BallArgs {
 };
 
 static_assert(IM_BALL_KINDS <= 16 && BALL_MAX_KINDS * 4 <= 64, "sixteen kinds of four bits each fill the packed word");
-static_assert(BALL_MAX_KINDS <= IM_WAVE && BALL_SUMS <= IM_WAVE, "a row of features and the sums are stored by the first lanes of a wave");
+static_assert(BALL_MAX_KINDS <= IM_WAVE, "a row of features is stored by the first lanes of a wave");
 
 // the candidates at sorted positions [b, e), each lane its own
 __device__ __forceinline__ void ball_scan(const BallArgs& a, BallSums& S, int lane, double qx, double qy, double qz, int b, int e) {
@@ -55,52 +57,11 @@ __global__ __launch_bounds__(IM_WAVE * KNN_WAVES) void ball_features_kernel(Ball
     const int x0 = max(0, c[0] - R), x1 = min(a.g.n[0] - 1, c[0] + R);
     const int y0 = max(0, c[1] - R), y1 = min(a.g.n[1] - 1, c[1] + R);
     const int z0 = max(0, c[2] - R), z1 = min(a.g.n[2] - 1, c[2] + R);
-    const int wy = y1 - y0 + 1, rows = wy * (z1 - z0 + 1);            // <= ny * nz <= 2^24
     BallSums S;
     ball_zero(S);
-    int steps;
-    if ((rows + IM_WAVE - 1) / IM_WAVE > knn_step_budget(a.n)) {
-        // looking the rows up would cost more than reading the whole cloud: a tiny cell size, or a grid stretched by a far outlier
-        ball_scan(a, S, lane, qx, qy, qz, 0, a.n);
-        steps = -((a.n + IM_WAVE - 1) / IM_WAVE);
-    } else {
-        steps = 0;
-        for (int base = 0; base < rows; base += IM_WAVE) {
-            const int row = base + lane;
-            int b = 0, e = 0;
-            if (row < rows) knn_row_range(a.g, a.start, a.n, x0, x1, y0 + row % wy, z0 + row / wy, b, e);
-            unsigned long long m = __ballot(e > b);
-            ++steps;
-            while (m) {
-                const int src = __ffsll((long long)m) - 1;
-                m &= m - 1;
-                const int sb = __shfl(b, src), se = __shfl(e, src);
-                ball_scan(a, S, lane, qx, qy, qz, sb, se);
-                steps += (se - sb + IM_WAVE - 1) / IM_WAVE;
-            }
-        }
-    }
-    // integer sums: any order gives the same bits, so the butterfly leaves the ball's sums in every lane
-#pragma unroll
-    for (int k = 0; k < BALL_SUMS; ++k)
-#pragma unroll
-        for (int o = IM_WAVE / 2; o > 0; o >>= 1) S.s[k] += __shfl_xor(S.s[k], o);
+    const int steps = knn_box_walk(a.g, a.start, a.n, lane, x0, x1, y0, y1, z0, z1, [&](int b, int e) { ball_scan(a, S, lane, qx, qy, qz, b, e); });
     double eig[3], e3[3];
-    ball_finish(S, a.hh, eig, e3);
-    if (lane == 0) {
-        if (a.count) a.count[qi] = (int)S.s[0];
-        if (a.steps) a.steps[qi] = steps;
-    }
-    if (a.sums) {
-        long long v = 0;
-#pragma unroll
-        for (int k = 0; k < BALL_SUMS; ++k) v = lane == k ? S.s[k] : v;
-        if (lane < BALL_SUMS) a.sums[(long long)qi * BALL_SUMS + lane] = v;
-    }
-    if (lane < 3) {
-        if (a.eig) a.eig[3LL * qi + lane] = lane == 0 ? eig[0] : (lane == 1 ? eig[1] : eig[2]);
-        if (a.normal) a.normal[3LL * qi + lane] = lane == 0 ? e3[0] : (lane == 1 ? e3[1] : e3[2]);
-    }
+    ball_wave_finish(S, lane, qi, a.hh, steps, a.count, a.sums, a.eig, a.normal, a.steps, eig, e3);
     if (a.feat && lane < a.n_kinds)
         a.feat[(long long)qi * a.n_kinds + lane] = ball_feature((int)((a.kinds >> (4 * lane)) & 15), eig, e3, S.s[0]);
 }

@@ -31,7 +31,12 @@ BINARY IS UNPINNED: what could differ is its float32 storage of coordinates, its
 
 `voxel_down_sample` (csrc/voxel.hip) thins a cloud before any of the above: one output point per filled voxel of the grid of
 `post_processing/voxel_grid.py`, the mean of the voxel's points (the reference: `scripts/tracking_experimental.py:462,602`). Bit-identical
-to tests/voxel_oracle.py; parity with an Open3D binary is unpinned (its output order is a hash map's, ours ascending voxel key)."""
+to tests/voxel_oracle.py; parity with an Open3D binary is unpinned (its output order is a hash map's, ours ascending voxel key).
+
+`knn_cross`, `ball_cross` and `cylinder_stats` (csrc/cloud_distance.hip) ask a TARGET cloud at external queries: the nearest target
+points, the ball's sums and normal, and the statistics of the target inside a cylinder along a normal, the pieces of cloud-to-cloud
+distances and M3C2 (`post_processing/cloud_distance.py`). The grid comes from the target; the queries may lie anywhere. Bit-identical to
+tests/cloud_distance_oracle.py for any cell size and any query order; parity with CloudCompare or Open3D is unpinned."""
 import math
 
 import numpy as np
@@ -276,6 +281,162 @@ def ball_features(points, radius, features=("Linearity",), cell_size=None, engin
     for name in want:
         out[name] = raw[name]
     return out if isinstance(points, torch.Tensor) else {k: v.cpu().numpy() for k, v in out.items()}
+
+
+# ---- a target cloud asked at external queries (csrc/cloud_distance.hip) ------------------------------------------------------------------
+class BinnedCloud:
+    """A target cloud on the device, binned once into a grid over its own bounds by `bin_cloud`: what `knn_cross`, `ball_cross` and
+    `cylinder_stats` take as `binned=`, so that a cloud binned once serves several calls. `pts` [n, 3] float64 device tensor, `cell_size`,
+    `dims`, `grid` (host, origin and cell size), `perm` and `start` (device) as `_binned` returns them; all None but `pts` for n == 0."""
+
+    def __init__(self, pts, cell_size=None, dims=None, grid=None, perm=None, start=None):
+        self.pts, self.cell_size, self.dims, self.grid, self.perm, self.start = pts, cell_size, dims, grid, perm, start
+
+    def __len__(self):
+        return self.pts.shape[0]
+
+
+def bin_cloud(points, cell_size, engine=None):
+    """`points` (numpy or tensor, finite: ValueError otherwise) uploaded and binned into the grid of `cell_size` (enlarged to fit the cell cap)."""
+    if not (float(cell_size) > 0.0 and math.isfinite(float(cell_size))):
+        raise ValueError(f"cell_size must be finite and positive (got {cell_size})")
+    eng = default_engine(engine)
+    pts = _device_points(points, eng.device)
+    if pts.shape[0] > MAX_BALL_POINTS:
+        raise ValueError("at most 2^26 points")
+    if pts.shape[0] == 0:
+        return BinnedCloud(pts)
+    lo, hi = _bounds(pts)
+    return BinnedCloud(pts, *_binned(eng, pts, lo, hi, float(cell_size)))
+
+
+def _device_queries(queries, dev, what="queries"):
+    q = queries.to(device=dev, dtype=torch.float64).contiguous() if isinstance(queries, torch.Tensor) else to_device(queries, dev, np.float64)
+    if q.ndim != 2 or q.shape[1] != 3:
+        raise ValueError(f"{what} must be [m, 3] (got {tuple(q.shape)})")
+    if q.shape[0] > MAX_BALL_POINTS:
+        raise ValueError(f"at most 2^26 {what}")
+    return q
+
+
+def query_order(eng, q, target):
+    """The order in which the waves take the queries: ascending key of the query's (clamped) cell in the target's grid, so that neighbouring
+    waves read the same cells. A tunable: no result depends on it."""
+    m = q.shape[0]
+    key = torch.empty(m, dtype=torch.int64, device=q.device)
+    eng.ctx.call("im_knn_cells", ptr(q), m, target.grid.ctypes.data, target.dims[0], target.dims[1], target.dims[2], ptr(key), eng.stream_ptr())
+    return torch.sort(key, stable=True)[1]
+
+
+def _cross(eng, queries, points, binned, default_cell_size, cell_size, sort_queries):
+    """(q device [m, 3], target BinnedCloud, d_qorder or None) of a cross call."""
+    if cell_size is not None and not (float(cell_size) > 0.0 and math.isfinite(float(cell_size))):
+        raise ValueError(f"cell_size must be finite and positive (got {cell_size})")
+    q = _device_queries(queries, eng.device)
+    if binned is None:
+        pts = _device_points(points, eng.device)
+        if pts.shape[0] > MAX_BALL_POINTS:
+            raise ValueError("at most 2^26 points")
+        if pts.shape[0] == 0:
+            binned = BinnedCloud(pts)
+        else:
+            lo, hi = _bounds(pts)
+            s = default_cell_size(pts, lo, hi) if cell_size is None else float(cell_size)
+            binned = BinnedCloud(pts, *_binned(eng, pts, lo, hi, s))
+    order = query_order(eng, q, binned) if sort_queries and len(binned) > 0 and q.shape[0] > 1 else None
+    return q, binned, order
+
+
+def _target_args(t):
+    return (ptr(t.pts), ptr(t.perm), ptr(t.start), len(t), t.grid.ctypes.data, t.dims[0], t.dims[1], t.dims[2])
+
+
+def _result(out, queries):
+    return out if isinstance(queries, torch.Tensor) else {k: (v.cpu().numpy() if isinstance(v, torch.Tensor) else v) for k, v in out.items()}
+
+
+def knn_cross(queries, points, k, radius=None, cell_size=None, engine=None, want=("idx", "d2", "count"), binned=None, sort_queries=True):
+    """The k (1..64) nearest points of the target cloud `points` for every row of `queries` [m, 3], which may lie anywhere: {name: ...} for
+    the names in `want` out of idx [m, k] int32 (indices into `points`), d2 [m, k] float64, count [m] int32, rings [m] int32, with the
+    order, tie rule, radius cut and unused slots of `knn_self`. A query with a non-finite coordinate has no neighbours. The target must be
+    finite (ValueError). `binned` (a `bin_cloud` result) replaces `points`; `cell_size` and `sort_queries` are tunables: the result does
+    not depend on them. numpy queries in, numpy out; tensor in, tensors out."""
+    k = int(k)
+    if not 1 <= k <= MAX_K:
+        raise ValueError(f"k must be 1..{MAX_K} (got {k})")
+    if radius is not None and not float(radius) >= 0.0:
+        raise ValueError(f"radius must be >= 0 (got {radius})")
+    unknown = set(want) - {"idx", "d2", "count", "rings"}
+    if unknown:
+        raise ValueError(f"unknown outputs {sorted(unknown)}")
+    eng = default_engine(engine)
+    q, t, order = _cross(eng, queries, points, binned, lambda pts, lo, hi: choose_cell_size(eng, pts, lo, hi, k), cell_size, sort_queries)
+    m, dev = q.shape[0], eng.device
+    fill = {"idx": ((m, k), torch.int32, -1), "d2": ((m, k), torch.float64, math.inf), "count": ((m,), torch.int32, 0), "rings": ((m,), torch.int32, 0)}
+    out = {name: torch.full(fill[name][0], fill[name][2], dtype=fill[name][1], device=dev) for name in want}      # what an empty target leaves
+    if len(t) > 0 and m > 0:
+        r2 = math.inf if radius is None else float(radius) * float(radius)
+        eng.ctx.call("im_knn_cross", *_target_args(t), ptr(q), ptr(order), m, k, r2, ptr(out.get("count")), ptr(out.get("idx")),
+                     ptr(out.get("d2")), ptr(out.get("rings")), eng.stream_ptr())
+    return _result(out, queries)
+
+
+def _check_radius(radius, what="radius"):
+    radius = float(radius)
+    if not (radius > 0.0 and math.isfinite(radius)) or radius * 2.0 ** -18 < 2.2250738585072014e-308:
+        raise ValueError(f"{what} must be finite and positive, and {what} * 2^-18 a normal number (got {radius})")
+    return radius
+
+
+def ball_cross(queries, points, radius, want=("count", "normal"), cell_size=None, engine=None, binned=None, sort_queries=True):
+    """The ball of `radius` in the target cloud `points` around every row of `queries`, by the definitions of `ball_features` with offsets
+    relative to the query (which is no neighbour unless a target point coincides with it): {name: ...} for the names in `want` out of
+    count [m] int32, sums [m, 10] int64, eig [m, 3], normal [m, 3] float64 and steps [m] int32. A ball of fewer than three points or
+    without extent, and a query with a non-finite coordinate, give NaN. `binned`, `cell_size` (default radius / 2) and `sort_queries` as
+    in `knn_cross`."""
+    radius = _check_radius(radius)
+    unknown = set(want) - {"count", "sums", "eig", "normal", "steps"}
+    if unknown:
+        raise ValueError(f"unknown outputs {sorted(unknown)}")
+    eng = default_engine(engine)
+    q, t, order = _cross(eng, queries, points, binned, lambda pts, lo, hi: radius / 2.0, cell_size, sort_queries)
+    m, dev = q.shape[0], eng.device
+    fill = {"count": ((m,), torch.int32, 0), "sums": ((m, 10), torch.int64, 0), "eig": ((m, 3), torch.float64, math.nan),
+            "normal": ((m, 3), torch.float64, math.nan), "steps": ((m,), torch.int32, 0)}
+    out = {name: torch.full(fill[name][0], fill[name][2], dtype=fill[name][1], device=dev) for name in want}
+    if len(t) > 0 and m > 0:
+        eng.ctx.call("im_ball_cross", *_target_args(t), ptr(q), ptr(order), m, radius, ptr(out.get("count")), ptr(out.get("sums")),
+                     ptr(out.get("eig")), ptr(out.get("normal")), ptr(out.get("steps")), eng.stream_ptr())
+    return _result(out, queries)
+
+
+def cylinder_stats(queries, normals, points, radius, half_length, want=("count", "mean", "std"), cell_size=None, engine=None, binned=None,
+                   sort_queries=True):
+    """The points of the target cloud `points` inside the cylinder of `radius` and `half_length` around every row of `queries` along the
+    matching row of `normals` (used as given; csrc/cyl_point.h): {name: ...} for the names in `want` out of count [m] int32,
+    sums [m, 2] int64 (St, Stt of the projections quantised to half_length * 2^-18), mean [m] and std [m] float64 in metres (NaN for count 0
+    and count < 2), steps [m] int32. A query or normal with a non-finite component gives count 0 and NaN. `binned`, `cell_size` (default:
+    the radius) and `sort_queries` as in `knn_cross`."""
+    radius = float(radius)
+    if not (radius > 0.0 and math.isfinite(radius)):
+        raise ValueError(f"radius must be finite and positive (got {radius})")
+    half_length = _check_radius(half_length, "half_length")
+    unknown = set(want) - {"count", "sums", "mean", "std", "steps"}
+    if unknown:
+        raise ValueError(f"unknown outputs {sorted(unknown)}")
+    eng = default_engine(engine)
+    q, t, order = _cross(eng, queries, points, binned, lambda pts, lo, hi: radius, cell_size, sort_queries)
+    nrm = _device_queries(normals, eng.device, "normals")
+    if nrm.shape[0] != q.shape[0]:
+        raise ValueError(f"{q.shape[0]} queries but {nrm.shape[0]} normals")
+    m, dev = q.shape[0], eng.device
+    fill = {"count": ((m,), torch.int32, 0), "sums": ((m, 2), torch.int64, 0), "mean": ((m,), torch.float64, math.nan),
+            "std": ((m,), torch.float64, math.nan), "steps": ((m,), torch.int32, 0)}
+    out = {name: torch.full(fill[name][0], fill[name][2], dtype=fill[name][1], device=dev) for name in want}
+    if len(t) > 0 and m > 0:
+        eng.ctx.call("im_cyl_stats", *_target_args(t), ptr(q), ptr(nrm), ptr(order), m, radius, half_length, ptr(out.get("count")),
+                     ptr(out.get("sums")), ptr(out.get("mean")), ptr(out.get("std")), ptr(out.get("steps")), eng.stream_ptr())
+    return _result(out, queries)
 
 
 def voxel_down_sample(points, voxel_size, colors=None, normals=None, engine=None):

@@ -456,6 +456,48 @@ int im_ball_features(im_ctx* ctx, const double* d_pts, const long long* d_perm, 
                      int nx, int ny, int nz, double radius, const int32_t* h_kinds, int n_kinds, int32_t* d_count, long long* d_sums,
                      double* d_eig, double* d_normal, double* d_feat, int32_t* d_steps, void* stream);
 
+/* ---- distances between two clouds (CloudCompare's cloud-to-cloud distance and M3C2, Lague et al. 2013; Open3D's
+ * `compute_point_cloud_distance`); csrc/cloud_distance.hip, csrc/cyl_point.h, csrc/knn_list.h. Neither tool is a dependency and the
+ * reference calls neither: every quantity has a definition of its own (tests/cloud_distance_oracle.py: bit-identical); PARITY
+ * WITH A CLOUDCOMPARE OR OPEN3D BINARY IS UNPINNED. The three query calls ask a TARGET cloud, given exactly as to the ball features (d_pts,
+ * d_perm, d_start, n, h_grid, nx, ny, nz, prepared by the k-NN's three calls above), at m external queries d_q [m][3] float64. A query may
+ * lie anywhere, far outside the target's grid included: its cell is clamped into the grid and the stop rules stay conservative. d_qorder
+ * [m] int64 or NULL is the order in which the waves take the queries (a permutation of 0..m-1; an entry outside is clamped); every output
+ * is addressed by the query's own index and does not depend on d_qorder. Every output may be NULL. One wave per query; the target in cell
+ * order lives in scratch of the context (shared with the k-NN). Enqueue only.
+ * The cross k-NN: the k (1..64) nearest target points of every query, ascending by d2, the lower original index first among equal
+ * distances, dropped iff d2 > radius2 (+inf: no radius). d_count [m] int32, d_idx [m][k] int32 and d_d2 [m][k] float64 (unused slots -1 /
+ * +inf), d_rings [m] int32 as the k-NN's (negated after the whole-cloud scan). A query with a non-finite coordinate gets count 0, rings 0.
+ * The cross ball: the ball features' sums around the query, offsets fl(p - q) relative to it; the query is no neighbour unless a target point
+ * coincides with it. d_count [m] int32, d_sums [m][10] int64, d_eig [m][3], d_normal [m][3] float64, d_steps [m] int32, all as the ball
+ * features define them. A query with a non-finite coordinate gets count 0, zero sums, NaN, steps 0.
+ * The cylinder statistics: d_nrm [m][3] float64 is used as given, never renormalised. A target point p is inside iff |t| <= half_length
+ * and d2 - t*t <= fl(radius * radius), u = fl(p - q), t = ((ux*nx) + (uy*ny)) + (uz*nz), d2 = ((ux*ux) + (uy*uy)) + (uz*uz): cap and wall
+ * are inside. it = rint(t / h), h = half_length * 2^-18, clamped to +-(2^18 + 1); exact int64 sums count, St, Stt. d_count [m] int32,
+ * d_sums [m][2] int64 (St, Stt), d_mean [m] = (St / count) * h (NaN for count 0), d_std [m] = sqrt(max(0, Stt / count - (St / count)^2) *
+ * (count / (count - 1))) * h (NaN for count < 2), d_steps [m] int32: the steps of 64 rows looked up or 64 candidates read over the
+ * cylinder's axis-aligned box of cells, negated where the box would have cost more row lookups than 1024 + n / 32 and the whole sorted
+ * cloud was scanned instead. A query with a non-finite coordinate or normal component gets count 0, NaN, steps 0.
+ * The M3C2 finish, elementwise over m core points from the counts and sums of two cylinder calls with the same half_length: d_dist [m] =
+ * mean2 - mean1, d_lod [m] = 1.96 * (sqrt(std1^2 / count1 + std2^2 / count2) + reg_error), NaN where either count is below min_points,
+ * d_sig [m] uint8 = |dist| > lod (0 on NaN).
+ * All four return -79, without launching and with the outputs untouched, for a null required pointer (d_pts, d_perm, d_start, h_grid, d_q;
+ * d_nrm; the counts and sums), n or m negative or above 2^26, a grid the k-NN refuses, k outside 1..64, radius2 negative or NaN, a radius
+ * or half-length that is not finite and positive, a radius (cross ball) or half-length times 2^-18 that is not a normal number, reg_error
+ * negative or not finite, min_points below 2. n == 0 or m == 0 returns 0 and launches nothing. */
+int im_knn_cross(im_ctx* ctx, const double* d_pts, const long long* d_perm, const int32_t* d_start, long long n, const double* h_grid, int nx,
+                 int ny, int nz, const double* d_q, const long long* d_qorder, long long m, int k, double radius2, int32_t* d_count,
+                 int32_t* d_idx, double* d_d2, int32_t* d_rings, void* stream);
+int im_ball_cross(im_ctx* ctx, const double* d_pts, const long long* d_perm, const int32_t* d_start, long long n, const double* h_grid, int nx,
+                  int ny, int nz, const double* d_q, const long long* d_qorder, long long m, double radius, int32_t* d_count, long long* d_sums,
+                  double* d_eig, double* d_normal, int32_t* d_steps, void* stream);
+int im_cyl_stats(im_ctx* ctx, const double* d_pts, const long long* d_perm, const int32_t* d_start, long long n, const double* h_grid, int nx,
+                 int ny, int nz, const double* d_q, const double* d_nrm, const long long* d_qorder, long long m, double radius,
+                 double half_length, int32_t* d_count, long long* d_sums, double* d_mean, double* d_std, int32_t* d_steps, void* stream);
+int im_m3c2_finish(im_ctx* ctx, const int32_t* d_count1, const long long* d_sums1, const int32_t* d_count2, const long long* d_sums2,
+                   long long m, double half_length, double reg_error, int min_points, double* d_dist, double* d_lod, uint8_t* d_sig,
+                   void* stream);
+
 /* ---- volume variations (`scripts/pcd_postprocessing/volume_variations.py`; `post_processing/cloudcompare_fun.py`:
  * `DemOfDifference.compute_volume` over CloudCompare's `ComputeVolume25D`; `post_processing/open3d_fun.py`: `filter_pcd_by_polyline`);
  * csrc/dod.hip, csrc/dod_cell.h. The DEM of difference of P pairs (ground, ceil) over E clouds that lie one behind the other in d_pts
