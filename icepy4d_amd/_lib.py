@@ -131,6 +131,17 @@ SIGNATURES = {
     "im_mesh_in_hull": [_P, _P, _L, _P, _I, _P, _P],
     "im_mesh_sample_table": [_P, _P, _L, _P, _L, _L, _P, _P, _P, _P],
     "im_mesh_sample": [_P, _P, _L, _P, _L, _P, _L, _L, _P, _P, _P, _P, _P, _P, _P],
+    "im_poisson_max_depth": [],
+    "im_poisson_max_points": [],
+    "im_poisson_splat": [_P, _P, _P, _L, _P, _I, _P, _P],
+    "im_poisson_divergence": [_P, _P, _I, _D, _P, _P],
+    "im_poisson_jacobi": [_P, _P, _P, _I, _D, _P, _P],
+    "im_poisson_restrict": [_P, _P, _P, _I, _D, _P, _P, _P],
+    "im_poisson_prolong": [_P, _P, _I, _P, _P],
+    "im_poisson_coarse": [_P, _P, _D, _P, _P],
+    "im_poisson_reduce": [_P, _P, _P, _L, _P, _P],
+    "im_poisson_census": [_P, _P, _D, _I, _P, _P, _P, _P],
+    "im_poisson_extract": [_P, _P, _P, _D, _I, _P, _P, _P, _L, _L, _P, _P, _P, _P],
 }
 
 

@@ -1,7 +1,8 @@
 """The point-cloud helpers of the reference's `post_processing/open3d_fun.py` that need no Open3D here: `filter_pcd_by_polyline` (the
 crop of a cloud to the glacier outline, on the device: csrc/dod.hip `crop_polygon_kernel`) and `read_and_merge_point_clouds`, both on
 `core.PointCloud`, and `MeshingPoisson`: of its eight steps the Poisson solve is a hook (an octree solve is no data-parallel pass over
-points or cells), everything behind it runs on the device (`triangle_mesh.py`, csrc/mesh.hip).
+points or cells), everything behind it runs on the device (`triangle_mesh.py`, csrc/mesh.hip). `poisson.poisson_reconstruct`
+has the hook's signature: a Poisson reconstruction on the dense grid of the finest octree level (csrc/poisson.hip), not Open3D's solver.
 
 The reference tests the points with matplotlib's `Path.contains_points`; here the even-odd crossing rule in float64 is restated
 (include/icematch.h `im_crop_polygon`; tests/dod_oracle.py, bit-identical). The two agree on every point that does not lie on an edge
@@ -104,7 +105,7 @@ class MeshingPoisson:
     """The reference's class (`open3d_fun.py: MeshingPoisson`) with its defaults, cfg keys (its spelling `min_mesh_denisty` included),
     method names, step order, log and timer labels and output names `mesh_{date}.ply` / `sampled_{date}.ply`.
 
-    The Poisson solve is not provided. `poisson_meshing` calls `reconstruct(points, normals, depth=cfg.poisson_depth, width=0, scale=1.1,
+    The Poisson solve is not built in (`reconstruct=poisson.poisson_reconstruct` supplies one). `poisson_meshing` calls `reconstruct(points, normals, depth=cfg.poisson_depth, width=0, scale=1.1,
     linear_fit=False)`, which returns `(vertices, triangles, densities)`; without the hook it reads `cfg["mesh_path"]`, a PLY with a vertex
     property `density`. `orient_triangles` is not provided either: the supplied surface is taken as oriented. Everything else runs on the
     device: SOR (50, 1.5) and normals (radius 1, max_nn 30) of `utils/point_cloud_filters.py`, the mesh filters, the hull crop (qhull gives

@@ -216,6 +216,16 @@ class TriangleMesh:
         """From the tuple of `VoxelGrid.to_box_mesh`: `TriangleMesh.from_arrays(*vg.to_box_mesh())`."""
         return cls(vertices, triangles, vertex_colors, engine=engine)
 
+    @classmethod
+    def create_from_point_cloud_poisson(cls, pcd, depth=8, width=0, scale=1.1, linear_fit=False, engine=None):
+        """(mesh, densities) under Open3D's name: the surface of `poisson.poisson_reconstruct` over the points and normals of `pcd`, with
+        the densities also as the mesh's vertex attribute `density`. Not Open3D's solver (see `poisson.py`); the cloud needs normals."""
+        from .poisson import poisson_reconstruct
+        if pcd.normals is None:
+            raise ValueError("the point cloud has no normals: estimate them first")
+        vertices, triangles, densities = poisson_reconstruct(pcd.points, pcd.normals, depth=depth, width=width, scale=scale, linear_fit=linear_fit, engine=engine)
+        return cls(vertices, triangles, attributes={"density": densities}, engine=engine), densities
+
     def __len__(self):
         return len(self.vertices)
 

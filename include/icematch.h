@@ -644,6 +644,55 @@ int im_mesh_sample(im_ctx* ctx, const double* d_vertices, long long n_vertices, 
                    long long n_samples, long long seed, const double* d_vertex_colors, const double* d_vertex_normals, double* d_points, double* d_colors,
                    double* d_normals, int32_t* d_triangle_index, void* stream);
 
+/* Poisson surface reconstruction of an oriented cloud on the dense grid of the finest octree level (csrc/poisson.hip; definition in
+ * DESIGN §4, restated in tests/poisson_oracle.py and csrc/poisson_node.h). It stands in for Open3D's solve in the reference's
+ * `post_processing/open3d_fun.py:191-203` (`MeshingPoisson.poisson_meshing`: `create_from_point_cloud_poisson(pcd, depth, width=0,
+ * scale=1.1, linear_fit=False)` and its densities). Open3D's adaptive-octree solver is not reproduced and parity with an Open3D binary
+ * is unpinned. A grid is h_grid [4] float64 in HOST memory (origin x, y, z and the cell size h > 0) and a depth in [2, 9]: R = 2^depth
+ * cells and M = R + 1 nodes per axis, node (i, j, k) at (k M + j) M + i. Fields are [M^3] float64 device arrays of the caller.
+ * float64 arithmetic with contraction off.
+ * im_poisson_max_depth: 9. im_poisson_max_points: the most samples of a splat and vertices or triangles of an extraction (2^26).
+ * im_poisson_splat: d_fields [4][M^3] = W, V_x, V_y, V_z. Per sample and axis u = (p - o) / h, the cell c = floor u clamped to
+ *   [0, R - 1], the fraction t = u - c clamped to [0, 1]; the unit normal n / sqrt((n_x^2 + n_y^2) + n_z^2); at each of the 8 nodes of
+ *   the cell the weight w = (w_x w_y) w_z, w_a = t_a or 1 - t_a; W receives rint(w 2^32) and V_a rint((w n_a) 2^32) as int64 (a NaN adds
+ *   nothing), summed by integer atomics - exact in any order, below 2^58 for 2^26 samples - and the fields are the sums times 2^-32.
+ * im_poisson_divergence: d_vectors [3][M^3]; d_rhs = (((V_x[i+1] - V_x[i-1]) + (V_y[j+1] - V_y[j-1])) + (V_z[k+1] - V_z[k-1])) / (2 h)
+ *   on the interior nodes, 0 on the boundary.
+ * im_poisson_jacobi: d_out = u + 6/7 (((s - h2 f) / 6) - u) on the interior nodes, s = ((((x- + x+) + y-) + y+) + z-) + z+ of u, and u
+ *   on the boundary; h2 is the squared node spacing of the level. d_out may not be d_u.
+ * im_poisson_restrict: d_residual [M^3] = f - (s - 6 u) / h2 (0 on the boundary), then d_coarse_f [Mc^3], Mc = 2^(depth-1) + 1 = its
+ *   full weighting (1/4 a + 1/2 b) + 1/4 c along x, then y, then z on the interior coarse nodes, 0 on the boundary. d_residual may be
+ *   neither d_u nor d_f.
+ * im_poisson_prolong: d_u [M^3] += the trilinear interpolation of d_coarse_e [Mc^3] along x, then y, then z (a node between two coarse
+ *   nodes takes 1/2 (a + b)), on the interior nodes.
+ * im_poisson_coarse: the level of 3 nodes per axis: d_u [27] = 0 but for its centre, (h2 f) / -6.
+ * im_poisson_reduce: d_out [ceil(n / 1024)]: per chunk of 1024 items v = a, or a b with d_b (NULL = none), zero beyond n: lane t of 256
+ *   takes ((v[t] + v[t+256]) + v[t+512]) + v[t+768], then lane t += lane t + s for s = 128 .. 1. Applied again to its own output until
+ *   one item is left it is the ordered sum of the iso-value, iso = sum (W chi) / sum W.
+ * im_poisson_census: a node is inside iff chi < iso. d_mask [M^3] uint8: bit d - 1 = the edge from the node towards direction d = 1..7
+ *   (bit 0 of d = +x, bit 1 = +y, bit 2 = +z) stays in the grid and its ends differ; d_base [M^3] int32 = the crossing edges of all nodes
+ *   before it (the first vertex of the node); d_counts [2] int64 = the vertices and the triangles.
+ * im_poisson_extract: d_vertices [V][3], d_weights [V] in ascending edge key 8 node + d: t = (iso - f_a) / (f_b - f_a) from the lower
+ *   node a, position (o + i h) + t (step h) per axis, weight w_a + t (w_b - w_a) of d_weight_field. d_triangles [T][3] int32 ordered by
+ *   (cell, tetrahedron, triangle): the six Kuhn tetrahedra of a cell in lexicographic order of their axis orders, the cases by rule
+ *   (poisson_node.h), wound so that the normal points towards higher chi. d_mask and d_base are the census's; ones that are not lead to
+ *   meaningless figures but to no access outside a buffer.
+ * All return -80, without launching and with the outputs untouched, for a null required pointer, a depth outside [2, 9], a negative
+ * count, more than 2^26 points, vertices or triangles, a grid that is not finite or has h <= 0, and buffers that may not coincide.
+ * Zero-size calls return 0 and launch nothing. */
+int im_poisson_max_depth(void);
+int im_poisson_max_points(void);
+int im_poisson_splat(im_ctx* ctx, const double* d_points, const double* d_normals, long long n_points, const double* h_grid, int depth, double* d_fields, void* stream);
+int im_poisson_divergence(im_ctx* ctx, const double* d_vectors, int depth, double h, double* d_rhs, void* stream);
+int im_poisson_jacobi(im_ctx* ctx, const double* d_u, const double* d_f, int depth, double h2, double* d_out, void* stream);
+int im_poisson_restrict(im_ctx* ctx, const double* d_u, const double* d_f, int depth, double h2, double* d_residual, double* d_coarse_f, void* stream);
+int im_poisson_prolong(im_ctx* ctx, const double* d_coarse_e, int depth, double* d_u, void* stream);
+int im_poisson_coarse(im_ctx* ctx, const double* d_f, double h2, double* d_u, void* stream);
+int im_poisson_reduce(im_ctx* ctx, const double* d_a, const double* d_b, long long n, double* d_out, void* stream);
+int im_poisson_census(im_ctx* ctx, const double* d_chi, double iso, int depth, unsigned char* d_mask, int32_t* d_base, long long* d_counts, void* stream);
+int im_poisson_extract(im_ctx* ctx, const double* d_chi, const double* d_weight_field, double iso, int depth, const double* h_grid, const unsigned char* d_mask,
+                       const int32_t* d_base, long long n_vertices, long long n_triangles, double* d_vertices, double* d_weights, int32_t* d_triangles, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,374 @@
+"""The Poisson surface reconstruction without a device: properties of the numpy restatement alone (tests/poisson_oracle.py, the
+definition) on the shared cases (tests/poisson_cases.py); the kernels' own arithmetic compiled for the host (csrc/poisson_node.h through
+tests/poisson_host_harness.cpp, a stand-alone program built plain and with the address and undefined-behaviour sanitizers) against values
+the restatement dumps, bit for bit; the ABI, the refusals of the Python layer and the hook that stays a hook.
+
+Bounds. They are the issue's, not measured ones; the observed values stand next to the asserts.
+ - every V-cycle from the second on at least halves the max-norm residual (two-grid theory for 2 + 2 damped Jacobi sweeps with full
+   weighting gives about 0.2 per cycle; observed 0.15 to 0.25 on every case);
+ - on the spheres the zero set of chi - iso lies within h / 2 of the unit sphere on 500 seeded rays and no node farther than h from it is
+   on the wrong side (h / 2 is the resolution of the grid: the splat spreads a sample over one cell);
+ - iso equals the mean over the samples of chi interpolated with the samples' quantised trilinear weights to 1e-12 relative: the two are
+   the same sum of products in two orders, about 10^5 terms with rounding 1.1e-16 each;
+ - the mesh is closed and oriented on every case and of genus 0 on the spheres; permuting the points changes no bit; density is higher by
+   about log2(2) / 2 = 0.5 where the sampling is twice as dense."""
+import os
+import re
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import toolchain  # noqa: E402
+import poisson_cases as PC  # noqa: E402
+import poisson_oracle as O  # noqa: E402
+
+from icepy4d_amd.post_processing import poisson as P  # noqa: E402  (the feature under test: without it nothing here can pass)
+
+NAMES = ["im_poisson_max_depth", "im_poisson_max_points", "im_poisson_splat", "im_poisson_divergence", "im_poisson_jacobi", "im_poisson_restrict",
+         "im_poisson_prolong", "im_poisson_coarse", "im_poisson_reduce", "im_poisson_census", "im_poisson_extract"]
+
+
+def same(a, b):
+    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
+    return a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes()
+
+
+def interpolate(field, origin, h, pts):
+    """Trilinear interpolation of a node field [z, y, x] at points inside the cube."""
+    R = field.shape[0] - 1
+    u = (pts - origin) / h
+    c = np.clip(np.floor(u), 0, R - 1).astype(np.int64)
+    t = u - c
+    out = np.zeros(len(pts))
+    for corner in range(8):
+        d = [(corner >> a) & 1 for a in range(3)]
+        w = np.prod([t[:, a] if d[a] else 1 - t[:, a] for a in range(3)], 0)
+        out += w * field[c[:, 2] + d[2], c[:, 1] + d[1], c[:, 0] + d[0]]
+    return out
+
+
+# ---- (a) the restatement alone ---------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", [n for n in PC.ALL if PC.case(n)["cycles"] > 1])
+def test_every_cycle_from_the_second_on_halves_the_residual(name):
+    f = PC.oracle(name)
+    res = [O.residual_norm(u, f["rhs"], f["h"]) for u in f["chis"]]
+    ratios = [res[i + 1] / res[i] for i in range(len(res) - 1)]
+    print(name, "residual ratios", [round(r, 3) for r in ratios])          # observed: 0.15 .. 0.25
+    assert len(ratios) == 7 and max(ratios) <= 0.5, ratios
+
+
+@pytest.mark.parametrize("name", PC.SPHERES)
+def test_zero_set_lies_on_the_sphere(name):
+    f = PC.oracle(name)
+    h, origin, M = f["h"], f["origin"], f["chi"].shape[0]
+    rng = np.random.default_rng(11)
+    d = rng.normal(size=(500, 3))
+    d /= np.linalg.norm(d, axis=1)[:, None]
+    radii = np.linspace(0.6, 1.4, 1601)                                   # steps of 0.0005: far below h / 2 >= 0.017
+    g = np.stack([interpolate(f["chi"], origin, h, r * d) - f["iso"] for r in radii], 1)       # [ray, radius]
+    cross = (g[:, :-1] < 0) != (g[:, 1:] < 0)
+    assert cross.any(1).all(), "a ray without a crossing"
+    mid = 0.5 * (radii[:-1] + radii[1:])
+    worst = float(np.abs(np.where(cross, mid[None, :], 1.0) - 1.0).max()) / h
+    print(name, "zero set within", round(worst, 3), "h of the sphere")     # observed: 0.19 h, 0.14 h, 0.13 h
+    assert worst <= 0.5
+    assert (g[:, 0] < 0).all() and (g[:, -1] >= 0).all()                   # lower inside, with outward normals
+    ax = [origin[a] + np.arange(M) * h for a in range(3)]
+    z, y, x = np.meshgrid(ax[2], ax[1], ax[0], indexing="ij")
+    r = np.sqrt(x * x + y * y + z * z)
+    far = np.abs(r - 1.0) > h
+    assert np.array_equal((f["chi"] < f["iso"])[far], (r < 1.0)[far])
+    assert float(np.abs(np.linalg.norm(f["vertices"], axis=1) - 1.0).max()) <= 0.5 * h
+
+
+@pytest.mark.parametrize("name", PC.ALL)
+def test_iso_is_the_mean_of_chi_at_the_samples(name):
+    c, f = PC.case(name), PC.oracle(name)
+    cell, t = O.cells(c["points"], f["origin"], f["h"], f["depth"])
+    num = den = 0.0
+    for corner in range(8):
+        q = O.quantise(O.corner_weight(t, corner)).astype(np.float64)
+        chi = f["chi"][cell[:, 2] + ((corner >> 2) & 1), cell[:, 1] + ((corner >> 1) & 1), cell[:, 0] + (corner & 1)]
+        num, den = num + float((q * chi).sum()), den + float(q.sum())
+    mean = num / den
+    print(name, "iso", f["iso"], "difference", abs(mean - f["iso"]), "allowed", 1e-12 * abs(f["iso"]))      # observed: at most 8e-15 relative
+    # (lattice_d2 has every sample on the boundary of the cube, where chi is 0: both are exactly 0)
+    assert abs(mean - f["iso"]) <= 1e-12 * abs(f["iso"])
+
+
+@pytest.mark.parametrize("name", PC.ALL)
+def test_mesh_is_closed_and_oriented(name):
+    f = PC.oracle(name)
+    v, t = f["vertices"], f["triangles"]
+    assert len(t) > 0 and t.min() == 0 and t.max() == len(v) - 1 and len(np.unique(t)) == len(v)      # every vertex is used
+    once, paired, E = PC.edge_census(t)
+    assert once and paired                                                 # every undirected edge in exactly two triangles, once each way
+    assert np.array_equal(f["keys"], np.sort(f["keys"])) and len(np.unique(f["keys"])) == len(v)
+    if name in PC.SPHERES:
+        assert len(v) - E + len(t) == 2                                    # genus 0
+        n = np.cross(v[t[:, 1]] - v[t[:, 0]], v[t[:, 2]] - v[t[:, 0]])
+        assert ((n * v[t].mean(1)).sum(1) > 0).all()                       # outward: along the input normals
+
+
+def test_winding_follows_the_gradient_on_every_case_of_every_tetrahedron():
+    for tet in range(6):
+        corners = tet_corners = O.tet_corners(tet)
+        assert sorted(tet_corners) == tet_corners and tet_corners[0] == 0 and tet_corners[3] == 7
+        for code in range(16):
+            tris = O.TET_CASES[tet][code]
+            assert len(tris) == {0: 0, 1: 1, 2: 2, 3: 1, 4: 0}[bin(code).count("1")]
+            for tri in tris:
+                for lo, hi in tri:
+                    assert ((code >> lo) & 1) != ((code >> hi) & 1) and corners[lo] & corners[hi] == corners[lo]
+    faces = {}                                                             # the diagonal of every cube face is shared by the two cells on it
+    for tet in range(6):
+        c = O.tet_corners(tet)
+        for a in range(4):
+            for b in range(a + 1, 4):
+                faces.setdefault(c[a] ^ c[b], set()).add((c[a], c[b]))
+    assert sorted(faces) == [1, 2, 3, 4, 5, 6, 7]
+
+
+def test_a_permutation_of_the_points_changes_no_bit():
+    c, f = PC.case("sphere_d4"), PC.oracle("sphere_d4")
+    perm = np.random.default_rng(5).permutation(len(c["points"]))
+    g = O.field(c["points"][perm], c["normals"][perm], depth=c["depth"])
+    assert same(g["W"], f["W"]) and same(g["V"], f["V"]) and same(g["chi"], f["chi"]) and g["iso"] == f["iso"]
+    v, t, w, _ = O.extract(g["chi"], g["W"], g["iso"], g["origin"], g["h"], g["depth"])
+    assert same(v, f["vertices"]) and same(t, f["triangles"]) and same(w, f["weights"])
+
+
+def test_density_rises_with_the_sampling():
+    f = PC.oracle("two_densities_d4")
+    z, d = f["vertices"][:, 2], f["density"]
+    upper, lower = float(d[z > 0.3].mean()), float(d[z < -0.3].mean())
+    print("density: upper", upper, "lower", lower)                         # observed: 5.47 and 4.90, 0.57 apart; log2(2) / 2 = 0.5 is the expectation
+    assert upper > lower
+    assert same(O.density(np.array([0.0, 4.0 ** -4, 1.0, 4.0]), 4), np.array([0.0, 0.0, 4.0, 5.0]))
+    assert same(P.density_of(f["weights"], f["depth"]), d)
+
+
+def test_sums_cannot_overflow():
+    assert O.MAX_POINTS * (2 ** 32 + 1) < 2 ** 63 and O.MAX_POINTS == P.MAX_POINTS == 2 ** 26
+    t = np.array([[0.0, 1.0, 0.5]])
+    assert max(int(O.quantise(O.corner_weight(t, c))[0]) for c in range(8)) <= 2 ** 32
+
+
+# ---- (b) the host build of the kernels' arithmetic ---------------------------------------------------------------------------------------------
+def dump(directory, name, array, dtype):
+    np.ascontiguousarray(array, dtype).tofile(os.path.join(directory, name + ".bin"))
+
+
+def write_harness_inputs(d):
+    rng = np.random.default_rng(21)
+    # the splat: the front's first samples and the lattice (samples on nodes and on the upper faces, where the cell clamps)
+    c = PC.case("lattice_d2")
+    f = PC.oracle("lattice_d2")
+    pts = np.concatenate([c["points"], rng.random((200, 3)) * 4.0])
+    nrm = np.concatenate([c["normals"], rng.normal(size=(200, 3))])
+    cell, t = O.cells(pts, f["origin"], f["h"], 2)
+    unit = O.unit_normals(nrm)
+    add = np.zeros((len(pts), 8, 4), np.int64)
+    for corner in range(8):
+        w = O.corner_weight(t, corner)
+        add[:, corner, 0] = O.quantise(w)
+        for a in range(3):
+            add[:, corner, 1 + a] = O.quantise(w * unit[:, a])
+    sums = O.splat_sums(pts, nrm, f["origin"], f["h"], 2)
+    dump(d, "splat_meta", [*f["origin"], f["h"], 4.0], np.float64)
+    dump(d, "splat_points", pts, np.float64)
+    dump(d, "splat_normals", nrm, np.float64)
+    dump(d, "splat_cells", cell, np.int64)
+    dump(d, "splat_fractions", t, np.float64)
+    dump(d, "splat_addends", add, np.int64)
+    dump(d, "splat_sums", sums, np.int64)
+    dump(d, "splat_fields", sums.astype(np.float64) * 2.0 ** -32, np.float64)
+    # the stencils on a 9^3 grid over a 5^3 one
+    M, h = 9, 0.37
+    h2 = h * h
+    V, u, fr, e = rng.normal(size=(3, M, M, M)), np.zeros((M, M, M)), rng.normal(size=(M, M, M)), np.zeros((5, 5, 5))
+    u[1:-1, 1:-1, 1:-1] = rng.normal(size=(M - 2,) * 3)
+    e[1:-1, 1:-1, 1:-1] = rng.normal(size=(3, 3, 3))
+    res = O.residual(u, fr, h2)
+    up = u.copy()
+    up[1:-1, 1:-1, 1:-1] = u[1:-1, 1:-1, 1:-1] + O.prolong(e)[1:-1, 1:-1, 1:-1]
+    dump(d, "grid_meta", [M, h, h2], np.float64)
+    for name, a in (("grid_v", V), ("grid_u", u), ("grid_f", fr), ("grid_e", e), ("grid_rhs", O.divergence(V, h)), ("grid_jacobi", O.jacobi(u, fr, h2)),
+                    ("grid_residual", res), ("grid_restricted", O.restrict(res)), ("grid_prolonged", up),
+                    ("grid_coarse", [(h2 * fr.ravel()[0]) / -6.0])):
+        dump(d, name, a, np.float64)
+    # edges: the crossings of a case, with their interpolation
+    f = PC.oracle("sphere_d4")
+    Mg = f["chi"].shape[0]
+    node, dirn = f["keys"] // 8, f["keys"] % 8
+    upper = node + (dirn & 1) + ((dirn >> 1) & 1) * Mg + ((dirn >> 2) & 1) * Mg * Mg
+    chi, W = f["chi"].ravel(), f["W"].ravel()
+    rows, out = [], []
+    for a in range(3):
+        ia = [node % Mg, (node // Mg) % Mg, node // (Mg * Mg)][a]
+        step = (dirn >> a) & 1
+        rows.append(np.stack([chi[node], chi[upper], np.full(len(node), f["iso"]), np.full(len(node), f["origin"][a]), ia, step,
+                              np.full(len(node), f["h"]), W[node], W[upper]], 1))
+        tt = (f["iso"] - chi[node]) / (chi[upper] - chi[node])
+        out.append(np.stack([tt, f["vertices"][:, a], f["weights"]], 1))
+    rows, out = np.concatenate(rows), np.concatenate(out)
+    dump(d, "edge_in", rows, np.float64)
+    dump(d, "edge_out", out, np.float64)
+    dump(d, "edge_inside", np.stack([rows[:, 0] < rows[:, 2], rows[:, 1] < rows[:, 2]], 1), np.int64)
+    # the tetrahedra
+    table = []
+    for tet in range(6):
+        for code in range(16):
+            tris = O.TET_CASES[tet][code]
+            row = list(O.tet_corners(tet)) + [len(tris)]
+            for q in range(2):
+                for e_ in range(3):
+                    row += list(tris[q][e_]) if q < len(tris) else [-1, -1]
+            table.append(row)
+    dump(d, "tet_cases", table, np.int32)
+    dump(d, "popcount", [bin(m).count("1") for m in range(128)], np.int32)
+    # depth 9: node (512, 512, 512), the last edge key, the bytes of four fields and of the vertex table, the scratch of the scans
+    M9 = 513
+    N9 = M9 ** 3
+    up256 = lambda b: (b + 255) // 256 * 256  # noqa: E731
+    node9 = (512 * M9 + 512) * M9 + 512
+    assert node9 == N9 - 1 and 2 ** 30 < node9 * 8 + 7 < 2 ** 31 and 4 * N9 * 8 > 2 ** 32        # keys would still fit 32 bits, byte offsets do not
+    dump(d, "depth9", [M9, N9, node9, node9 * 8 + 7, 4 * N9 * 8, N9 * 4, node9, up256((N9 + 255) // 256 * 8) + 256, 2 ** 26, 2, 9, 1024], np.int64)
+
+
+def build_harness(tmp, sanitize):
+    if not os.path.exists(toolchain.CLANGXX):
+        pytest.skip("no clang++")
+    os.makedirs(os.path.join(tmp, "hip"), exist_ok=True)
+    with open(os.path.join(tmp, "hip", "hip_runtime.h"), "w") as f:
+        f.write(toolchain.HIP_STUB)
+    exe = os.path.join(tmp, "poisson_host_harness" + ("_san" if sanitize else ""))
+    flags = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-g", "-O1"] if sanitize else ["-O2"]
+    r = subprocess.run([toolchain.CLANGXX, "-std=c++17", "-ffp-contract=off", *flags, "-I" + tmp, "-I" + toolchain.CSRC,
+                        os.path.join(ROOT, "tests", "poisson_host_harness.cpp"), "-o", exe], capture_output=True, text=True)
+    if sanitize and r.returncode != 0 and "clang_rt" in r.stderr and "poisson_host_harness.cpp:" not in r.stderr:
+        pytest.skip("this clang++ has no sanitizer runtimes")
+    assert r.returncode == 0, r.stderr[-2000:]
+    return exe
+
+
+@pytest.fixture(scope="module")
+def harness_dir(tmp_path_factory):
+    d = str(tmp_path_factory.mktemp("poisson_host"))
+    write_harness_inputs(d)
+    return d
+
+
+@pytest.mark.parametrize("sanitize", [False, True], ids=["plain", "asan_ubsan"])
+def test_host_build_equals_the_restatement_bit_for_bit(harness_dir, sanitize):
+    exe = build_harness(harness_dir, sanitize)
+    r = subprocess.run([exe, harness_dir], capture_output=True, text=True)
+    print(r.stdout)
+    assert r.returncode == 0 and r.stdout.strip().endswith("PASSED"), r.stdout[-3000:] + r.stderr[-3000:]
+    assert r.stdout.count("\nok ") + r.stdout.startswith("ok ") == 15 and "DIFFERENT" not in r.stdout and "MISSING" not in r.stdout
+
+
+# ---- (c) the ABI, the refusals, the hook -------------------------------------------------------------------------------------------------------
+def test_abi_is_declared_bound_and_exported():
+    from icepy4d_amd import _lib
+    with open(os.path.join(ROOT, "include", "icematch.h")) as f:
+        header = f.read()
+    for n in NAMES:
+        m = re.search(r"\nint " + n + r"\(([^;]*)\);", header)
+        assert m and n in _lib.SIGNATURES, n
+        args = [a for a in m.group(1).split(",") if a.strip() != "void"]
+        assert len(args) == len(_lib.SIGNATURES[n]), (n, len(args), len(_lib.SIGNATURES[n]))
+    assert "-80" in header and "open3d_fun.py:191-203" in header
+    lib = _lib.load()
+    assert lib.im_poisson_max_depth() == O.MAX_DEPTH == P.MAX_DEPTH == 9 and P.MIN_DEPTH == O.MIN_DEPTH == 2
+    assert lib.im_poisson_max_points() == O.MAX_POINTS
+    assert P.CHUNK == O.CHUNK and P.CYCLES == O.CYCLES == 8
+
+
+def test_the_kernels_spill_nothing(tmp_path):
+    res = toolchain.kernel_resources(toolchain.device_listing("poisson.hip", str(tmp_path)))
+    mine = {k: v for k, v in res.items() if "poisson_" in k or "Poisson" in k}
+    assert len(mine) >= 11 + 4, sorted(res)                               # eleven kernels and the two scans' templates
+    for k, f in mine.items():
+        assert f["vgpr_spill_count"] == 0 and f["sgpr_spill_count"] == 0, (k, dict(f))
+        if "PoissonCellScan" not in k:                                     # the triangle writer indexes its small case arrays at run time
+            assert f["private_segment_fixed_size"] == 0, (k, dict(f))
+    assert [f["group_segment_fixed_size"] for k, f in mine.items() if "reduce" in k] == [256 * 8]
+
+
+REFUSALS = [
+    ("differing lengths", dict(normals=np.ones((3, 3)))),
+    ("no points", dict(points=np.zeros((0, 3)), normals=np.zeros((0, 3)))),
+    ("not [n, 3]", dict(points=np.zeros((4, 2)), normals=np.zeros((4, 2)))),
+    ("a NaN point", dict(points=np.array([[0, 0, np.nan], [1, 0, 0], [0, 1, 0], [0, 0, 1.0]]))),
+    ("an infinite normal", dict(normals=np.array([[0, 0, np.inf], [1, 0, 0], [0, 1, 0], [0, 0, 1.0]]))),
+    ("a zero-length normal", dict(normals=np.array([[0, 0, 0], [1, 0, 0], [0, 1, 0], [0, 0, 1.0]]))),
+    ("depth 1", dict(depth=1)),
+    ("depth 10", dict(depth=10)),
+    ("depth 2.5", dict(depth=2.5)),
+    ("scale below 1", dict(scale=0.99)),
+    ("a width that asks for depth 10", dict(width=1.1 / 1000)),
+    ("a width that asks for depth 1", dict(width=0.6)),
+    ("no cycle", dict(cycles=0)),
+    ("a degenerate cloud", dict(points=np.ones((4, 3)))),
+    ("a grid of depth 12", dict(grid=(np.zeros(3), 0.1, 12))),
+    ("a grid without a cell size", dict(grid=(np.zeros(3), 0.0, 4))),
+]
+
+
+@pytest.mark.parametrize("what,change", REFUSALS, ids=[r[0] for r in REFUSALS])
+def test_python_layer_refuses_before_any_device_work(what, change):
+    args = dict(points=np.array([[0, 0, 0], [1, 0, 0], [0, 1, 0], [0, 0, 1.0]]), normals=np.array([[0, 0, -1], [1, 0, 0], [0, 1, 0], [0, 0, 1.0]]))
+    args.update(change)
+    with pytest.raises(ValueError):
+        P.poisson_field(**args)                                            # no device is present or asked for: a ValueError, not a RuntimeError
+    oracle_args = {k: v for k, v in args.items() if k != "engine"}
+    with pytest.raises(ValueError):
+        O.field(**oracle_args)
+
+
+def test_a_width_replaces_the_depth():
+    mn, mx = np.zeros(3), np.array([1.0, 0.5, 0.25])
+    assert P.grid_of(mn, mx, depth=8, width=1.1 / 32, scale=1.1)[2] == 5 and P.grid_of(mn, mx, depth=8, width=1.1 / 33, scale=1.1)[2] == 6
+    c = PC.case("front_d6")
+    origin, h, depth = P.grid_of(c["points"].min(0), c["points"].max(0), 6, 0, 1.1)
+    want = O.grid_of(c["points"], 6, 0, 1.1)
+    assert same(origin, want[0]) and h == want[1] and depth == want[2] == 6
+
+
+def test_no_cpu_fallback():
+    import torch
+    if torch.cuda.is_available():
+        pytest.skip("GPU present")
+    c = PC.case("sphere_d2")
+    with pytest.raises(RuntimeError):
+        P.poisson_reconstruct(c["points"], c["normals"], depth=2)
+
+
+def test_meshing_poisson_without_a_hook_still_raises(tmp_path):
+    from icepy4d_amd.core import PointCloud
+    from icepy4d_amd.post_processing import MeshingPoisson, TriangleMesh, poisson_reconstruct
+    from icepy4d_amd import meshing
+    pcd = PointCloud(points3d=np.random.default_rng(1).normal(0, 1, (30, 3)))
+    pcd.normals = np.ones((30, 3))
+    pcd.write_ply(tmp_path / "dense_2022_01_01.ply")
+    mp = MeshingPoisson(tmp_path / "dense_2022_01_01.ply", tmp_path / "out", {"do_SOR": False})
+    mp.read_pcd()
+    with pytest.raises(NotImplementedError):
+        mp.poisson_meshing()
+    assert MeshingPoisson(tmp_path / "dense_2022_01_01.ply", tmp_path / "out", {}, reconstruct=poisson_reconstruct).reconstruct is poisson_reconstruct
+    assert meshing.poisson_mesh_series([], tmp_path / "out") == []
+    assert callable(TriangleMesh.create_from_point_cloud_poisson)
+    pcd.normals = None
+    with pytest.raises(ValueError):
+        TriangleMesh.create_from_point_cloud_poisson(pcd, depth=3)
+
+
+@pytest.mark.parametrize("module", ["icepy4d_amd.post_processing.poisson", "icepy4d_amd.meshing", "icepy4d_amd.post_processing"])
+def test_module_imports_as_the_first_import(module):
+    r = subprocess.run([sys.executable, "-c", f"import {module}"], cwd=ROOT, capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-2000:]
