@@ -107,6 +107,10 @@ SIGNATURES = {
     "im_ball_cross": [_P, _P, _P, _P, _L, _P, _I, _I, _I, _P, _P, _L, _D, _P, _P, _P, _P, _P, _P],
     "im_cyl_stats": [_P, _P, _P, _P, _L, _P, _I, _I, _I, _P, _P, _P, _L, _D, _D, _P, _P, _P, _P, _P, _P],
     "im_m3c2_finish": [_P, _P, _P, _P, _P, _L, _D, _D, _I, _P, _P, _P, _P],
+    "im_icp_chunk": [],
+    "im_transform_points": [_P, _P, _P, _P, _L, _I, _P],
+    "im_icp_accumulate": [_P, _P, _L, _P, _P, _L, _P, _P, _P, _I, _L, _P, _P],
+    "im_icp_finish": [_P, _P, _L, _L, _P, _P, _I, _P, _P],
     "im_dod_chunk": [],
     "im_dod_max_cells": [],
     "im_dod_max_batch_cells": [],

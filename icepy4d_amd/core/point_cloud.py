@@ -150,6 +150,16 @@ class PointCloud:
         from ..post_processing.cloud_distance import cloud_to_cloud_distance
         return cloud_to_cloud_distance(self.points, target, engine=engine).distance
 
+    def transform(self, T, engine=None) -> "PointCloud":
+        """A new cloud under the rigid 4x4 `T` (last row (0, 0, 0, 1)), on the device (`utils/transformations.py`, csrc/icp.hip): the
+        points transformed, the normals rotated without the translation, the colours kept."""
+        from ..utils.transformations import check_transform, transform_points
+        T = check_transform(T)
+        out = PointCloud(points3d=transform_points(T, self.points, engine=engine), points_col=self.colors, verbose=self._verbose)
+        if self.normals is not None:
+            out.normals = transform_points(T, np.ascontiguousarray(self.normals, np.float64), as_vectors=True, engine=engine)
+        return out
+
     def voxel_down_sample(self, voxel_size: float, engine=None) -> "PointCloud":
         """A new cloud with one point per filled voxel: the mean of the voxel's points, colours and normals (`utils/point_cloud_filters.py`,
         csrc/voxel.hip), in ascending voxel key."""

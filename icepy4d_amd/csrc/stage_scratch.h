@@ -91,5 +91,11 @@ struct MeshSampleScratch : Carve {
     explicit MeshSampleScratch(long long T) : area(take<double>(T)), cum(take<long long>(T)), sums(take<long long>(blocks_of(T, SCAN_THREADS))),
           amax(take<unsigned long long>(1)), total(take<long long>(1)) {}
 };
+// im_icp_accumulate and im_icp_finish, `chunks` >= 0 chunks of source points: parts [32 * max(chunks, 1)], one partial of 32 sums per chunk
+constexpr int ICP_PART = 32;
+struct IcpScratch : Carve {
+    Piece<double> parts;
+    explicit IcpScratch(long long chunks) : parts(take<double>(ICP_PART * (chunks > 0 ? chunks : 1))) {}
+};
 
 }  // namespace im

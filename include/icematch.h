@@ -498,6 +498,34 @@ int im_m3c2_finish(im_ctx* ctx, const int32_t* d_count1, const long long* d_sums
                    long long m, double half_length, double reg_error, int min_points, double* d_dist, double* d_lod, uint8_t* d_sig,
                    void* stream);
 
+/* ---- co-registration of two clouds (ICP) and rigid transforms (`src/icepy4d/utils/transformations.py`: `Rotrotranslation`;
+ * Open3D's `registration_icp`, CloudCompare's fine registration); csrc/icp.hip, csrc/icp_point.h. Definitions in DESIGN §4, restated in
+ * tests/icp_oracle.py: bit-identical; parity with an Open3D or CloudCompare binary is unpinned. float64, contraction off, only + - * / sqrt.
+ * im_icp_chunk: ICP_CHUNK (1024), the source points per partial; part of the definition of every sum.
+ * im_transform_points: d_out [n][3] = M applied to d_in [n][3] (d_out == d_in allowed), M = d_M [16] row-major 4x4 in DEVICE memory, last
+ * row taken as (0, 0, 0, 1): p_a = ((M_a0*x + M_a1*y) + M_a2*z) + M_a3; as_vectors != 0 leaves the + M_a3 out (normals).
+ * im_icp_accumulate: d_src [n][3] the transformed source, d_tgt [n_tgt][3], d_nrm [n_tgt][3] (NULL allowed for method 0), d_idx [n] int32
+ * and d_d2 [n] float64 as im_knn_cross(k = 1) returned them, h_centre [3] in HOST memory, method 0 = point to point, 1 = point to plane,
+ * n_chunks = ceil(n / ICP_CHUNK). Source point i is usable iff 0 <= d_idx[i] < n_tgt, its coordinates are finite and (method 1) the
+ * normal is finite; an unusable point adds +0.0. Writes one partial of 32 doubles per chunk (21 upper entries of J^T J, 6 of J^T r,
+ * sum r^2, sum d2, count, two zeros) into d_partials [n_chunks][32], or into the context's scratch when d_partials is NULL.
+ * im_icp_finish: sums the partials (d_partials, or the context's scratch when NULL), solves A x = -b by LDL^T without pivoting and writes
+ * d_record [64] float64: M_next [16], fitness = count / n, inlier_rmse = sqrt(sum d2 / count), count, status (0 OK, 1 EMPTY: count 0,
+ * 2 DEGENERATE: count < 6 or a pivot d_k <= 2^-40 A_kk or NaN), x [6] = (w, t), the six pivots, the 30 sums and two zeros.
+ * M_next = [R | fl(fl(t + c) - R c)] o M with R the Cayley map of w, M = d_M [16] in DEVICE memory (may be the M_next of another record);
+ * M_next = M with a status other than OK and with solve == 0 (the evaluation only: x and the pivots are 0, the status EMPTY or OK).
+ * All three return -81, without launching and with the outputs untouched, for a null required pointer, n or n_tgt outside 0..2^26, a
+ * non-finite centre, a method outside {0, 1}, method 1 without normals, solve outside {0, 1}, n_chunks != ceil(n / ICP_CHUNK), or a
+ * finish from the context's scratch before an accumulate of as many chunks. n == 0: transform and accumulate return 0 and launch nothing;
+ * the finish writes the EMPTY record. Enqueue only. */
+int im_icp_chunk(void);
+int im_transform_points(im_ctx* ctx, const double* d_M, const double* d_in, double* d_out, long long n, int as_vectors, void* stream);
+int im_icp_accumulate(im_ctx* ctx, const double* d_src, long long n, const double* d_tgt, const double* d_nrm, long long n_tgt,
+                      const int32_t* d_idx, const double* d_d2, const double* h_centre, int method, long long n_chunks, double* d_partials,
+                      void* stream);
+int im_icp_finish(im_ctx* ctx, const double* d_partials, long long n, long long n_chunks, const double* d_M, const double* h_centre, int solve,
+                  double* d_record, void* stream);
+
 /* ---- volume variations (`scripts/pcd_postprocessing/volume_variations.py`; `post_processing/cloudcompare_fun.py`:
  * `DemOfDifference.compute_volume` over CloudCompare's `ComputeVolume25D`; `post_processing/open3d_fun.py`: `filter_pcd_by_polyline`);
  * csrc/dod.hip, csrc/dod_cell.h. The DEM of difference of P pairs (ground, ceil) over E clouds that lie one behind the other in d_pts
