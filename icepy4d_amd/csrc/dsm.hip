@@ -15,34 +15,24 @@
 //   dsm_eval_kernel         one thread per cell: barycentric interpolation in scipy's operation order, float64
 //   proj_color_kernel       one thread per point / cell: cv2.projectPoints restated in float64, bilinear sampling of the image,
 //                           float32 projections, float64 colours and uint8 orthophoto cells
-// Every function that must reproduce the reference's rounding keeps contraction off: whether a * b + c becomes one fused operation
-// is otherwise the compiler's choice (`__fmul_rn` / `__fadd_rn` do not prevent it on this toolchain, lg_misc.hip).
+// The arithmetic of every item is dsm_cell.h's, which a host program compiles too (tests/dsm_host_harness.cpp); the kernels here are the
+// launch geometry, the scans, the search of a span's triangle and the atomicMin. Every function that must reproduce the reference's
+// rounding keeps contraction off: whether a * b + c becomes one fused operation is otherwise the compiler's choice (`__fmul_rn` /
+// `__fadd_rn` do not prevent it on this toolchain, lg_misc.hip).
+// What is pinned: the lowest simplex index that contains a cell, on every cell, and every output bit for bit against the brute-force
+// restatement (tests/dsm_oracle.py; tests/test_dsm_cpu.py on the host build, tests/test_gpu_dsm_edges.py on the device, on the cases
+// of tests/dsm_cases.py). The comparison with scipy's `find_simplex` (tests/test_gpu_dsm.py) remains the statement about the
+// reference: its walk may stop in a neighbour on a shared edge or vertex, so it is exact on cells with a unique triangle only.
 #include <climits>
 #include <cmath>
 
 #include "common.h"
 #include "ctx.h"
+#include "dsm_cell.h"
 #include "stage_scratch.h"
 
 namespace im {
 namespace {
-
-constexpr double DSM_EPS = 100.0 * 2.220446049250313e-16;   // scipy's inside tolerance, 100 * DBL_EPSILON
-constexpr int WIN_NONE = 0x7f7f7f7f;                           // hipMemset byte 0x7f: no triangle contains the cell
-
-// sortable keys: ascending unsigned order == ascending value; -0.0 folded into +0.0 (pandas groups by value)
-__device__ __forceinline__ uint32_t f32_key(float f) {
-    uint32_t u = __float_as_uint(f);
-    if (u == 0x80000000u) u = 0;
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ long long f64_key(double d) {   // NaN after everything, all NaN equal (numpy's sort order)
-    if (d != d) return LLONG_MAX;
-    unsigned long long u = (unsigned long long)__double_as_longlong(d);
-    if (u == 0x8000000000000000ull) u = 0;
-    u = (u & 0x8000000000000000ull) ? ~u : (u | 0x8000000000000000ull);
-    return (long long)(u ^ 0x8000000000000000ull);
-}
 
 __global__ __launch_bounds__(256) void dsm_round_kernel(const double* __restrict__ pts, long long n, float step, float* __restrict__ xr,
                                                         float* __restrict__ yr, long long* __restrict__ xykey, long long* __restrict__ ykey,
@@ -50,15 +40,7 @@ __global__ __launch_bounds__(256) void dsm_round_kernel(const double* __restrict
 #pragma clang fp contract(off)
     const long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const float x = (float)pts[3 * i], y = (float)pts[3 * i + 1];
-    const float qx = rintf(__fdiv_rn(x, step)) * step;   // np.round: half to even
-    const float qy = rintf(__fdiv_rn(y, step)) * step;
-    xr[i] = qx;
-    yr[i] = qy;
-    const uint32_t kx = f32_key(qx), ky = f32_key(qy);
-    xykey[i] = (long long)((((unsigned long long)kx << 32) | ky) ^ 0x8000000000000000ull);
-    ykey[i] = (long long)ky;
-    zkey[i] = f64_key(pts[3 * i + 2]);
+    dsm_round_point(pts, i, step, xr, yr, xykey, ykey, zkey);
 }
 
 __global__ __launch_bounds__(256) void dsm_zero_first_kernel(const float* __restrict__ xr, const float* __restrict__ yr,
@@ -66,8 +48,8 @@ __global__ __launch_bounds__(256) void dsm_zero_first_kernel(const float* __rest
     const int j = blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= n) return;
     const long long i = perm_b[j];
-    if (xr[i] == 0.f) atomicMin(&first[0], j);
-    if (yr[i] == 0.f) atomicMin(&first[1], j);
+    if (dsm_zero_key(xr[i])) atomicMin(&first[0], j);
+    if (dsm_zero_key(yr[i])) atomicMin(&first[1], j);
 }
 
 // ---- exclusive scans over per-item counts (group starts: 0 / 1 per sorted row; triangles: grid rows per triangle): scan.h -----------
@@ -78,38 +60,14 @@ struct GroupScan {            // 1 where a sorted row starts a new (x, y) group
     const long long* perm;    // [n] rows in group order
     long long n;
     long long* starts;        // [G] first sorted position of each group
-    __device__ long long count(long long j) const { return j < n && (j == 0 || key[perm[j]] != key[perm[j - 1]]) ? 1 : 0; }
+    __device__ long long count(long long j) const { return dsm_group_count(key, perm, n, j); }
     __device__ void write(long long j, long long pos) const { if (j < n && count(j)) starts[pos] = j; }
 };
-
-struct TriGrid {
-    const float* bx; const float* by;   // binned points (float32; float64 of them is what qhull saw)
-    const int* simp;                    // [T][3]
-    const double* tr;                   // [T][3][2] scipy's barycentric transforms
-    long long T;
-    const double* xq; const double* yq; int nx, ny;
-    double x0, dx, y0, dy;              // xq[c] == x0 + c * dx (np.arange's own delta), likewise yq
-};
-
-__device__ __forceinline__ void tri_rows(const TriGrid& g, long long t, int& r0, int& r1) {
-    r0 = 0; r1 = -1;
-    if (!(g.tr[6 * t] == g.tr[6 * t])) return;   // NaN transform: a degenerate simplex never contains a cell
-    const double ya = g.by[g.simp[3 * t]], yb = g.by[g.simp[3 * t + 1]], yc = g.by[g.simp[3 * t + 2]];
-    const double lo = fmin(ya, fmin(yb, yc)), hi = fmax(ya, fmax(yb, yc));
-    const double a = fmax(floor((lo - g.y0) / g.dy) - 1.0, 0.0), b = fmin(ceil((hi - g.y0) / g.dy) + 1.0, (double)(g.ny - 1));
-    if (!(a <= b)) return;
-    r0 = (int)a; r1 = (int)b;
-}
 
 struct RowScan {              // grid rows (spans) per triangle
     TriGrid g;
     long long* offs;          // [T] first span of each triangle
-    __device__ long long count(long long t) const {
-        if (t >= g.T) return 0;
-        int r0, r1;
-        tri_rows(g, t, r0, r1);
-        return r1 - r0 + 1;
-    }
+    __device__ long long count(long long t) const { return tri_span_count(g, t); }
     __device__ void write(long long t, long long pos) const { if (t < g.T) offs[t] = pos; }
 };
 
@@ -122,37 +80,7 @@ __global__ __launch_bounds__(256) void dsm_group_mean_kernel(const double* __res
     const long long g = blockIdx.x * (long long)blockDim.x + threadIdx.x;
     const long long G = *n_groups;
     if (g >= G) return;
-    const long long j0 = starts[g], j1 = g + 1 < G ? starts[g + 1] : n;
-    const long long i0 = perm_c[j0];
-    float x = xr[i0], y = yr[i0];
-    // a zero key keeps the sign of its first occurrence in the reference's sorted table (pandas factorises each key column)
-    if (x == 0.f) x = xr[perm_b[zero_first[0]]];
-    if (y == 0.f) y = yr[perm_b[zero_first[1]]];
-    double s = 0.0, c = 0.0;
-    long long cnt = 0;
-    for (long long j = j0; j < j1; ++j) {
-        const double v = pts[3 * perm_c[j] + 2];
-        if (v != v) continue;
-        ++cnt;
-        const double yv = v - c;
-        const double t = s + yv;
-        c = (t - s) - yv;
-        if (c != c) c = 0.0;    // pandas: an infinite value makes the compensation NaN; it is reset
-        s = t;
-    }
-    bx[g] = x;
-    by[g] = y;
-    bz[g] = cnt ? (float)(s / (double)cnt) : __int_as_float(0x7fc00000);
-}
-
-// scipy's `_barycentric_inside` (2-D): c_i = 0 + T[i][0] dx + T[i][1] dy, c_2 = (1 - c_0) - c_1, all within [-eps, 1 + eps]
-__device__ __forceinline__ bool bary(const double* __restrict__ T, double qx, double qy, double& c0, double& c1, double& c2) {
-#pragma clang fp contract(off)
-    const double dx = qx - T[4], dy = qy - T[5];
-    c0 = (0.0 + T[0] * dx) + T[1] * dy;
-    c1 = (0.0 + T[2] * dx) + T[3] * dy;
-    c2 = (1.0 - c0) - c1;
-    return c0 >= -DSM_EPS && c0 <= 1.0 + DSM_EPS && c1 >= -DSM_EPS && c1 <= 1.0 + DSM_EPS && c2 >= -DSM_EPS && c2 <= 1.0 + DSM_EPS;
+    dsm_group_mean(pts, xr, yr, perm_b, perm_c, zero_first, starts, G, n, g, bx, by, bz);
 }
 
 __global__ __launch_bounds__(256) void dsm_raster_kernel(TriGrid g, const long long* __restrict__ offs, const long long* __restrict__ n_spans,
@@ -169,30 +97,9 @@ __global__ __launch_bounds__(256) void dsm_raster_kernel(TriGrid g, const long l
         int r0, r1;
         tri_rows(g, t, r0, r1);
         const int r = r0 + (int)(q - offs[t]);
-        const double y = g.yq[r];
-        const double* T = g.tr + 6 * t;
-        double vx[3], vy[3];
-        for (int k = 0; k < 3; ++k) { vx[k] = g.bx[g.simp[3 * t + k]]; vy[k] = g.by[g.simp[3 * t + k]]; }
-        const double ylo = fmin(vy[0], fmin(vy[1], vy[2])), yhi = fmax(vy[0], fmax(vy[1], vy[2]));
-        const double yc = fmin(fmax(y, ylo), yhi);   // rows of the margin use the nearest row of the triangle
-        double xlo = INFINITY, xhi = -INFINITY;
-        for (int k = 0; k < 3; ++k) {
-            const int m = k == 2 ? 0 : k + 1;
-            const double ya = vy[k], yb = vy[m];
-            if (yc < fmin(ya, yb) || yc > fmax(ya, yb)) continue;
-            if (ya == yb) { xlo = fmin(xlo, fmin(vx[k], vx[m])); xhi = fmax(xhi, fmax(vx[k], vx[m])); continue; }
-            const double x = vx[k] + (yc - ya) * ((vx[m] - vx[k]) / (yb - ya));
-            xlo = fmin(xlo, x); xhi = fmax(xhi, x);
-        }
-        if (!(xlo <= xhi)) continue;
-        // one column of margin on each side: the exact test below decides
-        const double a = fmax(floor((xlo - g.x0) / g.dx) - 1.0, 0.0), b = fmin(ceil((xhi - g.x0) / g.dx) + 1.0, (double)(g.nx - 1));
-        if (!(a <= b)) continue;
-        int* row = win + (long long)r * g.nx;
-        for (int c = (int)a; c <= (int)b; ++c) {
-            double c0, c1, c2;
-            if (bary(T, g.xq[c], y, c0, c1, c2) && (int)t < row[c]) atomicMin(&row[c], (int)t);
-        }
+        tri_span_cells(g, t, r, [&](long long cell) {
+            if ((int)t < win[cell]) atomicMin(&win[cell], (int)t);
+        });
     }
 }
 
@@ -201,89 +108,14 @@ __global__ __launch_bounds__(256) void dsm_eval_kernel(TriGrid g, const float* _
 #pragma clang fp contract(off)
     const long long cell = blockIdx.x * (long long)blockDim.x + threadIdx.x;
     if (cell >= (long long)g.nx * g.ny) return;
-    const int r = (int)(cell / g.nx), c = (int)(cell - (long long)r * g.nx);
-    const double qx = g.xq[c], qy = g.yq[r];
-    const int s = win[cell];
-    // scipy's `_is_point_fully_outside`: outside the points' bounding box (+- eps) is outside
-    if (s == WIN_NONE || qx < bounds.x - DSM_EPS || qx > bounds.z + DSM_EPS || qy < bounds.y - DSM_EPS || qy > bounds.w + DSM_EPS) {
-        z[cell] = fill;
-        return;
-    }
-    double c0, c1, c2;
-    bary(g.tr + 6 * (long long)s, qx, qy, c0, c1, c2);
-    const double v0 = bz[g.simp[3 * s]], v1 = bz[g.simp[3 * s + 1]], v2 = bz[g.simp[3 * s + 2]];
-    z[cell] = ((0.0 + c0 * v0) + c1 * v1) + c2 * v2;
-}
-
-// ---- projection + bilinear colours -------------------------------------------------------------------------------------------
-struct CamParams { double fx, fy, cx, cy, R[9], t[3], k[12]; };
-
-struct ColorArgs {
-    const double* x; long long xr, xc;     // element (r, c) of each coordinate plane at r * xr + c * xc
-    const double* y; long long yr, yc;
-    const double* z; long long zr, zc;
-    int rows, cols, cells;                 // cells: a NaN z is an invalid cell (black, nothing sampled)
-    const unsigned char* img; int h, w, cin, cout;
-    int chmap[4];                          // output channel -> image channel (BGR -> RGB reverses)
-    float* proj; double* col; unsigned char* ortho;   // [n][2], [n][cout], [n][3]; each may be null
-};
-
-__device__ __forceinline__ long long floor_index(float u) {   // np.floor(u).astype(int) on x86: out of range / NaN -> INT64_MIN
-    const float f = floorf(u);
-    return (f == f && fabsf(f) < 9.2e18f) ? (long long)f : LLONG_MIN;
-}
-__device__ __forceinline__ long long clip(long long v, long long hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
-__device__ __forceinline__ unsigned char to_u8(double v) {    // np.uint8(float64) on x86: truncation to int32, low byte
-    return (v == v && v > -2147483649.0 && v < 2147483648.0) ? (unsigned char)((int)v & 0xff) : 0;
+    z[cell] = dsm_eval_cell(g, bz, win, bounds.x, bounds.y, bounds.z, bounds.w, fill, cell);
 }
 
 __global__ __launch_bounds__(256) void proj_color_kernel(ColorArgs a, CamParams p) {
 #pragma clang fp contract(off)
     const long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x;
     if (i >= (long long)a.rows * a.cols) return;
-    const long long r = i / a.cols, c = i - r * a.cols;
-    const double X = a.x[r * a.xr + c * a.xc], Y = a.y[r * a.yr + c * a.yc], Z = a.z[r * a.zr + c * a.zc];
-    if (a.cells && Z != Z) {
-        if (a.ortho) a.ortho[3 * i] = a.ortho[3 * i + 1] = a.ortho[3 * i + 2] = 0;
-        return;
-    }
-    // cv2.projectPoints (cvProjectPoints2Internal), float64
-    double x = ((p.R[0] * X + p.R[1] * Y) + p.R[2] * Z) + p.t[0];
-    double y = ((p.R[3] * X + p.R[4] * Y) + p.R[5] * Z) + p.t[1];
-    double zz = ((p.R[6] * X + p.R[7] * Y) + p.R[8] * Z) + p.t[2];
-    zz = zz != 0.0 ? 1.0 / zz : 1.0;
-    x *= zz;
-    y *= zz;
-    const double* k = p.k;
-    const double r2 = x * x + y * y, r4 = r2 * r2, r6 = r4 * r2;
-    const double a1 = 2 * x * y, a2 = r2 + 2 * x * x, a3 = r2 + 2 * y * y;
-    const double cdist = ((1 + k[0] * r2) + k[1] * r4) + k[4] * r6;
-    const double icdist2 = 1.0 / (((1 + k[5] * r2) + k[6] * r4) + k[7] * r6);
-    const double xd = ((((x * cdist) * icdist2 + k[2] * a1) + k[3] * a2) + k[8] * r2) + k[9] * r4;
-    const double yd = ((((y * cdist) * icdist2 + k[2] * a3) + k[3] * a1) + k[10] * r2) + k[11] * r4;
-    const float u = (float)(xd * p.fx + p.cx), v = (float)(yd * p.fy + p.cy);
-    if (a.proj) { a.proj[2 * i] = u; a.proj[2 * i + 1] = v; }
-    if (!a.col && !a.ortho) return;
-    // bilinear_interpolate: clipped corners, weights from the unclipped position, float64
-    const long long fu = floor_index(u), fv = floor_index(v);
-    const long long x0 = clip(fu, a.w - 1), x1 = clip(fu + 1, a.w - 1), y0 = clip(fv, a.h - 1), y1 = clip(fv + 1, a.h - 1);
-    const double du = (double)u, dv = (double)v;
-    const double wa = ((double)x1 - du) * ((double)y1 - dv);
-    const double wb = ((double)x1 - du) * (dv - (double)y0);
-    const double wc = (du - (double)x0) * ((double)y1 - dv);
-    const double wd = (du - (double)x0) * (dv - (double)y0);
-    const unsigned char* pa = a.img + (y0 * a.w + x0) * a.cin;
-    const unsigned char* pb = a.img + (y1 * a.w + x0) * a.cin;
-    const unsigned char* pc = a.img + (y0 * a.w + x1) * a.cin;
-    const unsigned char* pd = a.img + (y1 * a.w + x1) * a.cin;
-    for (int ch = 0; ch < a.cout; ++ch) {
-        const int m = a.chmap[ch];
-        const double Ia = __fdiv_rn((float)pa[m], 255.0f), Ib = __fdiv_rn((float)pb[m], 255.0f);
-        const double Ic = __fdiv_rn((float)pc[m], 255.0f), Id = __fdiv_rn((float)pd[m], 255.0f);
-        const double sum = ((wa * Ia + wb * Ib) + wc * Ic) + wd * Id;
-        if (a.col) a.col[i * a.cout + ch] = sum;
-        if (a.ortho) a.ortho[3 * i + ch] = to_u8((double)(float)sum * 255.0);
-    }
+    proj_color_item(a, p, i);
 }
 
 }  // namespace
@@ -335,7 +167,7 @@ extern "C" int im_dsm_rasterize(im_ctx* ctx, const float* d_bx, const float* d_b
                                 const double* d_yq, int ny, double x0, double dx, double y0, double dy, double fill, double* d_z, void* stream) {
     IM_CHECK_CTX(ctx);
     if (!d_bx || !d_by || !d_bz || !d_simplices || !d_transform || !h_bounds || !d_xq || !d_yq || !d_z || n_simplices < 0 ||
-        n_simplices >= INT_MAX || nx < 0 || ny < 0)
+        n_simplices >= WIN_NONE || nx < 0 || ny < 0)
         return ctx->fail(-72, "im_dsm_rasterize: bad arguments");
     if (!(dx > 0.0) || !(dy > 0.0) || !std::isfinite(x0) || !std::isfinite(y0)) return ctx->fail(-72, "im_dsm_rasterize: the grid spacing must be positive");
     const long long cells = (long long)nx * ny;
@@ -368,7 +200,8 @@ extern "C" int im_project_colors(im_ctx* ctx, const double* d_x, long long sxr, 
                                  const unsigned char* d_img, int h, int w, int cin, const int32_t* h_chmap, int cout, float* d_proj,
                                  double* d_col, unsigned char* d_ortho, void* stream) {
     IM_CHECK_CTX(ctx);
-    if (!d_x || !d_y || !d_zc || !h_cam || rows < 0 || cols < 0) return ctx->fail(-72, "im_project_colors: bad arguments");
+    // cout bounds the channel map below whether or not colours are asked for
+    if (!d_x || !d_y || !d_zc || !h_cam || rows < 0 || cols < 0 || cout < 0 || cout > 4) return ctx->fail(-72, "im_project_colors: bad arguments");
     if ((d_col || d_ortho) && (!d_img || !h_chmap || h < 1 || w < 1 || cin < 1 || cout < 1 || cout > 4))
         return ctx->fail(-72, "im_project_colors: bad image arguments");
     if (d_ortho && cout != 3) return ctx->fail(-72, "im_project_colors: an orthophoto has 3 channels (got %d)", cout);

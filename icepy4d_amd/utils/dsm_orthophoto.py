@@ -5,10 +5,12 @@ are torch's and the Delaunay triangulation is scipy's qhull on the host, on exac
 set is the reference's. Every entry point takes an optional `engine=` (default: the shared engine of device 0); there is no CPU
 fallback: without a HIP device the calls raise.
 
-Numerics (tests/test_gpu_dsm.py, g12): the binned points are bit-identical to pandas' group means, the NaN mask of the grid is the
-reference's, and z is bit-identical wherever a cell lies inside a unique triangle. A cell on a shared edge or vertex takes the lowest
-simplex index that contains it, where scipy's directed walk may stop in a neighbour: the value then differs in the last bits.
-Orthophotos from the same DSM are bit-identical."""
+Numerics. The binned points are bit-identical to pandas' group means. Every grid cell takes the lowest simplex index that contains it
+(scipy's own inside test and tolerance) and the interpolation in scipy's operation order: z is bit-identical, on every cell, to the
+brute-force restatement of that rule (tests/dsm_oracle.py `rasterize`; tests/test_gpu_dsm_edges.py, tests/test_dsm_cpu.py). Against the
+reference itself (tests/test_gpu_dsm.py, g12) the NaN mask of the grid is the reference's and z is bit-identical wherever a cell lies
+inside a unique triangle; on a shared edge or vertex scipy's directed walk may stop in a neighbouring triangle that contains the cell
+as well, and the value then differs in the last bits. Projections, colours and orthophotos from the same DSM are bit-identical."""
 from pathlib import Path
 
 import numpy as np

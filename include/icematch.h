@@ -284,7 +284,8 @@ int im_dsm_group_mean(im_ctx* ctx, const double* d_pts, const float* d_xr, const
  * host: d_simplices [T][3] int32 and d_transform [T][3][2] float64 are scipy's `Delaunay.simplices` / `.transform`, h_bounds its
  * min_bound (x, y) and max_bound (x, y); d_xq [nx] / d_yq [ny] the grid axes (np.arange), xq[c] == x0 + c * dx. Every cell takes the
  * lowest-index simplex that contains it (scipy's inside test, eps = 100 DBL_EPSILON) and z = ((0 + c0 v0) + c1 v1) + c2 v2 with
- * v = float64 of d_bz; cells in none get `fill`. d_z [ny][nx] float64. Scratch from the context. Enqueue only. */
+ * v = float64 of d_bz; cells in none get `fill`. d_z [ny][nx] float64. T below 0x7f7f7f7f, the mark of a cell without a triangle
+ * (-72 from there upward). Scratch from the context. Enqueue only. */
 int im_dsm_rasterize(im_ctx* ctx, const float* d_bx, const float* d_by, const float* d_bz, const int32_t* d_simplices,
                      const double* d_transform, long long n_simplices, const double* h_bounds, const double* d_xq, int nx,
                      const double* d_yq, int ny, double x0, double dx, double y0, double dy, double fill, double* d_z, void* stream);
@@ -292,7 +293,7 @@ int im_dsm_rasterize(im_ctx* ctx, const float* d_bx, const float* d_by, const fl
  * `bilinear_interpolate` (`sfm/interpolate_colors.py:13-92`), and the colouring of `generate_ortophoto` (`dsm_orthophoto.py:176-211`).
  * Items (r, c) of a rows x cols table; coordinate plane P has element (r, c) at d_P[r * sPr + c * sPc]. cells = 1: a NaN z is an
  * invalid cell (black in d_ortho). h_cam [28] float64: fx, fy, cx, cy, R (9, row-major), t (3), k1 k2 p1 p2 k3 k4 k5 k6 s1..s4 (zeros
- * where absent). d_img [h][w][cin] uint8; output channel ch samples image channel h_chmap[ch] (cout <= 4) as float32(v) / 255.
+ * where absent). d_img [h][w][cin] uint8; output channel ch samples image channel h_chmap[ch] (0 <= cout <= 4, whatever is asked for) as float32(v) / 255.
  * Outputs, each optional: d_proj [n][2] float32 projections, d_col [n][cout] float64 colours (the float64 sum of the reference),
  * d_ortho [n][3] uint8 = np.uint8(float32(colour) * 255). Enqueue only. */
 int im_project_colors(im_ctx* ctx, const double* d_x, long long sxr, long long sxc, const double* d_y, long long syr, long long syc,

@@ -6,7 +6,9 @@ tests/golden/g12_dsm_orthophoto.npz (tests/test_dsm_cpu.py) and used for random 
 
 `interpolate` finds each cell's triangle with scipy's own `find_simplex`, so it reproduces `LinearNDInterpolator` exactly. The
 device takes the lowest simplex index that contains a cell instead; the two agree except on cells that lie on a shared edge or
-vertex, where both are valid and the values differ in the last bits."""
+vertex, where both are valid and the values differ in the last bits. `lowest_simplex` / `rasterize` restate the device's rule by
+brute force over all triangles, `project_colors` / `ortho_bytes` the colouring from the 28-vector of the C entry point: what the
+host build of csrc/dsm_cell.h (tests/test_dsm_cpu.py) and the kernels (tests/test_gpu_dsm_edges.py) are compared with bit for bit."""
 import numpy as np
 from scipy.spatial import Delaunay
 
@@ -83,23 +85,90 @@ def triangulate(bx, by):
     return Delaunay(np.ascontiguousarray(np.stack([bx, by], 1), dtype=np.float64))
 
 
-def barycentric(tri, simplex, qx, qy):
-    """(c0, c1, c2) of cells (qx, qy) in `simplex`, in scipy's operation order (no fused multiply-add in numpy)."""
-    T = tri.transform[simplex]
-    dx, dy = qx - T[:, 2, 0], qy - T[:, 2, 1]
-    c0 = (0.0 + T[:, 0, 0] * dx) + T[:, 0, 1] * dy
-    c1 = (0.0 + T[:, 1, 0] * dx) + T[:, 1, 1] * dy
+def barycentric_of(T, qx, qy):
+    """(c0, c1, c2) of cells (qx, qy) under the transforms T [..., 3, 2], in scipy's operation order (no fused multiply-add in numpy)."""
+    dx, dy = qx - T[..., 2, 0], qy - T[..., 2, 1]
+    c0 = (0.0 + T[..., 0, 0] * dx) + T[..., 0, 1] * dy
+    c1 = (0.0 + T[..., 1, 0] * dx) + T[..., 1, 1] * dy
     return c0, c1, (1.0 - c0) - c1
 
 
-def eval_cells(tri, values, simplex, qx, qy, fill):
+def barycentric(tri, simplex, qx, qy):
+    """(c0, c1, c2) of cells (qx, qy) in `simplex` of a `Delaunay` object."""
+    return barycentric_of(tri.transform[simplex], qx, qy)
+
+
+def eval_cells_of(simplices, transform, values, simplex, qx, qy, fill):
     """z of cells whose simplex is known (-1: outside): ((0 + c0 v0) + c1 v1) + c2 v2 in float64."""
     out = np.full(len(qx), float(fill))
     ok = simplex >= 0
     s = simplex[ok]
-    c0, c1, c2 = barycentric(tri, s, qx[ok], qy[ok])
-    v = np.asarray(values, np.float64)[tri.simplices[s]]
-    out[ok] = ((0.0 + c0 * v[:, 0]) + c1 * v[:, 1]) + c2 * v[:, 2]
+    with np.errstate(invalid="ignore", over="ignore"):
+        c0, c1, c2 = barycentric_of(np.asarray(transform)[s], qx[ok], qy[ok])
+        v = np.asarray(values, np.float64)[np.asarray(simplices)[s]]
+        out[ok] = ((0.0 + c0 * v[:, 0]) + c1 * v[:, 1]) + c2 * v[:, 2]
+    return out
+
+
+def eval_cells(tri, values, simplex, qx, qy, fill):
+    return eval_cells_of(tri.simplices, tri.transform, values, simplex, qx, qy, fill)
+
+
+def lowest_simplex(transform, qx, qy, block=1 << 21):
+    """The lowest index t whose three barycentric coordinates of the cell lie in [-EPS, 1 + EPS]; -1 if none. Brute force over all
+    triangles; a NaN transform never contains a cell (every comparison with it is false)."""
+    T = np.asarray(transform, np.float64).reshape(-1, 3, 2)
+    qx, qy = np.asarray(qx, np.float64), np.asarray(qy, np.float64)
+    out = np.full(len(qx), -1, np.int64)
+    if not len(qx):
+        return out
+    per = max(1, block // len(qx))
+    with np.errstate(invalid="ignore", over="ignore"):
+        for t0 in range(0, len(T), per):
+            c0, c1, c2 = barycentric_of(T[t0:t0 + per, None], qx[None, :], qy[None, :])
+            inside = (c0 >= -EPS) & (c0 <= 1.0 + EPS) & (c1 >= -EPS) & (c1 <= 1.0 + EPS) & (c2 >= -EPS) & (c2 <= 1.0 + EPS)
+            hit = inside.any(axis=0) & (out < 0)
+            out[hit] = t0 + inside[:, hit].argmax(axis=0)
+    return out
+
+
+def rasterize(bx, by, bz, simplices, transform, bounds, xq, yq, fill):
+    """What `im_dsm_rasterize` computes: the lowest containing simplex of every cell, `fill` where there is none or the cell lies outside
+    `bounds` (min x, min y, max x, max y) by more than EPS, else the interpolation of `eval_cells`. [len(yq), len(xq)] float64."""
+    gx, gy = np.meshgrid(np.asarray(xq, np.float64), np.asarray(yq, np.float64))
+    qx, qy = gx.ravel(), gy.ravel()
+    s = lowest_simplex(transform, qx, qy)
+    b = np.asarray(bounds, np.float64)
+    s[(qx < b[0] - EPS) | (qx > b[2] + EPS) | (qy < b[1] - EPS) | (qy > b[3] + EPS)] = -1
+    return eval_cells_of(simplices, transform, bz, s, qx, qy, fill).reshape(gx.shape)
+
+
+def span_rows(by, simplices, transform, y0, dy, ny):
+    """(r0, r1) per triangle: the grid rows its spans cover (its rows and one row of margin on each side), r1 < r0 where it has none."""
+    T = np.asarray(transform, np.float64).reshape(-1, 6)
+    y = np.asarray(by, np.float64)[np.asarray(simplices).reshape(-1, 3)]
+    with np.errstate(invalid="ignore"):
+        a = np.maximum(np.floor((y.min(axis=1) - y0) / dy) - 1.0, 0.0)
+        b = np.minimum(np.ceil((y.max(axis=1) - y0) / dy) + 1.0, float(ny - 1))
+        none = np.isnan(T[:, 0]) | ~(a <= b)
+    return np.where(none, 0, a).astype(np.int64), np.where(none, -1, b).astype(np.int64)
+
+
+def span_count(by, simplices, transform, y0, dy, ny):
+    """The number of (triangle, grid row) spans `im_dsm_rasterize` walks: only to assert what the scan and stride cases claim."""
+    r0, r1 = span_rows(by, simplices, transform, y0, dy, ny)
+    return int((r1 - r0 + 1).sum())
+
+
+def transforms_of(bx, by, simplices):
+    """Barycentric transforms of hand-made triangles as scipy lays them out, [T, 3, 2]: the inverse of [[x0 - x2, x1 - x2],
+    [y0 - y2, y1 - y2]], then the third vertex; NaN throughout for a singular triangle, as scipy leaves a degenerate simplex."""
+    p = np.stack([np.asarray(bx, np.float64), np.asarray(by, np.float64)], 1)[np.asarray(simplices).reshape(-1, 3)]
+    out = np.full((len(p), 3, 2), np.nan)
+    A = np.swapaxes(p[:, :2] - p[:, 2:3], 1, 2)
+    ok = A[:, 0, 0] * A[:, 1, 1] - A[:, 0, 1] * A[:, 1, 0] != 0
+    out[ok, :2] = np.linalg.inv(A[ok])
+    out[ok, 2] = p[ok, 2]
     return out
 
 
@@ -210,6 +279,26 @@ def to_uint8(a):
     return np.where(ok, i & 0xFF, 0).astype(np.uint8)
 
 
+def project_colors(points3d, cam, image, chmap):
+    """`im_project_colors` on points: cam [28] = fx fy cx cy, R row-major, t, k[12] (thin-prism terms included); (proj [n, 2] float32,
+    col [n, len(chmap)] float64), output channel ch sampled from image channel chmap[ch]."""
+    cam = np.asarray(cam, np.float64)
+    K = np.array([[cam[0], 0.0, cam[2]], [0.0, cam[1], cam[3]], [0.0, 0.0, 1.0]])
+    with np.errstate(invalid="ignore", over="ignore"):
+        uv = project_points(points3d, K, cam[16:28], cam[4:13], cam[13:16])
+        f = np.asarray(image).astype(np.float32) / np.float32(255.0)
+        col = np.stack([bilinear(f[:, :, int(m)], uv[:, 0], uv[:, 1]) for m in chmap], 1).reshape(len(uv), len(chmap))
+    return uv, col
+
+
+def ortho_bytes(col, z):
+    """The orthophoto bytes of cells with the float64 colours `col` [n, 3]: float32, times 255, the uint8 cast; black where z is NaN."""
+    with np.errstate(invalid="ignore", over="ignore"):
+        out = to_uint8(np.asarray(col).astype(np.float32).astype(np.float64) * 255)
+    out[np.isnan(np.asarray(z))] = 0
+    return out
+
+
 def orthophoto(xx, yy, zz, image, K, dist, R, t):
     """`generate_ortophoto`: [rows, cols, 3] uint8; cells with NaN z are black."""
     zz = np.asarray(zz, np.float64)
@@ -236,6 +325,20 @@ def g12_case(g, name):
     fill = {0: np.nan, 1: "mean", 2: float(num)}[int(kind)]
     xq, yq = grid_axes(lim[:2], lim[2:], step)
     return pts, step, xlim, ylim, fill, xq, yq
+
+
+def same_bits(a, b):
+    """Same shape, dtype and bit pattern on every element (signed zeros included), a NaN equal to a NaN: IEEE 754 leaves the sign and
+    payload of a NaN result open, whether an invalid operation makes it (inf - inf, 0 * inf) or a NaN operand passes through an
+    addition or a product (a subtraction done as an addition of the negated operand flips its sign), and processors differ."""
+    a, b = np.asarray(a), np.asarray(b)
+    if a.shape != b.shape or a.dtype != b.dtype:
+        return False
+    if a.dtype.kind != "f":
+        return bool(np.array_equal(a, b))
+    u = {4: np.uint32, 8: np.uint64}[a.dtype.itemsize]
+    both_nan = np.isnan(a) & np.isnan(b)
+    return bool(((np.ascontiguousarray(a).view(u) == np.ascontiguousarray(b).view(u)) | both_nan).all())
 
 
 def bits_equal(a, b):

@@ -7,7 +7,11 @@ shared edge or vertex takes the lowest simplex index that contains it where scip
 cell to within scipy's own tolerance (eps = 100 DBL_EPSILON in barycentric units), so there z may differ by 4 ulp plus
 eps * max |z of the vertices| * 4 (on at most 1 % of the cells by more than 4 ulp), and a NaN vertex value of the one triangle
 reaches the cell through a zero weight (0 * NaN) only there. Orthophotos from the same DSM and projections bit-identical; colours
-within 1e-12."""
+within 1e-12.
+
+This file is the statement about the reference (scipy's `find_simplex`, g12). What the device itself computes, the lowest simplex index
+that contains a cell, is pinned exactly and on every cell, shared edges and vertices included, against the brute-force restatement in
+tests/test_gpu_dsm_edges.py, with the colours, the refusals and the code's own boundaries."""
 import os
 import sys
 import types
