@@ -111,6 +111,12 @@ SIGNATURES = {
     "im_transform_points": [_P, _P, _P, _P, _L, _I, _P],
     "im_icp_accumulate": [_P, _P, _L, _P, _P, _L, _P, _P, _P, _I, _L, _P, _P],
     "im_icp_finish": [_P, _P, _L, _L, _P, _P, _I, _P, _P],
+    "im_ba_chunk": [],
+    "im_ba_accumulate": [_P, _P, _I, _L, _L, _P, _P, _P, _P, _P, _P, _P, _P],
+    "im_ba_solve": [_P, _P, _I, _L, _P, _P, _P, _P, C.c_uint, _P, _P],
+    "im_ba_step_points": [_P, _P, _I, _L, _L, _P, _P, _P, _P, _P, _P, _P, _P, _P],
+    "im_ba_decide": [_P, _P, _I, _L, _P, _P, _P, _P, _P, _P, _P, _L, _P],
+    "im_ba_residuals": [_P, _P, _I, _L, _L, _P, _P, _P, _P, _P, _P],
     "im_dod_chunk": [],
     "im_dod_max_cells": [],
     "im_dod_max_batch_cells": [],

@@ -129,6 +129,7 @@ struct im_ctx {
         im::Scratch mesh;        // triangle and vertex flags, segment heads, hull facets, areas and their cumulative counts (mesh.hip)
         im::Scratch poisson;     // block sums of the crossing census and the extraction of the Poisson reconstruction (poisson.hip)
         im::Scratch icp;         // one partial of 32 sums per chunk of source points of an ICP iteration (icp.hip)
+        im::Scratch ba;          // chunk partials of 448 sums, chunk cost partials and 95 doubles per point of a bundle-adjustment iteration (ba.hip)
         im::Scratch clock[2];    // im_debug_clock_probe: per-block (cycles, 100 MHz ticks) of the attention / Winograd BX main loops
     } scratch;
     // hipSuccess: s holds at least `bytes`. A larger buffer is allocated (through dalloc: guards and `allocs` ownership as for every buffer; `name`

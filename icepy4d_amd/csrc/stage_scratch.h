@@ -97,5 +97,14 @@ struct IcpScratch : Carve {
     Piece<double> parts;
     explicit IcpScratch(long long chunks) : parts(take<double>(ICP_PART * (chunks > 0 ? chunks : 1))) {}
 };
+// im_ba_accumulate .. im_ba_decide, E >= 1 epochs of M >= 0 points in all: an epoch's chunks start at slot off[e] / BA_CHUNK + e, so
+// slots = M / 256 + E + 1 hold every epoch's. parts [448 * slots], cparts [slots], keep [95 * max(M, 1)]
+constexpr int BA_PART = 448, BA_KEPT = 95, BA_SLOT_POINTS = 256;
+struct BaScratch : Carve {
+    Piece<double> parts, cparts, keep;
+    long long slots;
+    BaScratch(long long E, long long M) : parts(take<double>(BA_PART * (M / BA_SLOT_POINTS + E + 1))), cparts(take<double>(M / BA_SLOT_POINTS + E + 1)),
+          keep(take<double>(BA_KEPT * (M > 0 ? M : 1))), slots(M / BA_SLOT_POINTS + E + 1) {}
+};
 
 }  // namespace im

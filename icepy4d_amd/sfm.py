@@ -610,3 +610,397 @@ class RelativeOrientation:
         self.features[0] = self.features[0][self.inlMask]
         self.features[1] = self.features[1][self.inlMask]
         return self.F, self.inlMask
+
+
+# ---- two-view bundle adjustment with control points (csrc/ba.hip, csrc/ba_point.h) -------------------------------------------------
+BA_DIM, BA_CAM, BA_CAMSTATE, BA_STATE, BA_RECORD, BA_SOL = 28, 14, 24, 8, 64, 512
+BA_REC_COST0, BA_REC_COST1, BA_REC_LAMBDA, BA_REC_ACCEPTED, BA_REC_COUNT, BA_REC_STATUS, BA_REC_X, BA_REC_PIVOT, BA_REC_ITER = 0, 1, 2, 3, 4, 5, 6, 34, 62
+BA_STATUS = {-1: "RUNNING", 0: "OK", 1: "MAX_ITER", 2: "STALLED", 3: "EMPTY", 4: "DEGENERATE"}
+BA_PARAMETERS = ("w0", "w1", "w2", "dC0", "dC1", "dC2", "f", "cx", "cy", "k1", "k2", "p1", "p2", "k3")
+BA_MASK_DEFAULT = 0x7F | (0x7F << 14)
+
+
+class BundleResult(NamedTuple):
+    """What `bundle_adjust` returns: new `Camera` objects (the originals untouched), the adjusted points [n, 3], the status name, the final
+    cost 0.5 sum (residual / sigma)^2, sigma0 = sqrt(2 cost / max(rows - unknowns, 1)), the number of iterations, `history`
+    [iterations, 64] (cost before, cost after, lambda, accepted, usable count, status after, the 28 steps, the 28 pivots, the iteration),
+    `residuals` [n, 2, 3] (x, y, norm in pixels per camera, NaN where not seen) and the `state` [8] that a further call may resume from."""
+    cameras: list
+    points3d: np.ndarray
+    status: str
+    cost: float
+    sigma0: float
+    iterations: int
+    history: np.ndarray
+    residuals: np.ndarray
+    state: np.ndarray
+
+
+def ba_mask(free=("pose", "f"), cameras=(0, 1)) -> int:
+    """The 28-bit mask that frees the named parameters of the named cameras: "pose" (w and dC), "rotation", "centre", "f", "cx", "cy",
+    "k1", "k2", "p1", "p2", "k3", or "all". The default is what the driver's `optimizeCameras(fit_f=True)` names."""
+    groups = {"pose": range(0, 6), "rotation": range(0, 3), "centre": range(3, 6), "all": range(0, BA_CAM)}
+    mask = 0
+    for name in free:
+        if name in groups:
+            bits = groups[name]
+        elif name in BA_PARAMETERS[6:]:
+            bits = [BA_PARAMETERS.index(name)]
+        else:
+            raise ValueError(f"ba_mask: unknown parameter {name!r}")
+        for c in cameras:
+            if c not in (0, 1):
+                raise ValueError("ba_mask: cameras are 0 and 1")
+            for b in bits:
+                mask |= 1 << (BA_CAM * c + b)
+    return mask
+
+
+def _ba_camera_state(camera) -> np.ndarray:
+    """[24] float64 of a camera object: R row-major, C, fx fy cx cy, k1 k2 p1 p2 k3 k4 k5 k6 (a shorter distortion vector is zero-filled)."""
+    out = np.zeros(BA_CAMSTATE)
+    R = np.asarray(camera.R, np.float64).reshape(3, 3)
+    out[:9] = R.reshape(9)
+    out[9:12] = -(R.T @ np.asarray(camera.t, np.float64).reshape(3))
+    out[12:] = _intrinsics(camera)
+    return out
+
+
+def _ba_camera_from_state(camera, state: np.ndarray):
+    """A copy of `camera` with K, extrinsics and distortion of the state [24]; the distortion vector keeps its length."""
+    import copy
+    new = copy.deepcopy(camera)
+    K = np.array(camera.K, np.float64)
+    K[0, 0], K[1, 1], K[0, 2], K[1, 2] = state[12:16]
+    new.update_K(K)
+    R, C = state[:9].reshape(3, 3), state[9:12].reshape(3, 1)
+    ext = np.eye(4)
+    ext[:3, :3], ext[:3, 3:4] = R, -(R @ C)
+    new.update_extrinsics(ext)
+    if camera.dist is not None:
+        d = np.array(camera.dist, np.float64)
+        flat = d.reshape(-1)
+        flat[:min(flat.size, 8)] = state[16:16 + min(flat.size, 8)]
+        new.update_dist(d)
+    return new
+
+
+def _ba_options(lambda0, lambda_min, lambda_max, ftol, max_iter, ctol):
+    if not (np.isfinite(lambda0) and lambda0 >= 0.0):
+        raise ValueError(f"bundle_adjust: lambda0 must be finite and >= 0 (got {lambda0})")
+    if not (0.0 < lambda_min <= lambda_max and np.isfinite(lambda_max)):
+        raise ValueError(f"bundle_adjust: 0 < lambda_min <= lambda_max is expected (got {lambda_min}, {lambda_max})")
+    if not (ftol >= 0.0 and ctol >= 0.0):
+        raise ValueError(f"bundle_adjust: ftol and ctol must be >= 0 (got {ftol}, {ctol})")
+    if int(max_iter) != max_iter or not 1 <= max_iter <= 10000:
+        raise ValueError(f"bundle_adjust: max_iter must be an integer in 1..10000 (got {max_iter})")
+    return np.array([lambda_min, lambda_max, ftol, float(max_iter), ctol])
+
+
+def ba_problem(cameras, image_points, points3d, targets=None, camera_centers_world=None, image_sigma=1.0, target_image_sigma=None,
+               target_accuracy=0.01, cam_accuracy=0.1) -> dict:
+    """The arrays of one epoch in the layout of `im_ba_*` (host, float64): cams [48], X [n, 3], obs [n, 4], sig [n], prior [n, 6],
+    cprior [12]; the tie points first, then the targets. `targets` = (image coordinates per camera: two [m, 2] arrays with NaN rows where a
+    camera does not see the target, object coordinates [m, 3]); their start is the object coordinate and their prior sigma is
+    `target_accuracy` (a scalar, [3] or [m, 3]; 0 leaves a component free). `camera_centers_world` = two [3] centres (or None per camera)
+    with `cam_accuracy` (a scalar or [3])."""
+    if len(cameras) != 2 or len(image_points) != 2:
+        raise ValueError("bundle_adjust: two cameras and two arrays of image points are expected")
+    X = np.ascontiguousarray(_points(points3d), np.float64)
+    uv = [_image_points(p, np.float64) for p in image_points]
+    if not (len(uv[0]) == len(uv[1]) == len(X)):
+        raise ValueError(f"bundle_adjust: image_points and points3d must have one row per tie point (got {len(uv[0])}, {len(uv[1])}, {len(X)})")
+    if not (np.isfinite(image_sigma) and image_sigma > 0.0):
+        raise ValueError(f"bundle_adjust: image_sigma must be > 0 (got {image_sigma})")
+    n = len(X)
+    obs, sig, prior = np.concatenate(uv, 1).reshape(n, 4), np.full(n, float(image_sigma)), np.zeros((n, 6))
+    if targets is not None:
+        t_img, t_obj = targets
+        t_obj = np.ascontiguousarray(t_obj, np.float64).reshape(-1, 3)
+        t_uv = [np.asarray(p, np.float64).reshape(-1, 2) for p in t_img]
+        if len(t_uv) != 2 or not (len(t_uv[0]) == len(t_uv[1]) == len(t_obj)):
+            raise ValueError("bundle_adjust: targets = ([uv in camera 0 [m, 2], uv in camera 1 [m, 2]], object coordinates [m, 3])")
+        acc = np.broadcast_to(np.asarray(target_accuracy, np.float64), t_obj.shape)
+        if not (np.isfinite(acc).all() and (acc >= 0.0).all()):
+            raise ValueError("bundle_adjust: target_accuracy must be finite and >= 0")
+        ts = float(image_sigma if target_image_sigma is None else target_image_sigma)
+        if not (np.isfinite(ts) and ts > 0.0):
+            raise ValueError(f"bundle_adjust: target_image_sigma must be > 0 (got {ts})")
+        X = np.concatenate([X, t_obj])
+        obs = np.concatenate([obs, np.concatenate(t_uv, 1)])
+        sig = np.concatenate([sig, np.full(len(t_obj), ts)])
+        prior = np.concatenate([prior, np.concatenate([t_obj, acc], 1)])
+    cprior = np.zeros(12)
+    if camera_centers_world is not None:
+        if len(camera_centers_world) != 2:
+            raise ValueError("bundle_adjust: camera_centers_world holds one centre (or None) per camera")
+        acc = np.broadcast_to(np.asarray(cam_accuracy, np.float64), (3,))
+        if not (np.isfinite(acc).all() and (acc >= 0.0).all()):
+            raise ValueError("bundle_adjust: cam_accuracy must be finite and >= 0")
+        for c, centre in enumerate(camera_centers_world):
+            if centre is not None:
+                centre = np.asarray(centre, np.float64).reshape(-1)
+                if centre.shape != (3,) or not np.isfinite(centre).all():
+                    raise ValueError("bundle_adjust: a camera centre is three finite numbers")
+                cprior[6 * c:6 * c + 3], cprior[6 * c + 3:6 * c + 6] = centre, acc
+    cams = np.concatenate([_ba_camera_state(c) for c in cameras])
+    return dict(cams=cams, X=X, obs=np.ascontiguousarray(obs), sig=sig, prior=np.ascontiguousarray(prior), cprior=cprior)
+
+
+def ba_run_device(problems, mask, lambda0, opts, states=None, engine=None):
+    """The whole loop of E epochs on the device: 4 launches per iteration for all epochs at once and ONE read-back at the end. `problems`:
+    dicts as `ba_problem` returns them (host arrays or device tensors). Returns per epoch (cams [48], X [n, 3], state [8], history
+    [iterations, 64], residuals [n, 2, 3])."""
+    eng = default_engine(engine)
+    dev, E = eng.device, len(problems)
+    if E < 1:
+        raise ValueError("bundle_adjust: at least one epoch is expected")
+    f64 = lambda v, w: (v if torch.is_tensor(v) else torch.from_numpy(np.ascontiguousarray(v, np.float64))).to(dev, torch.float64).reshape(-1, w)
+    X = [f64(p["X"], 3) for p in problems]
+    off = np.concatenate([[0], np.cumsum([len(x) for x in X])]).astype(np.int64)
+    M, max_points = int(off[-1]), int(np.diff(off).max())
+    cat = lambda k, w: torch.cat([f64(p[k], w) for p in problems] + [torch.zeros((0 if M else 1, w), dtype=torch.float64, device=dev)]).contiguous()
+    dX = torch.cat(X + [torch.zeros((0 if M else 1, 3), dtype=torch.float64, device=dev)])
+    cams = torch.cat([f64(p["cams"], 2 * BA_CAMSTATE) for p in problems])
+    cprior = torch.cat([f64(p["cprior"], 12) for p in problems]).contiguous()
+    return _ba_split(off, *_ba_run_batched(eng, E, M, max_points, to_device(off, dev), dX, cat("obs", 4), cat("sig", 1), cat("prior", 6), cams, cprior,
+                                           mask, lambda0, opts, states))
+
+
+def _ba_run_batched(eng, E, M, max_points, doff, dX, obs, sig, prior, cams, cprior, mask, lambda0, opts, states=None):
+    """The loop on arrays that are on the device already (doff [E + 1] int64, dX [max(M, 1), 3], obs, sig, prior, cams [E, 48], cprior
+    [E, 12]): enqueues everything and returns device tensors (state, history, cams2, pts2, residuals) and the first history row of every
+    epoch. Nothing is read back here; `max_points` bounds the points of an epoch."""
+    dev, max_iter = eng.device, int(opts[3])
+    pts2 = torch.zeros((2, max(M, 1), 3), dtype=torch.float64, device=dev)
+    pts2[0] = dX
+    cams2 = torch.zeros((2, E, 2 * BA_CAMSTATE), dtype=torch.float64, device=dev)
+    cams2[0] = cams
+    st = np.zeros((E, BA_STATE))
+    st[:, 0], st[:, 3] = lambda0, -1.0
+    if states is not None:
+        st = np.ascontiguousarray(states, np.float64).reshape(E, BA_STATE).copy()
+        st[:, 1], st[:, 2] = 0.0, 0.0                              # the current buffers are the ones handed in; the run goes on
+        st[:, 3] = -1.0
+    first = st[:, 4].astype(np.int64)
+    if (first >= max_iter).any():
+        raise ValueError("bundle_adjust: a resumed state has used its max_iter iterations already")
+    state = to_device(st, dev)
+    sol = torch.zeros((E, BA_SOL), dtype=torch.float64, device=dev)
+    history = torch.zeros((max_iter, E, BA_RECORD), dtype=torch.float64, device=dev)
+    res = torch.full((max(M, 1), 2, 3), float("nan"), dtype=torch.float64, device=dev)
+    h_opts = np.ascontiguousarray(opts, np.float64)
+    s, call = eng.stream_ptr(), eng.ctx.call
+    for _ in range(max_iter - int(first.min())):
+        call("im_ba_accumulate", ptr(doff), E, M, max_points, ptr(pts2), ptr(obs), ptr(sig), ptr(prior), ptr(cams2), ptr(state), None, s)
+        call("im_ba_solve", ptr(doff), E, M, None, ptr(cams2), ptr(cprior), ptr(state), int(mask), ptr(sol), s)
+        call("im_ba_step_points", ptr(doff), E, M, max_points, ptr(pts2), ptr(obs), ptr(sig), ptr(prior), ptr(cams2), ptr(state), ptr(sol), None, s)
+        call("im_ba_decide", ptr(doff), E, M, None, ptr(cams2), ptr(cprior), ptr(state), ptr(sol), h_opts.ctypes.data, ptr(history), max_iter, s)
+    call("im_ba_residuals", ptr(doff), E, M, max_points, ptr(pts2), ptr(obs), ptr(cams2), ptr(state), ptr(res), s)
+    return state, history, cams2, pts2, res, first
+
+
+def _ba_split(off, state, history, cams2, pts2, res, first) -> list:
+    """The one read-back, and per epoch (cams [48], X [n, 3], state [8], history [iterations, 64], residuals [n, 2, 3])."""
+    st, hist, cams_h, pts_h, res_h = state.cpu().numpy(), history.cpu().numpy(), cams2.cpu().numpy(), pts2.cpu().numpy(), res.cpu().numpy()
+    out = []
+    for e in range(len(st)):
+        par, a, b = int(st[e, 1] != 0.0), int(off[e]), int(off[e + 1])
+        out.append((cams_h[par, e].copy(), pts_h[par, a:b].copy(), st[e].copy(), hist[first[e]:int(st[e, 4]), e].copy(), res_h[a:b].copy()))
+    return out
+
+
+def _ba_result(cameras, problem, mask, out) -> BundleResult:
+    cams, X, st, hist, res = out
+    if len(hist):
+        last = hist[-1]
+        cost = float(last[BA_REC_COST1] if last[BA_REC_ACCEPTED] else last[BA_REC_COST0])
+    else:
+        cost = float("nan")
+    rows = 2 * int(np.isfinite(res[:, :, 2]).sum()) + int((problem["prior"][:, 3:] > 0).sum()) + int((problem["cprior"].reshape(2, 6)[:, 3:] > 0).sum())
+    unknowns = bin(int(mask)).count("1") + 3 * int(np.isfinite(res[:, :, 2]).any(1).sum())
+    sigma0 = float(np.sqrt(2.0 * cost / max(rows - unknowns, 1)))
+    new = [_ba_camera_from_state(c, cams[BA_CAMSTATE * i:BA_CAMSTATE * (i + 1)]) for i, c in enumerate(cameras)]
+    return BundleResult(new, X, BA_STATUS[int(st[3])], cost, sigma0, len(hist), hist, res, st)
+
+
+def bundle_adjust(cameras, image_points, points3d, targets=None, camera_centers_world=None, image_sigma=1.0, target_image_sigma=None,
+                  target_accuracy=0.01, cam_accuracy=0.1, mask=BA_MASK_DEFAULT, lambda0=1e-3, lambda_min=1e-12, lambda_max=1e8, ftol=1e-9,
+                  ctol=0.0, max_iter=30, state=None, engine=None, _run=None) -> BundleResult:
+    """Bundle adjustment of ONE epoch (two cameras) on the device, where the driver calls `chunk.optimizeCameras(fit_f=True)`: the two
+    `Camera`s, their matched image points [n, 2] each (distorted pixels, as the matcher gives them), the triangulated points [n, 3], and
+    optionally the targets (image and object coordinates with `target_accuracy`) and the surveyed camera centres with `cam_accuracy`.
+    Levenberg-Marquardt with the points eliminated over 14 parameters per camera (`BA_PARAMETERS`; `mask`, see `ba_mask`, frees poses and
+    f by default), cost 0.5 sum (residual / sigma)^2, every sum in an order fixed by the point index: bit-identical to the restatement
+    `tests/ba_oracle.py`. A definition of its own: parity with Metashape is unpinned; there is no b1 / b2, no robust loss and
+    no covariance. `state` = the `state` of an earlier result resumes that run (with its lambda and iteration count) from the cameras and
+    points that are handed in; since a target always starts at its object coordinates, a run with `targets` resumes bit for bit only
+    through `ba_run_device` on the returned arrays, or with the adjusted targets passed as tie points. The originals are untouched."""
+    if int(mask) != mask or not 0 <= int(mask) < (1 << BA_DIM):
+        raise ValueError(f"bundle_adjust: the mask has {BA_DIM} bits (got {mask})")
+    opts = _ba_options(lambda0, lambda_min, lambda_max, ftol, max_iter, ctol)
+    problem = ba_problem(cameras, image_points, points3d, targets, camera_centers_world, image_sigma, target_image_sigma, target_accuracy,
+                         cam_accuracy)
+    run = _run if _run is not None else (lambda ps, m, l0, o, sts: ba_run_device(ps, m, l0, o, sts, engine=engine))
+    out = run([problem], int(mask), float(lambda0), opts, None if state is None else [state])[0]
+    return _ba_result(cameras, problem, mask, out)
+
+
+def bundle_adjust_epochs(cameras, image_points, points3d, targets=None, camera_centers_world=None, engine=None, _run=None, mask=BA_MASK_DEFAULT,
+                         lambda0=1e-3, lambda_min=1e-12, lambda_max=1e8, ftol=1e-9, ctol=0.0, max_iter=30, **problem_options) -> list:
+    """`bundle_adjust` for EVERY epoch of a sequence at once: `cameras` one pair or a list of E pairs, `image_points` a list of E
+    [uv0, uv1], `points3d` a list of E arrays (e.g. `triangulate_table(...).points3d`), `targets` None, one (image, object) TUPLE for all
+    epochs or a LIST of E of them, `camera_centers_world` likewise (a tuple of two centres for all epochs, or a list of E). All epochs share the launches: 4 per iteration, one read-back at the end; each
+    epoch stops on its own. Returns a list of E `BundleResult`, each bit-identical to the epoch run alone."""
+    E = len(points3d)
+    if len(image_points) != E:
+        raise ValueError(f"bundle_adjust_epochs: image_points and points3d hold one entry per epoch (got {len(image_points)}, {E})")
+    if int(mask) != mask or not 0 <= int(mask) < (1 << BA_DIM):
+        raise ValueError(f"bundle_adjust_epochs: the mask has {BA_DIM} bits (got {mask})")
+    pairs = _camera_pairs(cameras)
+    if len(pairs) not in (1, E):
+        raise ValueError(f"bundle_adjust_epochs: one camera pair or one per epoch ({E}) is expected (got {len(pairs)})")
+    for name, v in (("targets", targets), ("camera_centers_world", camera_centers_world)):
+        if isinstance(v, list) and len(v) != E:
+            raise ValueError(f"bundle_adjust_epochs: a list of {name} holds one entry per epoch ({E}); a tuple is shared by all epochs")
+    per = lambda v, e: v[e] if isinstance(v, list) else v
+    opts = _ba_options(lambda0, lambda_min, lambda_max, ftol, max_iter, ctol)
+    problems = [ba_problem(pairs[e if len(pairs) > 1 else 0], image_points[e], points3d[e], None if targets is None else per(targets, e),
+                           None if camera_centers_world is None else per(camera_centers_world, e), **problem_options) for e in range(E)]
+    run = _run if _run is not None else (lambda ps, m, l0, o, sts: ba_run_device(ps, m, l0, o, sts, engine=engine))
+    outs = run(problems, int(mask), float(lambda0), opts, None)
+    return [_ba_result(pairs[e if len(pairs) > 1 else 0], problems[e], mask, outs[e]) for e in range(E)]
+
+
+def table_image_points(table, max_kpts: int) -> list:
+    """Per record of a gathered match table with the keypoint payload: [uv0, uv1], the matched keypoints [n_e, 2] float64 in ascending
+    keypoint-0 index, the order in which `triangulate_table` triangulates them; a failed or empty record gives zero rows."""
+    from .sequence import decode_record, record_words
+    t = table.cpu().numpy() if torch.is_tensor(table) else np.ascontiguousarray(table, dtype=np.int32)
+    if t.dtype != np.int32 or t.ndim != 2 or t.shape[1] != record_words(int(max_kpts), True):
+        raise ValueError(f"an int32 table with rows of {record_words(int(max_kpts), True)} words (max_kpts = {max_kpts}, with_keypoints=True) is "
+                         f"expected (got {t.dtype}, shape {t.shape})")
+    out = []
+    for rec in t:
+        d = decode_record(rec, int(max_kpts))
+        m = d["matches0"] if d["n_matches"] > 0 else np.zeros(0, np.int64)
+        hit = m > -1
+        out.append([d["keypoints0"][:len(m)][hit].astype(np.float64), d["keypoints1"][m[hit]].astype(np.float64)])
+    return out
+
+
+def _table_observations(t, K: int, doff, M: int):
+    """The matched keypoints of a gathered match table ON THE DEVICE, in the rows `im_triangulate_table` gives their points: obs
+    [max(M, 1), 4] float64 = (u0, v0, u1, v1). As the kernel takes them: the entries 0 <= matches0[i] < K of a record in ascending i, the
+    first n_matches of them, at rows doff[e] + rank; a row the record does not fill stays NaN (its point is NaN too). torch index
+    arithmetic only, no read-back: surplus entries go to a spare last row that is cut off."""
+    E, dev = int(t.shape[0]), t.device
+    obs = torch.full((M + 1, 4), float("nan"), dtype=torch.float64, device=dev)
+    if E and M:
+        m = t[:, 8:8 + K].to(torch.int64)
+        valid = (m >= 0) & (m < K)
+        rank = torch.cumsum(valid.to(torch.int64), 1) - 1
+        keep = valid & (rank < t[:, 3].clamp(min=0).to(torch.int64)[:, None])
+        dest = torch.where(keep, doff[:E, None] + rank, torch.full_like(rank, M)).clamp(max=M)
+        kp = t[:, 8 + 2 * K:].contiguous().view(torch.float32).reshape(E, 2, K, 2).to(torch.float64)
+        uv1 = torch.gather(kp[:, 1], 1, m.clamp(0, K - 1)[:, :, None].expand(-1, -1, 2))
+        obs[dest.reshape(-1)] = torch.cat([kp[:, 0], uv1], 2).reshape(E * K, 4)
+    return obs[:max(M, 1)].contiguous() if M else torch.full((1, 4), float("nan"), dtype=torch.float64, device=dev)
+
+
+def _triangulate_table_device(eng, table, K: int, cameras, undistort=True, tolerance=DEFAULT_TOLERANCE, launch=True):
+    """`triangulate_table`'s launch with everything left on the device: (table, E, M, offsets [E + 1] int64, points [M, 3], status [M]);
+    launch=False only uploads the table and sizes the arrays."""
+    from .sequence import record_words
+    t = table if torch.is_tensor(table) else torch.from_numpy(np.ascontiguousarray(table, dtype=np.int32))
+    if t.dtype != torch.int32 or t.ndim != 2 or t.shape[1] != record_words(K, True):
+        raise ValueError(f"an int32 table with rows of {record_words(K, True)} words (max_kpts = {K}, with_keypoints=True) is expected "
+                         f"(got {t.dtype}, shape {tuple(t.shape)})")
+    dev = eng.device
+    t = t.to(dev).contiguous()
+    E = int(t.shape[0])
+    cams = _camera_table(cameras, E) if E else np.zeros((1, 2, 24))
+    dcams = to_device(cams, dev)
+    M = int(t[:, 3].clamp(min=0).sum().item()) if E else 0            # before the launch: the outputs are sized by it
+    doff = torch.zeros(E + 1, dtype=torch.int64, device=dev)
+    dX = torch.empty((M, 3), dtype=torch.float64, device=dev)
+    dst = torch.empty(M, dtype=torch.int32, device=dev)
+    if launch:
+        eng.ctx.call("im_triangulate_table", ptr(t), E, K, ptr(dcams), len(cams), int(bool(undistort)), float(tolerance), MAX_SOLVES, M,
+                     ptr(doff), ptr(dX) if M else None, ptr(dst) if M else None, None, None, eng.stream_ptr())
+    return t, E, M, doff, dX, dst
+
+
+def bundle_adjust_table(table, max_kpts: int, cameras, reconstruction=None, targets=None, camera_centers_world=None, image_sigma=1.0,
+                        target_image_sigma=None, target_accuracy=0.01, cam_accuracy=0.1, mask=BA_MASK_DEFAULT, lambda0=1e-3, lambda_min=1e-12,
+                        lambda_max=1e8, ftol=1e-9, ctol=0.0, max_iter=30, undistort=True, engine=None, _run=None) -> list:
+    """`bundle_adjust` for EVERY record of a gathered match table (`sequence.py`: int32 [E, 8 + 6 max_kpts] with the keypoint payload, a
+    device tensor or a host array) without leaving the device between triangulation and the final read-back: `im_triangulate_table`
+    leaves its points and offsets on the device, the matched keypoints are gathered there into the same rows, the targets (one (image,
+    object) tuple for all epochs) are laid behind every epoch's tie points there, the four kernels run `max_iter` rounds for all epochs,
+    and states, histories, cameras, points, residuals and offsets come back in ONE read-back. The only earlier read is the table's total
+    match count, before the triangulation, which sizes the arrays. `cameras` is one pair or a list of E pairs. A point whose
+    triangulation failed (NaN) is unusable and stays. `reconstruction` (a `TableReconstruction` of this table) replaces the
+    triangulation by its points, uploaded. One `BundleResult` per record, each bit-identical to `bundle_adjust` on the record's own
+    keypoints and points. (`_run`: the restatement in the device's place, for tests without one; then everything is host work.)"""
+    K = int(max_kpts)
+    if int(mask) != mask or not 0 <= int(mask) < (1 << BA_DIM):
+        raise ValueError(f"bundle_adjust_table: the mask has {BA_DIM} bits (got {mask})")
+    opts = _ba_options(lambda0, lambda_min, lambda_max, ftol, max_iter, ctol)
+    if isinstance(targets, list) or isinstance(camera_centers_world, list):
+        raise ValueError("bundle_adjust_table: targets and camera_centers_world are shared by all epochs (a tuple each); use bundle_adjust_epochs for one per epoch")
+    pkw = dict(image_sigma=image_sigma, target_image_sigma=target_image_sigma, target_accuracy=target_accuracy, cam_accuracy=cam_accuracy)
+    if _run is not None:
+        uv = table_image_points(table, K)
+        if reconstruction is None or len(reconstruction.points3d) != len(uv) or any(len(x) != len(p[0]) for x, p in zip(reconstruction.points3d, uv)):
+            raise ValueError("bundle_adjust_table: the reconstruction does not belong to this table (points per record differ)")
+        if not uv:
+            return []
+        return bundle_adjust_epochs(cameras, uv, list(reconstruction.points3d), targets=targets, camera_centers_world=camera_centers_world,
+                                    _run=_run, mask=mask, lambda0=lambda0, lambda_min=lambda_min, lambda_max=lambda_max, ftol=ftol, ctol=ctol,
+                                    max_iter=max_iter, **pkw)
+    eng = default_engine(engine)
+    dev = eng.device
+    t, E, M, doff, dX, _ = _triangulate_table_device(eng, table, K, cameras, undistort=undistort, launch=reconstruction is None)
+    if E == 0:
+        return []
+    if reconstruction is not None:
+        if len(reconstruction.points3d) != E or int(np.asarray(reconstruction.offsets)[-1]) != M:
+            raise ValueError("bundle_adjust_table: the reconstruction does not belong to this table (points per record differ)")
+        dX = to_device(np.concatenate([np.asarray(x, np.float64).reshape(-1, 3) for x in reconstruction.points3d] + [np.zeros((0, 3))]), dev)
+        doff = to_device(np.asarray(reconstruction.offsets, np.int64), dev)
+    pairs = _camera_pairs(cameras)
+    # what one epoch adds behind its tie points (targets) and its cameras and centre priors: ba_problem's own host logic on an empty epoch
+    tail = [ba_problem(pairs[e if len(pairs) > 1 else 0], [np.zeros((0, 2)), np.zeros((0, 2))], np.zeros((0, 3)), targets, camera_centers_world, **pkw)
+            for e in range(len(pairs))]
+    m = len(tail[0]["X"])
+    Mt = M + E * m
+    obs_tie = _table_observations(t, K, doff, M)
+    doff2 = doff + m * torch.arange(E + 1, dtype=torch.int64, device=dev)
+    X = torch.zeros((max(Mt, 1), 3), dtype=torch.float64, device=dev)
+    obs = torch.full((max(Mt, 1), 4), float("nan"), dtype=torch.float64, device=dev)
+    sig = torch.full((max(Mt, 1),), float(image_sigma), dtype=torch.float64, device=dev)
+    prior = torch.zeros((max(Mt, 1), 6), dtype=torch.float64, device=dev)
+    if M:
+        epoch = torch.searchsorted(doff[1:].contiguous(), torch.arange(M, dtype=torch.int64, device=dev), right=True)
+        row = torch.arange(M, dtype=torch.int64, device=dev) + m * epoch
+        X[row], obs[row] = dX, obs_tie[:M]
+    if m:
+        row = (doff2[1:, None] - m + torch.arange(m, dtype=torch.int64, device=dev)[None, :]).reshape(-1)
+        X[row] = to_device(tail[0]["X"], dev).repeat(E, 1)
+        obs[row] = to_device(tail[0]["obs"], dev).repeat(E, 1)
+        sig[row] = to_device(tail[0]["sig"], dev).repeat(E)
+        prior[row] = to_device(tail[0]["prior"], dev).repeat(E, 1)
+    cams = to_device(np.stack([tail[e if len(tail) > 1 else 0]["cams"] for e in range(E)]), dev)
+    cprior = to_device(np.stack([tail[e if len(tail) > 1 else 0]["cprior"] for e in range(E)]), dev)
+    max_points = min(K + m, Mt)
+    ran = _ba_run_batched(eng, E, Mt, max_points, doff2.contiguous(), X, obs, sig, prior, cams, cprior, mask, lambda0, opts)
+    off2 = doff2.cpu().numpy()                                            # with the results: the one read-back
+    outs = _ba_split(off2, *ran)
+    obs_h, prior_h = obs.cpu().numpy(), prior.cpu().numpy()
+    results = []
+    for e in range(E):
+        a, b = int(off2[e]), int(off2[e + 1])
+        problem = dict(prior=prior_h[a:b], cprior=tail[e if len(tail) > 1 else 0]["cprior"])
+        results.append(_ba_result(pairs[e if len(pairs) > 1 else 0], problem, mask, outs[e]))
+    return results

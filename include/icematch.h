@@ -527,6 +527,49 @@ int im_icp_accumulate(im_ctx* ctx, const double* d_src, long long n, const doubl
 int im_icp_finish(im_ctx* ctx, const double* d_partials, long long n, long long n_chunks, const double* d_M, const double* h_centre, int solve,
                   double* d_record, void* stream);
 
+/* ---- two-view bundle adjustment with control points (the driver's last step, `chunk.optimizeCameras(fit_f=True)` in
+ * `MetashapeProject.run_full_workflow`, with a definition of its own); csrc/ba.hip, csrc/ba_point.h. Definitions in DESIGN §4, restated in
+ * tests/ba_oracle.py: bit-identical; parity with a Metashape binary is unpinned. float64, contraction off, only + - * / sqrt.
+ * Levenberg-Marquardt with the points eliminated, batched over E epochs. All arrays in DEVICE memory unless named h_:
+ * d_off [E + 1] int64, the first point of every epoch and the end; M points in all; max_points bounds the points of an epoch (the grid).
+ * PRECONDITION: max_points >= d_off[e + 1] - d_off[e] for every epoch. The offsets are in device memory, so the entry points cannot check
+ * it: with a smaller value the chunks beyond max_points of a longer epoch are not computed, and im_ba_solve / im_ba_decide, which sum
+ * ceil(n_e / 256) partials per epoch, would add whatever those slots held.
+ * d_pts2 [2][M][3] and d_cams2 [2][E][2][24] are double-buffered: an epoch's current ones are those of its parity. A camera is R [9]
+ * row-major, C [3], fx fy cx cy, k1 k2 p1 p2 k3 k4 k5 k6 with Xc = R (X - C). d_obs [M][4] = (u0, v0, u1, v1) pixels, a NaN = not seen;
+ * d_sig [M] pixels; d_prior [M][6] = (X0 [3], sX [3]), sX_k > 0 puts a prior on component k; d_cprior [E][2][6] likewise for the centres.
+ * d_state [E][8] = lambda, parity, done, status (-1 running, 0 OK, 1 MAX_ITER, 2 STALLED, 3 EMPTY, 4 DEGENERATE), iterations recorded, 3 spare:
+ * the caller writes (lambda_0, 0, 0, -1, 0) before the first iteration, and may hand a returned state back to go on.
+ * im_ba_chunk: BA_CHUNK (256), the points per partial; part of the definition of every sum.
+ * One iteration is the four calls in this order, none of which reads back; the blocks of a finished epoch return at once.
+ * im_ba_accumulate: one partial of 448 doubles per chunk (406 upper entries of the reduced 28 x 28 system, 28 right-hand sides, cost, usable
+ * count, 12 zeros) into d_parts [M / 256 + E + 1][448] (the context's scratch when NULL) at slot off[e] / 256 + e + chunk, and 95 doubles
+ * per point for the back-substitution into the context's scratch.
+ * im_ba_solve: the partials in ascending order, centre priors, damping, the mask (bit p frees parameter p of 28: per camera w [3], dC [3],
+ * df, dcx, dcy, dk1, dk2, dp1, dp2, dk3), LDL^T without pivoting with im_icp_finish's pivot rule; d_sol [E][512] = the 448 sums and the
+ * draft of the record; the candidate cameras go into the other half of d_cams2.
+ * im_ba_step_points: the back-substitution, candidate points into the other half of d_pts2, one cost partial per chunk into d_cparts
+ * [M / 256 + E + 1] (the context's scratch when NULL).
+ * im_ba_decide: accept iff the candidate's cost is strictly lower; h_opts [5] in HOST memory = lambda floor, lambda ceiling, ftol, max_iter, ctol;
+ * writes the record [64] = cost before, cost after, lambda, accepted, count, status after, x [28], pivots [28], iteration, 0 to d_history
+ * [hist_rows][E][64] at the row of the epoch's iteration count, and updates d_state.
+ * im_ba_residuals: d_res [M][2][3] = (u - u_obs, v - v_obs, norm) in pixels per camera of the current state, NaN where not seen.
+ * All five return -82, without launching, for a null required pointer, E outside 1..65535, M outside 0..2^26, max_points outside 0..M, a
+ * mask outside 28 bits, options outside 0 < floor <= ceiling, ftol >= 0, 1 <= max_iter <= hist_rows, ctol >= 0, or a call that finds the context's
+ * scratch smaller than an im_ba_accumulate of the same E and M left it. Enqueue only. */
+int im_ba_chunk(void);
+int im_ba_accumulate(im_ctx* ctx, const long long* d_off, int E, long long M, long long max_points, const double* d_pts2, const double* d_obs,
+                     const double* d_sig, const double* d_prior, const double* d_cams2, const double* d_state, double* d_parts, void* stream);
+int im_ba_solve(im_ctx* ctx, const long long* d_off, int E, long long M, const double* d_parts, double* d_cams2, const double* d_cprior,
+                const double* d_state, unsigned mask, double* d_sol, void* stream);
+int im_ba_step_points(im_ctx* ctx, const long long* d_off, int E, long long M, long long max_points, double* d_pts2, const double* d_obs,
+                      const double* d_sig, const double* d_prior, const double* d_cams2, const double* d_state, const double* d_sol,
+                      double* d_cparts, void* stream);
+int im_ba_decide(im_ctx* ctx, const long long* d_off, int E, long long M, const double* d_cparts, const double* d_cams2, const double* d_cprior,
+                 double* d_state, const double* d_sol, const double* h_opts, double* d_history, long long hist_rows, void* stream);
+int im_ba_residuals(im_ctx* ctx, const long long* d_off, int E, long long M, long long max_points, const double* d_pts2, const double* d_obs,
+                    const double* d_cams2, const double* d_state, double* d_res, void* stream);
+
 /* ---- volume variations (`scripts/pcd_postprocessing/volume_variations.py`; `post_processing/cloudcompare_fun.py`:
  * `DemOfDifference.compute_volume` over CloudCompare's `ComputeVolume25D`; `post_processing/open3d_fun.py`: `filter_pcd_by_polyline`);
  * csrc/dod.hip, csrc/dod_cell.h. The DEM of difference of P pairs (ground, ceil) over E clouds that lie one behind the other in d_pts
