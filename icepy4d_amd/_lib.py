@@ -117,6 +117,11 @@ SIGNATURES = {
     "im_ba_step_points": [_P, _P, _I, _L, _L, _P, _P, _P, _P, _P, _P, _P, _P, _P],
     "im_ba_decide": [_P, _P, _I, _L, _P, _P, _P, _P, _P, _P, _P, _L, _P],
     "im_ba_residuals": [_P, _P, _I, _L, _L, _P, _P, _P, _P, _P, _P],
+    "im_dense_tile_w": [],
+    "im_dense_tile_h": [],
+    "im_dense_sweep": [_P, _P, _I, _I, _P, _I, _I, _P, _P, _D, _D, _I, _I, _L, _D, _P, _P, _P, _P],
+    "im_dense_consistency": [_P, _P, _P, _I, _I, _P, _P, _I, _I, _P, _D, _I, _P, _P],
+    "im_dense_cloud": [_P, _P, _P, _P, _P, _I, _I, _I, _P, _L, _P, _P, _P, _P, _P, _P],
     "im_dod_chunk": [],
     "im_dod_max_cells": [],
     "im_dod_max_batch_cells": [],

@@ -81,6 +81,7 @@ class PointCloud:
         self.points = np.zeros((0, 3), np.float64)
         self.colors = None
         self.normals = None
+        self.confidence = None            # [n] float32 where the producer has one (`dense.build_dense_cloud`); not written to PLY
         if isinstance(points3d, np.ndarray):
             self.from_numpy(points3d, points_col)
         elif pcd_path is not None:

@@ -106,5 +106,10 @@ struct BaScratch : Carve {
     BaScratch(long long E, long long M) : parts(take<double>(BA_PART * (M / BA_SLOT_POINTS + E + 1))), cparts(take<double>(M / BA_SLOT_POINTS + E + 1)),
           keep(take<double>(BA_KEPT * (M > 0 ? M : 1))), slots(M / BA_SLOT_POINTS + E + 1) {}
 };
+// im_dense_cloud, n = h w > 0 pixels: sums [scan blocks of n]
+struct DenseCloudScratch : Carve {
+    Piece<long long> sums;
+    explicit DenseCloudScratch(long long n) : sums(take<long long>(blocks_of(n, SCAN_THREADS))) {}
+};
 
 }  // namespace im

@@ -1,0 +1,342 @@
+"""Two-view dense stereo: depth maps and the dense cloud of an epoch's stereo pair, on the device (csrc/dense.hip). In the reference this
+step is Metashape's: `MetashapeProject.build_dense_cloud` calls `chunk.buildDepthMaps(downscale=..., filter_mode=...)` and
+`chunk.buildDenseCloud(point_colors=True, point_confidence=True)` straight after the bundle adjustment (`metashape/metashape.py:198-240,
+361-371`) and exports `dense_{date}.ply`, which every later stage reads. Metashape's matcher is closed and is NOT reproduced: the stage has
+a definition of its own (csrc/dense_pixel.h, DESIGN §4, restated in tests/dense_oracle.py) - a plane sweep over fronto-parallel planes
+of each view scored by the zero-mean normalised cross-correlation of exact integer window sums, a left-right consistency check whose
+tolerance the reference's four `depth_filter` names select, and a cloud of the kept pixels with colours, camera-oriented normals and the
+score as confidence. Parity with Metashape is unpinned by construction. No host fallback: `default_engine(engine)`.
+
+Cameras are objects with `.K .R .t` (X_cam = R X_world + t) and optionally `.dist`, as `core.Camera` and the cameras of a
+`sfm.BundleResult`. Images are uint8 [h, w] or [h, w, 3] (RGB) numpy arrays or device tensors."""
+import logging
+from pathlib import Path
+from typing import NamedTuple, Optional
+
+import numpy as np
+import torch
+
+from ._lib import ptr
+from .core.point_cloud import PointCloud
+from .engine import default_engine, to_device
+from .utils.homography import inv3
+
+logger = logging.getLogger(__name__)
+
+MAX_SIDE, MAX_PLANES, MAX_RADIUS = 16384, 4096, 7
+DEPTH_FILTERS = {"NoFiltering": None, "MildFiltering": 2.0, "ModerateFiltering": 1.0, "AggressiveFiltering": 0.5}
+
+
+def filter_tolerance(depth_filter: str) -> Optional[float]:
+    """tau of the consistency check, in plane steps of the other view, for one of the reference's four names; None skips the check.
+    An unknown name raises the reference's ValueError (`metashape.py:217-220`)."""
+    if depth_filter not in DEPTH_FILTERS:
+        raise ValueError("Error: invalid choise of depth filtering. Choose one in [NoFiltering, MildFiltering, ModerateFiltering, AggressiveFiltering]")
+    return DEPTH_FILTERS[depth_filter]
+
+
+# ---- images: grey, downscaling ------------------------------------------------------------------------------------------------------------
+def _tensor(image) -> torch.Tensor:
+    t = image if torch.is_tensor(image) else torch.from_numpy(np.ascontiguousarray(image))
+    if t.dtype != torch.uint8 or not (t.ndim == 2 or (t.ndim == 3 and t.shape[2] == 3)):
+        raise ValueError(f"dense: a uint8 [h, w] or [h, w, 3] image is expected (got {t.dtype}, shape {tuple(t.shape)})")
+    return t
+
+
+def to_grey(image):
+    """(77 R + 150 G + 29 B + 128) >> 8 of an RGB image, in integers; a grey image is returned as it is. numpy in, numpy out; tensor in, tensor out."""
+    t = _tensor(image)
+    if t.ndim == 2:
+        return image
+    i = t.to(torch.int32)
+    g = ((77 * i[..., 0] + 150 * i[..., 1] + 29 * i[..., 2] + 128) >> 8).to(torch.uint8)
+    return g if torch.is_tensor(image) else g.numpy()
+
+
+def downscale_image(image, f: int):
+    """The exact integer mean (sum + f^2 // 2) // f^2 of f x f blocks, per channel; rows and columns beyond the last whole block are dropped."""
+    f = _factor(f)
+    t = _tensor(image)
+    if f == 1:
+        return image
+    h, w = t.shape[0] // f, t.shape[1] // f
+    if h < 1 or w < 1:
+        raise ValueError(f"dense: the image is smaller than one {f} x {f} block")
+    b = t[:h * f, :w * f].to(torch.int32).reshape((h, f, w, f) + tuple(t.shape[2:]))
+    out = torch.div(b.sum((1, 3)) + (f * f) // 2, f * f, rounding_mode="floor").to(torch.uint8)
+    return out if torch.is_tensor(image) else out.numpy()
+
+
+def downscale_K(K, f: int) -> np.ndarray:
+    """K of the downscaled image: the centre of pixel u of the small image lies at f u + (f - 1) / 2 of the large one."""
+    f = _factor(f)
+    K = np.array(K, np.float64).reshape(3, 3)
+    if f == 1:
+        return K
+    S = np.array([[1.0 / f, 0.0, -(f - 1) / (2.0 * f)], [0.0, 1.0 / f, -(f - 1) / (2.0 * f)], [0.0, 0.0, 1.0]])
+    return S @ K
+
+
+def _factor(f) -> int:
+    if int(f) != f or not 1 <= int(f) <= 64:
+        raise ValueError(f"dense: downscale must be an integer in 1..64 (got {f})")
+    return int(f)
+
+
+# ---- geometry on the host: a few 3 x 3 products ---------------------------------------------------------------------------------------------
+def _pose(cam):
+    R, t = np.asarray(cam.R, np.float64).reshape(3, 3), np.asarray(cam.t, np.float64).reshape(3)
+    if not (np.isfinite(R).all() and np.isfinite(t).all()):
+        raise ValueError("dense: a camera pose is not finite")
+    return R, t
+
+
+def relative_pose(cam0, cam1):
+    """(R, t) of X1 = R X0 + t."""
+    R0, t0 = _pose(cam0)
+    R1, t1 = _pose(cam1)
+    R = R1 @ R0.T
+    return R, t1 - R @ t0
+
+
+def sweep_matrices(K0, K1, R, t):
+    """A = K1 R inv(K0) and B = K1 t e3^T inv(K0), [9] float64 each: the homography of the plane of inverse depth w is A + w B."""
+    Ki = inv3(np.asarray(K0, np.float64).reshape(3, 3))
+    K1 = np.asarray(K1, np.float64).reshape(3, 3)
+    A = K1 @ np.asarray(R, np.float64).reshape(3, 3) @ Ki
+    B = np.outer(K1 @ np.asarray(t, np.float64).reshape(3), Ki[2])
+    return np.ascontiguousarray(A.reshape(9)), np.ascontiguousarray(B.reshape(9))
+
+
+def _corner_steps(A, B, shape, w_first, w_step, D) -> float:
+    """The largest distance, in pixels of the other view, that two adjacent planes put between the images of a corner of `shape`."""
+    h, w = shape
+    corners = np.array([[0.0, 0.0, 1.0], [w - 1.0, 0.0, 1.0], [0.0, h - 1.0, 1.0], [w - 1.0, h - 1.0, 1.0]])
+    ws = w_first + np.arange(D, dtype=np.float64) * w_step
+    H = A.reshape(1, 3, 3) + ws[:, None, None] * B.reshape(1, 3, 3)
+    p = np.einsum("dij,cj->dci", H, corners)
+    with np.errstate(all="ignore"):
+        xy = p[..., :2] / p[..., 2:3]
+        step = np.linalg.norm(np.diff(xy, axis=0), axis=-1)
+    step = step[np.isfinite(step)]
+    return float(step.max()) if step.size else 0.0
+
+
+def plane_schedule(cam0, cam1, d_min: float, d_max: float, max_step_px: float = 1.0, shape=None):
+    """(w_first, w_step, D): D inverse depths from 1 / d_max to 1 / d_min of view `cam0`, evenly spaced, with D the smallest count found
+    for which adjacent planes move no corner of cam0's image by more than `max_step_px` pixels in cam1's. `shape` = (h, w) of the image
+    (default cam0's height and width)."""
+    if not (0.0 < d_min <= d_max < np.inf) or not (max_step_px > 0.0):
+        raise ValueError(f"plane_schedule: 0 < d_min <= d_max and max_step_px > 0 are expected (got {d_min}, {d_max}, {max_step_px})")
+    shape = (int(cam0.height), int(cam0.width)) if shape is None else shape
+    R, t = relative_pose(cam0, cam1)
+    A, B = sweep_matrices(cam0.K, cam1.K, R, t)
+    w_first, w_last = 1.0 / d_max, 1.0 / d_min
+    if w_last == w_first:
+        return w_first, 0.0, 1
+    D = 2
+    for _ in range(64):
+        step = _corner_steps(A, B, shape, w_first, (w_last - w_first) / (D - 1), D)
+        if step <= max_step_px:
+            return w_first, (w_last - w_first) / (D - 1), D
+        D = max(D + 1, int(np.ceil((D - 1) * step / max_step_px)) + 1)
+        if D > MAX_PLANES:
+            break
+    raise ValueError(f"plane_schedule: the depth range {d_min}..{d_max} needs more than {MAX_PLANES} planes at {max_step_px} px per step; "
+                     f"narrow the range, raise max_step_px or downscale")
+
+
+def depth_range_from_points(points3d, cam, percentiles=(1, 99), margin: float = 0.25):
+    """(d_min, d_max) for `cam` from a sparse cloud [n, 3] in world coordinates: the two percentiles of the depths of the points in front
+    of the camera, widened to lo / (1 + margin) and hi (1 + margin)."""
+    X = np.asarray(points3d, np.float64).reshape(-1, 3)
+    lo_p, hi_p = percentiles
+    if not (0.0 <= lo_p <= hi_p <= 100.0) or not (margin >= 0.0):
+        raise ValueError(f"depth_range_from_points: 0 <= percentiles[0] <= percentiles[1] <= 100 and margin >= 0 are expected (got {percentiles}, {margin})")
+    R, t = _pose(cam)
+    z = (X @ R.T + t)[:, 2]
+    z = z[np.isfinite(z) & (z > 0.0)]
+    if z.size == 0:
+        raise ValueError("depth_range_from_points: no point lies in front of the camera")
+    lo, hi = np.percentile(z, [lo_p, hi_p])
+    return float(lo / (1.0 + margin)), float(hi * (1.0 + margin))
+
+
+# ---- the three launches ---------------------------------------------------------------------------------------------------------------------
+class DepthMap(NamedTuple):
+    """One view's map on the device: plane [h, w] int16 (-1: dropped), w [h, w] float64 inverse depths, score [h, w] float32; the
+    (downscaled) image the colours come from, its grey form, K of that image, the pose and the schedule (w_first, w_step, D)."""
+    plane: torch.Tensor
+    w: torch.Tensor
+    score: torch.Tensor
+    image: torch.Tensor
+    grey: torch.Tensor
+    K: np.ndarray
+    R: np.ndarray
+    t: np.ndarray
+    schedule: tuple
+
+
+class _SmallCam(NamedTuple):
+    """K of the downscaled image with the camera's pose."""
+    K: np.ndarray
+    R: np.ndarray
+    t: np.ndarray
+
+
+def _check_sweep(h0, w0, h1, w1, D, radius, min_var):
+    for v in (h0, w0, h1, w1):
+        if not 1 <= v <= MAX_SIDE:
+            raise ValueError(f"dense: image sides must be 1..{MAX_SIDE} (got {v})")
+    if int(D) != D or not 1 <= D <= MAX_PLANES:
+        raise ValueError(f"dense: the number of planes must be 1..{MAX_PLANES} (got {D})")
+    if int(radius) != radius or not 1 <= radius <= MAX_RADIUS:
+        raise ValueError(f"dense: the window radius must be 1..{MAX_RADIUS} (got {radius})")
+    if int(min_var) != min_var or not 0 <= min_var <= 1 << 26:
+        raise ValueError(f"dense: min_var must be an integer in 0..2^26 (got {min_var})")
+
+
+def sweep(ref, src, A, B, w_first, w_step, D, radius=3, min_var=4, min_score=0.8, engine=None):
+    """`im_dense_sweep` on two grey device images: (plane, w, score) device tensors of ref's shape."""
+    h0, w0 = ref.shape
+    h1, w1 = src.shape
+    _check_sweep(h0, w0, h1, w1, D, radius, min_var)
+    eng = default_engine(engine)
+    dev = eng.device
+    ref, src = ref.to(dev).contiguous(), src.to(dev).contiguous()
+    A, B = np.ascontiguousarray(A, np.float64).reshape(9), np.ascontiguousarray(B, np.float64).reshape(9)
+    plane = torch.empty((h0, w0), dtype=torch.int16, device=dev)
+    w = torch.empty((h0, w0), dtype=torch.float64, device=dev)
+    score = torch.empty((h0, w0), dtype=torch.float32, device=dev)
+    eng.ctx.call("im_dense_sweep", ptr(ref), h0, w0, ptr(src), h1, w1, A.ctypes.data, B.ctypes.data, float(w_first), float(w_step), int(D), int(radius),
+                 int(min_var), float(min_score), ptr(plane), ptr(w), ptr(score), eng.stream_ptr())
+    return plane, w, score
+
+
+def consistency(map0: DepthMap, map1: DepthMap, depth_filter: str = "ModerateFiltering", engine=None) -> torch.Tensor:
+    """`im_dense_consistency`: keep [h, w] uint8 on the device for the pixels of `map0` against `map1`."""
+    tau = filter_tolerance(depth_filter)
+    eng = default_engine(engine)
+    h0, w0 = map0.plane.shape
+    h1, w1 = map1.plane.shape
+    keep = torch.empty((h0, w0), dtype=torch.uint8, device=eng.device)
+    if tau is None:
+        eng.ctx.call("im_dense_consistency", ptr(map0.plane), ptr(map0.w), h0, w0, None, None, h1, w1, None, 0.0, 0, ptr(keep), eng.stream_ptr())
+        return keep
+    R = map1.R @ map0.R.T
+    t = map1.t - R @ map0.t
+    pose = np.ascontiguousarray(np.concatenate([inv3(map0.K).reshape(9), R.reshape(9), t, map1.K.reshape(9)]))
+    eng.ctx.call("im_dense_consistency", ptr(map0.plane), ptr(map0.w), h0, w0, ptr(map1.plane), ptr(map1.w), h1, w1, pose.ctypes.data,
+                 float(tau * abs(map1.schedule[1])), 1, ptr(keep), eng.stream_ptr())
+    return keep
+
+
+def cloud_of(m: DepthMap, keep: torch.Tensor, engine=None):
+    """`im_dense_cloud`: (points [n, 3] float64, rgb [n, 3] uint8, normals [n, 3] float64, confidence [n] float32) device tensors of the kept
+    pixels of one map in row-major order. One count is read back."""
+    eng = default_engine(engine)
+    dev = eng.device
+    h, w = m.plane.shape
+    cap = h * w
+    xyz = torch.empty((cap, 3), dtype=torch.float64, device=dev)
+    rgb = torch.empty((cap, 3), dtype=torch.uint8, device=dev)
+    nrm = torch.empty((cap, 3), dtype=torch.float64, device=dev)
+    conf = torch.empty(cap, dtype=torch.float32, device=dev)
+    count = torch.zeros(1, dtype=torch.int64, device=dev)
+    cam = np.ascontiguousarray(np.concatenate([inv3(m.K).reshape(9), m.R.reshape(9), m.t]))
+    img = m.image.contiguous()
+    eng.ctx.call("im_dense_cloud", ptr(keep), ptr(m.w), ptr(m.score), ptr(img), 3 if img.ndim == 3 else 1, h, w, cam.ctypes.data, cap, ptr(xyz),
+                 ptr(rgb), ptr(nrm), ptr(conf), ptr(count), eng.stream_ptr())
+    n = int(count.item())
+    return xyz[:n], rgb[:n], nrm[:n], conf[:n]
+
+
+# ---- the stage --------------------------------------------------------------------------------------------------------------------------------
+def _prepare(image, cam, downscale, eng):
+    """The (undistorted, downscaled) image of one view on the device and its grey form."""
+    t = _tensor(image)
+    dist = getattr(cam, "dist", None)
+    if dist is not None and np.any(np.asarray(dist, np.float64) != 0.0):
+        from .sfm import undistort_image
+        t = _tensor(undistort_image(t.to(eng.device), cam, engine=eng))
+    t = downscale_image(t.to(eng.device), downscale).contiguous()
+    return t, to_grey(t).contiguous()
+
+
+def build_depth_maps(images, cameras, depth_range=None, sparse_points=None, downscale: int = 1, radius: int = 3, min_score: float = 0.8,
+                     min_var: int = 4, max_step_px: float = 1.0, engine=None):
+    """The depth maps of both views of a stereo pair, `chunk.buildDepthMaps` of the reference with a definition of this project's own
+    (module docstring): [DepthMap of view 0, DepthMap of view 1], on the device. `depth_range` = (d_min, d_max) in view 0 (and, through the
+    same points, view 1) or None: then `sparse_points` [n, 3] give it per view (`depth_range_from_points`). Images with a non-zero
+    `dist` are undistorted first (`sfm.undistort_image`)."""
+    if len(images) != 2 or len(cameras) != 2:
+        raise ValueError("build_depth_maps: a stereo pair has two images and two cameras")
+    downscale = _factor(downscale)
+    if depth_range is None and sparse_points is None:
+        raise ValueError("build_depth_maps: a depth_range or sparse_points to take it from are needed")
+    # everything that can be refused is refused before the first launch
+    shapes = [tuple(_tensor(im).shape[:2]) for im in images]
+    small_shapes = [(s[0] // downscale, s[1] // downscale) for s in shapes]
+    _check_sweep(*small_shapes[0], *small_shapes[1], 1, radius, min_var)
+    ranges = [tuple(depth_range) if depth_range is not None else depth_range_from_points(sparse_points, c) for c in cameras]
+    small = [_SmallCam(downscale_K(c.K, downscale), *_pose(c)) for c in cameras]
+    plans = []
+    for v in range(2):
+        schedule = plane_schedule(small[v], small[1 - v], ranges[v][0], ranges[v][1], max_step_px, shape=small_shapes[v])
+        plans.append((schedule, sweep_matrices(small[v].K, small[1 - v].K, *relative_pose(small[v], small[1 - v]))))
+    eng = default_engine(engine)
+    prepared = [_prepare(im, c, downscale, eng) for im, c in zip(images, cameras)]
+    maps = []
+    for v in range(2):
+        (w_first, w_step, D), (A, B) = plans[v]
+        plane, w, score = sweep(prepared[v][1], prepared[1 - v][1], A, B, w_first, w_step, D, radius, min_var, min_score, engine=eng)
+        maps.append(DepthMap(plane, w, score, prepared[v][0], prepared[v][1], small[v].K, small[v].R, small[v].t, (w_first, w_step, D)))
+    return maps
+
+
+def build_dense_cloud(images, cameras, sparse_points=None, depth_filter: str = "ModerateFiltering", downscale: int = 1, views=(0,), save_path=None,
+                      depth_range=None, radius: int = 3, min_score: float = 0.8, min_var: int = 4, max_step_px: float = 1.0, engine=None) -> PointCloud:
+    """`MetashapeProject.build_dense_cloud` of the reference with a definition of this project's own: the depth maps of the pair, their
+    consistency under `depth_filter`, and the cloud of the kept pixels of `views` (view 0's points first) as a `core.PointCloud` with
+    colours, normals turned towards the camera and `confidence` (the score, float32). `save_path` writes it as PLY (`dense_{date}.ply`)."""
+    filter_tolerance(depth_filter)
+    views = tuple(views)
+    if not views or any(v not in (0, 1) for v in views):
+        raise ValueError(f"build_dense_cloud: views are 0 and / or 1 (got {views})")
+    maps = build_depth_maps(images, cameras, depth_range, sparse_points, downscale, radius, min_score, min_var, max_step_px, engine=engine)
+    eng = default_engine(engine)
+    parts = []
+    for v in views:
+        keep = consistency(maps[v], maps[1 - v], depth_filter, engine=eng)
+        parts.append(cloud_of(maps[v], keep, engine=eng))
+    xyz, rgb, nrm, conf = (torch.cat([p[i] for p in parts]).cpu().numpy() for i in range(4))
+    pcd = PointCloud(points3d=xyz, points_col=rgb.astype(np.float64) / 255.0)
+    pcd.normals = nrm
+    pcd.confidence = conf
+    if save_path is not None:
+        pcd.write_ply(Path(save_path))
+    return pcd
+
+
+def dense_series(images, cameras, sparse_points=None, out_dir=None, dates=None, **options) -> list:
+    """`build_dense_cloud` for every epoch of a sequence: `images` a list of E pairs, `cameras` one pair, a list of E pairs or a list of E
+    `sfm.BundleResult` (as `bundle_adjust_epochs` returns them: their cameras and, unless `sparse_points` is given, their points are
+    taken), `sparse_points` None, one array or a list of E. With `out_dir`, epoch e is written to `dense_{dates[e]}.ply` (default e)."""
+    E = len(images)
+    results = list(cameras) if len(cameras) == E and all(hasattr(c, "cameras") and hasattr(c, "points3d") for c in cameras) else None
+    if results is not None:
+        pairs = [r.cameras for r in results]
+        if sparse_points is None:
+            sparse_points = [r.points3d for r in results]
+    else:
+        pairs = [cameras] if len(cameras) == 2 and not isinstance(cameras[0], (list, tuple)) else list(cameras)
+    if len(pairs) not in (1, E):
+        raise ValueError(f"dense_series: one camera pair or one per epoch ({E}) is expected (got {len(pairs)})")
+    if isinstance(sparse_points, list) and len(sparse_points) != E:
+        raise ValueError(f"dense_series: a list of sparse_points holds one entry per epoch ({E})")
+    out = []
+    for e in range(E):
+        path = None if out_dir is None else Path(out_dir) / f"dense_{dates[e] if dates is not None else e}.ply"
+        sp = sparse_points[e] if isinstance(sparse_points, list) else sparse_points
+        out.append(build_dense_cloud(images[e], pairs[e if len(pairs) > 1 else 0], sparse_points=sp, save_path=path, **options))
+    return out

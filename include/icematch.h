@@ -570,6 +570,42 @@ int im_ba_decide(im_ctx* ctx, const long long* d_off, int E, long long M, const 
 int im_ba_residuals(im_ctx* ctx, const long long* d_off, int E, long long M, long long max_points, const double* d_pts2, const double* d_obs,
                     const double* d_cams2, const double* d_state, double* d_res, void* stream);
 
+/* ---- two-view dense stereo: depth maps, their consistency and the dense cloud (what the driver gets from Metashape's
+ * `chunk.buildDepthMaps` and `chunk.buildDenseCloud`, `metashape.py:198-240`, straight after the bundle adjustment); csrc/dense.hip,
+ * csrc/dense_pixel.h. Metashape's matcher is closed and is NOT reproduced: the stage has a definition of its own, restated in
+ * tests/dense_oracle.py: bit-identical; parity with Metashape is unpinned by construction. All arrays in DEVICE memory unless named h_.
+ * im_dense_sweep: a plane sweep over D fronto-parallel planes of the ref view, inverse depths w_k = w_first + k w_step. d_ref [h0][w0] and
+ * d_src [h1][w1] are undistorted 8-bit grey images; h_A = K1 R inv(K0) and h_B = K1 t e3^T inv(K0), [9] row-major in HOST memory, with
+ * X1 = R X0 + t. Per plane and ref pixel H = A + w_k B, (x, y, z) = H (u, v, 1); the sample is invalid if z <= 0, a coordinate is not
+ * finite or one of the four taps lies outside src; x / z and y / z are rounded to 1/32 pixel (im_warp_perspective's rounding) and the
+ * warped value is the 18-bit integer b = sum of 5-bit weight products times pixel. Window of radius r, n = (2 r + 1)^2: exact integer sums;
+ * VA = n Saa - Sa^2, VB = n Sbb - Sb^2, C = n Sab - Sa Sb; invalid if the window leaves ref, holds an invalid sample, VA < n^2 min_var,
+ * VB < n^2 min_var 2^20 or a variance is zero; else s = C / sqrt(VA VB). The best plane is the largest s (ties to the lower index); the
+ * sub-plane offset 0.5 (s- - s+) / (s- - 2 s0 + s+) applies for 1 <= k <= D - 2 with both neighbours valid and a negative denominator.
+ * d_plane [h0][w0] int16 (-1: no plane scored or s0 < min_score; then w and score are 0), d_w [h0][w0] float64 = w_first + (k + off) w_step,
+ * d_score [h0][w0] float32. One block per im_dense_tile_w() x im_dense_tile_h() pixels; the tile is no part of the definition.
+ * im_dense_consistency: d_keep [h0][w0] uint8 = 1 where map 0 holds a plane and (check = 1) its point X1 = R (inv(K0) (u, v, 1) / w) + t
+ * lies in front of view 1, projects (rint) onto a pixel of map 1 that holds a plane, and |w1 - 1 / X1.z| <= tol. h_pose [30] in HOST memory
+ * = inv(K0) [9], R [9], t [3], K1 [9]. check = 0: d_keep = (plane0 >= 0), map 1 and the pose may be NULL.
+ * im_dense_cloud: the kept pixels in row-major order: d_xyz [capacity][3] float64 = R0^T (X0 - t0), d_rgb [capacity][3] uint8 = the bytes
+ * of d_img [h][w][channels] (1 or 3 channels; grey three times), d_nrm [capacity][3] float64 = the unit cross product of the differences
+ * of the neighbours' points along u and v (central where both neighbours are kept, one-sided where one is, zero where a direction has
+ * none), turned towards the camera centre, d_conf [capacity] float32 = the score. h_cam [21] in HOST memory = inv(K0) [9], R0 [9], t0 [3].
+ * *d_count = the number of kept pixels; rows from min(count, capacity) on are left untouched.
+ * All three return -83, without launching and with the outputs untouched, for a null required pointer, h or w outside 1..16384, D outside
+ * 1..4096, r outside 1..7, min_var negative or above 2^26, check outside 0..1, a negative or NaN tol, channels other than 1 or 3, a
+ * negative capacity or a camera that is not finite. Enqueue only. */
+int im_dense_tile_w(void);
+int im_dense_tile_h(void);
+int im_dense_sweep(im_ctx* ctx, const uint8_t* d_ref, int h0, int w0, const uint8_t* d_src, int h1, int w1, const double* h_A, const double* h_B,
+                   double w_first, double w_step, int D, int r, long long min_var, double min_score, int16_t* d_plane, double* d_w, float* d_score,
+                   void* stream);
+int im_dense_consistency(im_ctx* ctx, const int16_t* d_plane0, const double* d_w0, int h0, int w0, const int16_t* d_plane1, const double* d_w1, int h1,
+                         int w1, const double* h_pose, double tol, int check, uint8_t* d_keep, void* stream);
+int im_dense_cloud(im_ctx* ctx, const uint8_t* d_keep, const double* d_w, const float* d_score, const uint8_t* d_img, int channels, int h, int w,
+                   const double* h_cam, long long capacity, double* d_xyz, uint8_t* d_rgb, double* d_nrm, float* d_conf, long long* d_count,
+                   void* stream);
+
 /* ---- volume variations (`scripts/pcd_postprocessing/volume_variations.py`; `post_processing/cloudcompare_fun.py`:
  * `DemOfDifference.compute_volume` over CloudCompare's `ComputeVolume25D`; `post_processing/open3d_fun.py`: `filter_pcd_by_polyline`);
  * csrc/dod.hip, csrc/dod_cell.h. The DEM of difference of P pairs (ground, ceil) over E clouds that lie one behind the other in d_pts
