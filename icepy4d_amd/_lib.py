@@ -85,6 +85,7 @@ SIGNATURES = {
     "im_triangulate_linear": [_P, _P, _P, _P, _P, _I, _P, _P],
     "im_forient": [_P, _P, _I, _I, _I, _I, _P, _P],
     "im_template_match_oc": [_P, _P, _I, _I, _P, _I, _I, _I, _P, _P, _I, _I, _I, _I, _P, _P],
+    "im_template_match_corr": [_P, _P, _I, _I, _P, _I, _I, _I, _P, _P, _I, _I, _I, _I, _P, _P],
     "im_dsm_round": [_P, _P, _L, _F, _P, _P, _P, _P, _P, _P],
     "im_dsm_group_mean": [_P, _P, _P, _P, _P, _P, _P, _L, _P, _P, _P, _P, _P],
     "im_dsm_rasterize": [_P, _P, _P, _P, _P, _P, _L, _P, _P, _I, _P, _I, _D, _D, _D, _D, _D, _P, _P],

@@ -10,114 +10,29 @@
 //   tm_corr_kernel   C of a tile of one pair: B rows of the tile and a chunk of template rows / columns staged in LDS (both
 //                    channels in separate planes), each thread a 1 x 16 strip of C slid along the template columns from a
 //                    32-value register window; template rows of a chunk split over `ks` thread groups, summed in a fixed order
-//   tm_peak_kernel   one wave per pair: argmax (first maximum in row-major order), mean |C|, edge test and the sub-pixel
-//                    centroid of `:303-325` with numpy's own summation order for the float32 / float64 sums of the window
+//   tm_peak_kernel   one wave per pair: the scan of both windows for a NaN or an infinity, argmax (first maximum in row-major order),
+//                    mean |C|, edge test and the sub-pixel centroid of `:303-325` with numpy's own summation order for the float32 /
+//                    float64 sums of the window
+// The arithmetic of a pair, the plan and the summation order of C are csrc/tm_pair.h, which a host program compiles too.
 #include <cmath>
 
 #include "common.h"
 #include "ctx.h"
+#include "tm_pair.h"
 
 namespace im {
 namespace {
 
-constexpr int TM_DX = 16;                       // C columns per thread
-constexpr int TM_MAX_THREADS = 256;
-constexpr int TM_LDS_FLOATS = 16384;            // 64 KiB of LDS per block: two blocks of 256 threads per CU at least
+static_assert(TM_WAVE == IM_WAVE, "tm_pair.h plans for the wave of common.h");
 
-struct TmPlan {
-    int R;            // S - T: C is R x R
-    int gy, gx, ks;   // rows of C, 16-column strips of C and template-row groups per block
-    int ny, nx;       // tiles of C per pair
-    int kt, kx;       // template rows / columns staged per chunk (kt a multiple of ks, kx a multiple of 16)
-    int pitch;        // floats per staged B row (== 4 mod 16: the 16 lanes of a ds_read_b128 group hit 16 different bank quads)
-    int brows;        // gy + kt - 1
-    int threads;
-    int lds_floats;
-};
-
-int tm_stage_floats(const TmPlan& p) { return 2 * p.brows * p.pitch + 2 * p.kt * p.kx; }
-
-TmPlan tm_plan(int T, int S) {
-    TmPlan p;
-    p.R = S - T;
-    const int R = p.R;
-    auto up = [](int a, int b) { return (a + b - 1) / b * b; };
-    p.gy = R < 16 ? R : (up(R, 32) <= up(R, 16) ? 32 : 16);
-    const int mx = (R + TM_DX - 1) / TM_DX;
-    p.gx = std::min(mx, TM_MAX_THREADS / p.gy);
-    p.nx = (mx + p.gx - 1) / p.gx;
-    p.gx = (mx + p.nx - 1) / p.nx;
-    p.ny = (R + p.gy - 1) / p.gy;
-    p.ks = std::max(1, std::min(TM_MAX_THREADS / (p.gy * p.gx), T));
-    p.kx = std::min(up(T, 16), 128);
-    auto set_rows = [&](int kt) { p.kt = kt; p.brows = p.gy + kt - 1; p.pitch = TM_DX * p.gx + p.kx + 4; };
-    set_rows(p.ks);
-    while (tm_stage_floats(p) > TM_LDS_FLOATS && p.ks > 1) { p.ks /= 2; set_rows(p.ks); }
-    while (tm_stage_floats(p) > TM_LDS_FLOATS && p.kx > 16) { p.kx -= 16; set_rows(p.ks); }
-    // as many template rows per chunk as fit, in chunks of equal size
-    int kt_max = p.ks;
-    for (int kt = 2 * p.ks; kt <= up(T, p.ks); kt += p.ks) {
-        set_rows(kt);
-        if (tm_stage_floats(p) > TM_LDS_FLOATS) break;
-        kt_max = kt;
-    }
-    const int nchunks = (T + kt_max - 1) / kt_max;
-    set_rows(up((T + nchunks - 1) / nchunks, p.ks));
-    p.threads = up(p.gy * p.gx * p.ks, IM_WAVE);
-    p.lds_floats = std::max(tm_stage_floats(p), p.ks > 1 ? p.threads * TM_DX : 0);
-    return p;
-}
-
-// Window of one pair (`templatematch.py:268-294`). `valid` = the reference correlates this pair.
-struct PairWin {
-    bool valid;
-    long arow, acol, brow, bcol;
-    double pu, pv, initdu, initdv;
-};
-
-__device__ PairWin pair_window(const double* __restrict__ pairs, const int32_t* __restrict__ bidx, int n_b, long i, int T, int S, int ha,
-                               int wa, int hb, int wb) {
-    const double u = pairs[4 * i], v = pairs[4 * i + 1], idu = pairs[4 * i + 2], idv = pairs[4 * i + 3];
-    PairWin w;
-    w.valid = false;
-    w.arow = w.acol = w.brow = w.bcol = 0;
-    w.initdu = w.initdv = NAN;
-    w.pu = u;   // `:264-265`: a NaN u is skipped before anything is written back
-    w.pv = v;
-    if (isnan(u)) return w;
-    const double th = (T & 1) ? 0.5 : 0.0, sh = (S & 1) ? 0.5 : 0.0;   // T / 2 % 1, S / 2 % 1
-    const double acx = rint(u) - th, acy = rint(v) - th;                 // np.round: half to even, as rint
-    const double bcx = rint(u + idu) - sh, bcy = rint(v + idv) - sh;
-    w.pu = acx;
-    w.pv = acy;
-    w.initdu = bcx - acx;
-    w.initdv = bcy - acy;
-    if (isnan(u + v)) return w;
-    // `.astype(int)` truncates toward zero; the reference skips a lower bound < 0 or an upper bound >= the image size
-    const double b0 = trunc(bcy - S / 2.0), b1 = trunc(bcy + S / 2.0), c0 = trunc(bcx - S / 2.0), c1 = trunc(bcx + S / 2.0);
-    const double a0 = trunc(acy - T / 2.0), a1 = trunc(acy + T / 2.0), d0 = trunc(acx - T / 2.0), d1 = trunc(acx + T / 2.0);
-    if (!(b0 >= 0) || !(a0 >= 0) || !(c0 >= 0) || !(d0 >= 0)) return w;
-    if (!(b1 < hb) || !(a1 < ha) || !(c1 < wb) || !(d1 < wa)) return w;
-    w.valid = (unsigned)bidx[i] < (unsigned)n_b;      // a B-image index out of range leaves the pair's outputs NaN
-    w.brow = (long)b0; w.bcol = (long)c0; w.arow = (long)a0; w.acol = (long)d0;
-    return w;
-}
-
-// r = convolve2d(img, [[1, 0, i], [0, 0, 0], [-i, 0, -1]], "same"): Re = img[y+1][x+1] - img[y-1][x-1], Im = img[y+1][x-1] - img[y-1][x+1]
 __global__ __launch_bounds__(256) void forient_kernel(const void* __restrict__ img, int dtype, int h, int w, float2* __restrict__ out) {
     const long n = blockIdx.y;
     const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.z;
     if (x >= w) return;
     const long base = n * (long)h * w;
-    auto at = [&](int yy, int xx) -> float {
-        if (yy < 0 || yy >= h || xx < 0 || xx >= w) return 0.f;          // convolve2d(mode="same"): zero padding
-        const long k = base + (long)yy * w + xx;
-        return dtype == 0 ? (float)static_cast<const uint8_t*>(img)[k] : static_cast<const float*>(img)[k];
-    };
-    const float re = at(y + 1, x + 1) - at(y - 1, x - 1);
-    const float im = at(y + 1, x - 1) - at(y - 1, x + 1);
-    const double m = sqrt((double)re * re + (double)im * im);           // np.abs; a modulus of 0 is set to 1
-    out[base + (long)y * w + x] = m == 0.0 ? make_float2(re, im) : make_float2((float)(re / m), (float)(im / m));
+    float re, im;
+    forient_pixel(img, dtype, base, h, w, y, x, re, im);
+    out[base + (long)y * w + x] = make_float2(re, im);
 }
 
 __global__ __launch_bounds__(TM_MAX_THREADS) void tm_corr_kernel(const float2* __restrict__ A, int ha, int wa, const float2* __restrict__ B,
@@ -221,26 +136,10 @@ __global__ __launch_bounds__(TM_MAX_THREADS) void tm_corr_kernel(const float2* _
     }
 }
 
-// numpy's pairwise summation of n <= 128 values (`pairwise_sum` of umath loops), started from the reduction identity 0
-template <typename T, typename F>
-__device__ T np_sum_small(int n, F get) {
-    if (n < 8) {
-        T r = 0;
-        for (int i = 0; i < n; ++i) r += get(i);
-        return (T)0 + r;
-    }
-    T r[8];
-    for (int j = 0; j < 8; ++j) r[j] = get(j);
-    int i = 8;
-    for (; i < n - n % 8; i += 8)
-        for (int j = 0; j < 8; ++j) r[j] += get(i + j);
-    T res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
-    for (; i < n; ++i) res += get(i);
-    return (T)0 + res;
-}
-
-// one wave per pair: `templatematch.py:303-329`
-__global__ __launch_bounds__(256) void tm_peak_kernel(const double* __restrict__ pairs, const int32_t* __restrict__ bidx, int n_b, long pair0, long n_batch, int T, int S, int ha, int wa,
+// one wave per pair: `templatematch.py:303-329`. A pair whose template or search window holds a NaN or an infinity keeps NaN in du, dv,
+// peakCorr and meanAbsCorr, as the reference's FFT of such a window leaves them.
+__global__ __launch_bounds__(256) void tm_peak_kernel(const float2* __restrict__ A, const float2* __restrict__ B, const double* __restrict__ pairs,
+                                                      const int32_t* __restrict__ bidx, int n_b, long pair0, long n_batch, int T, int S, int ha, int wa,
                                                       int hb, int wb, const float* __restrict__ C, long n_pairs, double* __restrict__ out) {
     const long pl = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
@@ -258,39 +157,25 @@ __global__ __launch_bounds__(256) void tm_peak_kernel(const double* __restrict__
         o_du[pi] = NAN; o_dv[pi] = NAN; o_pk[pi] = NAN; o_mc[pi] = NAN;
     }
     if (!w.valid) return;
+    const float* Bimg = reinterpret_cast<const float*>(B + (long)bidx[pi] * hb * wb);
+    const bool bad = tm_window_not_finite(reinterpret_cast<const float*>(A), w.arow, w.acol, wa, T, lane) ||
+                     tm_window_not_finite(Bimg, w.brow, w.bcol, wb, S, lane);
+    if (__any(bad)) return;
     const int R = S - T, n = R * R;
     const float* Cp = C + pl * (long)n;
-    float best = -INFINITY;
-    int bi = n;
-    double sabs = 0.0;
-    for (int e = lane; e < n; e += 64) {
-        const float c = Cp[e];
-        if (c > best || bi == n) { best = c; bi = e; }
-        sabs += fabs((double)c);
-    }
+    float best;
+    int bi;
+    double sabs;
+    tm_lane_scan(Cp, n, lane, best, bi, sabs);
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
-        const float ob = __shfl_xor(best, o);
-        const int oi = __shfl_xor(bi, o);
-        if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
+        tm_best_merge(best, bi, __shfl_xor(best, o), __shfl_xor(bi, o));
         sabs += __shfl_xor(sabs, o);
     }
     if (lane != 0) return;
-    o_mc[pi] = (double)(float)(sabs / n);     // np.mean of a float32 array is a float32
-    const int mi = bi / R, mj = bi - mi * R;
-    const int edge = min(min(mi, mj), min(R - 1 - mi, R - 1 - mj));
-    if (edge == 0) return;                    // a peak on the border of C is not trusted
-    const int ww = min(edge, 4), side = 2 * ww + 1, m = side * side;
-    auto cw = [&](int e) { return Cp[(mi - ww + e / side) * R + mj - ww + e % side]; };
-    const float mean_abs = np_sum_small<float>(m, [&](int e) { return fabsf(cw(e)); }) / (float)m;
-    auto cpos = [&](int e) { const float c = cw(e) - mean_abs; return c < 0.f ? 0.f : c; };
-    const float tot = np_sum_small<float>(m, cpos);
-    const double wkeep = R / 2.0;             // C_uu = C_vv = arange(-wkeep, wkeep + 1)
-    const double cv = np_sum_small<double>(m, [&](int e) { return (-wkeep + (mi - ww + e / side)) * (double)(cpos(e) / tot); });
-    const double cu = np_sum_small<double>(m, [&](int e) { return (-wkeep + (mj - ww + e % side)) * (double)(cpos(e) / tot); });
-    o_du[pi] = cu + w.initdu;
-    o_dv[pi] = cv + w.initdv;
-    o_pk[pi] = (double)best;
+    double r[4];
+    tm_peak_tail(Cp, R, bi, best, sabs, w.initdu, w.initdv, r);
+    o_du[pi] = r[0]; o_dv[pi] = r[1]; o_pk[pi] = r[2]; o_mc[pi] = r[3];
 }
 
 hipError_t launch_forient(const void* img, int dtype, int n, int h, int w, float* out, hipStream_t s) {
@@ -305,10 +190,10 @@ hipError_t launch_corr(const TmPlan& p, long blocks, const float2* A, int ha, in
     return hipGetLastError();
 }
 
-hipError_t launch_peak(const double* pairs, const int32_t* bidx, int n_b, long pair0, long nb, int T, int S, int ha, int wa, int hb, int wb,
+hipError_t launch_peak(const float2* A, const float2* B, const double* pairs, const int32_t* bidx, int n_b, long pair0, long nb, int T, int S, int ha, int wa, int hb, int wb,
                        const float* C, long n_pairs, double* out, hipStream_t s) {
-    hipLaunchKernelGGL(tm_peak_kernel, dim3((unsigned)blocks_of(nb, 4)), dim3(256), 0, s, pairs, bidx, n_b, pair0, nb, T, S, ha, wa, hb, wb, C,
-                       n_pairs, out);
+    hipLaunchKernelGGL(tm_peak_kernel, dim3((unsigned)blocks_of(nb, 4)), dim3(256), 0, s, A, B, pairs, bidx, n_b, pair0, nb, T, S, ha, wa, hb,
+                       wb, C, n_pairs, out);
     return hipGetLastError();
 }
 
@@ -328,13 +213,20 @@ extern "C" int im_forient(im_ctx* ctx, const void* d_img, int dtype, int n_image
     return 0;
 }
 
+// what im_template_match_oc and im_template_match_corr refuse; 0 when the arguments are fine
+static int tm_refuse(im_ctx* ctx, const char* who, const float* d_a, int ha, int wa, const float* d_b, int n_b, int hb, int wb, const double* d_pairs,
+                     const int32_t* d_bidx, int n_pairs, int T, int S, const void* d_out) {
+    if (!d_a || !d_b || !d_pairs || !d_bidx || !d_out || n_pairs < 0 || n_b < 1 || ha < 0 || wa < 0 || hb < 0 || wb < 0)
+        return ctx->fail(-72, "%s: bad arguments", who);
+    if (T < 1 || S <= T) return ctx->fail(-72, "%s: need 1 <= template width < search width (got %d, %d)", who, T, S);
+    return 0;
+}
+
 extern "C" int im_template_match_oc(im_ctx* ctx, const float* d_a, int ha, int wa, const float* d_b, int n_b, int hb, int wb,
                                     const double* d_pairs, const int32_t* d_bidx, int n_pairs, int T, int S, int conj_b,
                                     double* d_out, void* stream) {
     IM_CHECK_CTX(ctx);
-    if (!d_a || !d_b || !d_pairs || !d_bidx || !d_out || n_pairs < 0 || n_b < 1 || ha < 0 || wa < 0 || hb < 0 || wb < 0)
-        return ctx->fail(-72, "im_template_match_oc: bad arguments");
-    if (T < 1 || S <= T) return ctx->fail(-72, "im_template_match_oc: need 1 <= template width < search width (got %d, %d)", T, S);
+    if (const int rc = tm_refuse(ctx, "im_template_match_oc", d_a, ha, wa, d_b, n_b, hb, wb, d_pairs, d_bidx, n_pairs, T, S, d_out)) return rc;
     if (!n_pairs) return 0;
     hipStream_t s = (hipStream_t)stream;
     const TmPlan p = tm_plan(T, S);
@@ -352,8 +244,24 @@ extern "C" int im_template_match_oc(im_ctx* ctx, const float* d_a, int ha, int w
         const long blocks = nb * p.ny * p.nx;
         if (blocks > 0x7fffffffL) return ctx->fail(-72, "im_template_match_oc: too many pairs per launch");
         IM_LAUNCH(ctx, "tm_corr", s, launch_corr(p, blocks, A, ha, wa, B, hb, wb, d_pairs, d_bidx, n_b, p0, T, S, isign, C, s));
-        IM_LAUNCH(ctx, "tm_peak", s, launch_peak(d_pairs, d_bidx, n_b, p0, nb, T, S, ha, wa, hb, wb, C, (long)n_pairs, d_out, s));
+        IM_LAUNCH(ctx, "tm_peak", s, launch_peak(A, B, d_pairs, d_bidx, n_b, p0, nb, T, S, ha, wa, hb, wb, C, (long)n_pairs, d_out, s));
     }
     IM_GUARD_CHECK(ctx, s, "im_template_match_oc");
+    return 0;
+}
+
+extern "C" int im_template_match_corr(im_ctx* ctx, const float* d_a, int ha, int wa, const float* d_b, int n_b, int hb, int wb,
+                                      const double* d_pairs, const int32_t* d_bidx, int n_pairs, int T, int S, int conj_b, float* d_c,
+                                      void* stream) {
+    IM_CHECK_CTX(ctx);
+    if (const int rc = tm_refuse(ctx, "im_template_match_corr", d_a, ha, wa, d_b, n_b, hb, wb, d_pairs, d_bidx, n_pairs, T, S, d_c)) return rc;
+    if (!n_pairs) return 0;
+    hipStream_t s = (hipStream_t)stream;
+    const TmPlan p = tm_plan(T, S);
+    const long blocks = (long)n_pairs * p.ny * p.nx;
+    if (blocks > 0x7fffffffL) return ctx->fail(-72, "im_template_match_corr: too many pairs per launch");
+    IM_LAUNCH(ctx, "tm_corr", s, launch_corr(p, blocks, reinterpret_cast<const float2*>(d_a), ha, wa, reinterpret_cast<const float2*>(d_b), hb, wb,
+                                             d_pairs, d_bidx, n_b, 0, T, S, conj_b ? 1.f : -1.f, d_c, s));
+    IM_GUARD_CHECK(ctx, s, "im_template_match_corr");
     return 0;
 }

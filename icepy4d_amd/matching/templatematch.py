@@ -6,7 +6,9 @@ engine of device 0). There is no CPU fallback: without a HIP device the calls ra
 `OC` correlates every point of a call in ONE launch instead of the reference's per-point FFT loop, and `match_many` goes further:
 one A image against several B images (what `utils.track_targets.TrackTargets.track` uses for all epochs at once).
 Numerics (tests/test_gpu_templatematch.py): the correlation is the direct fp32 sum of the reference's (S - T)^2 block instead of
-complex64 FFTs, so peak / mean correlations agree to ~1e-7 T^2 and du / dv to ~1e-4 px; NaN patterns and pu / pv are identical."""
+complex64 FFTs, so peak / mean correlations agree to ~1e-7 T^2 and du / dv to ~1e-4 px; NaN patterns and pu / pv are identical.
+A point whose template or search window holds a NaN or an infinity (a float image with masked pixels) gets NaN for du, dv, peakCorr
+and meanAbsCorr, as the reference's FFT of such a window gives."""
 from typing import List, Tuple
 
 import numpy as np

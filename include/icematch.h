@@ -260,10 +260,17 @@ int im_forient(im_ctx* ctx, const void* d_img, int dtype, int n_images, int h, i
  *   d_a [ha][wa] float2: orientation map of A;  d_b [n_b][hb][wb] float2: orientation maps of the B images
  *   d_pairs [n_pairs][4] double: u, v, initialdu, initialdv;  d_bidx [n_pairs] int32: the B image of every pair
  *   T, S: template / search width (1 <= T < S);  conj_b: the reference's `B = np.conj(B)` was applied (1) or not (0)
- *   d_out [6][n_pairs] double: pu, pv (the centres used), du, dv, peakCorr, meanAbsCorr; NaN wherever the reference leaves NaN.
+ *   d_out [6][n_pairs] double: pu, pv (the centres used), du, dv, peakCorr, meanAbsCorr; NaN wherever the reference leaves NaN, which
+ *   includes every pair whose T x T template or S x S search window holds a NaN or an infinity (its FFT spreads it over all of C).
  * C = Re(corr(A window, conj B window)) over the (S - T)^2 valid offsets is computed directly in fp32. Enqueue only. */
 int im_template_match_oc(im_ctx* ctx, const float* d_a, int ha, int wa, const float* d_b, int n_b, int hb, int wb, const double* d_pairs,
                          const int32_t* d_bidx, int n_pairs, int T, int S, int conj_b, double* d_out, void* stream);
+/* The block C of im_template_match_oc itself, for tests: the same inputs, the same kernel and plan, written to d_c [n_pairs][S - T][S - T]
+ * float instead of the library's scratch. The plane of a pair that the reference does not correlate is left untouched. The sums are raw:
+ * the rule that a NaN or an infinity in either window of a pair turns that pair's du, dv, peakCorr and meanAbsCorr into NaN belongs to
+ * im_template_match_oc alone. Both refuse bad arguments with -72. Enqueue only. */
+int im_template_match_corr(im_ctx* ctx, const float* d_a, int ha, int wa, const float* d_b, int n_b, int hb, int wb, const double* d_pairs,
+                           const int32_t* d_bidx, int n_pairs, int T, int S, int conj_b, float* d_c, void* stream);
 
 /* ---- DSM and orthophoto rasters (`src/icepy4d/utils/dsm_orthophoto.py`, `sfm/interpolate_colors.py`, `sfm/geometry.py`) ------------
  * The binning of `build_dsm` (`dsm_orthophoto.py:40-81`) in two calls around three stable sorts done by the caller:
