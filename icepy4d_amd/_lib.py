@@ -123,6 +123,10 @@ SIGNATURES = {
     "im_dense_sweep": [_P, _P, _I, _I, _P, _I, _I, _P, _P, _D, _D, _I, _I, _L, _D, _P, _P, _P, _P],
     "im_dense_consistency": [_P, _P, _P, _I, _I, _P, _P, _I, _I, _P, _D, _I, _P, _P],
     "im_dense_cloud": [_P, _P, _P, _P, _P, _I, _I, _I, _P, _L, _P, _P, _P, _P, _P, _P],
+    "im_dense_sgm_max_planes": [],
+    "im_dense_costs": [_P, _P, _I, _I, _P, _I, _I, _P, _P, _D, _D, _I, _I, _L, _P, _P],
+    "im_dense_sgm": [_P, _P, _I, _I, _I, _I, _I, _I, _P, _P],
+    "im_dense_sgm_choose": [_P, _P, _P, _I, _I, _I, _D, _D, _D, _P, _P, _P, _P],
     "im_dod_chunk": [],
     "im_dod_max_cells": [],
     "im_dod_max_batch_cells": [],

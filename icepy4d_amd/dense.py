@@ -6,6 +6,9 @@ a definition of its own (csrc/dense_pixel.h, DESIGN §4, restated in tests/dense
 of each view scored by the zero-mean normalised cross-correlation of exact integer window sums, a left-right consistency check whose
 tolerance the reference's four `depth_filter` names select, and a cloud of the kept pixels with colours, camera-oriented normals and the
 score as confidence. Parity with Metashape is unpinned by construction. No host fallback: `default_engine(engine)`.
+`regularisation="sgm"` replaces the per-pixel choice of the sweep by a semi-global one (csrc/dense_sgm.hip, csrc/sgm_pixel.h, restated in
+tests/sgm_oracle.py): the scores as an 8-bit cost volume, min-plus path costs summed over four or eight directions, the plane of least
+sum. It is this project's own definition too, not Metashape's depth filter; the default None is the plain sweep.
 
 Cameras are objects with `.K .R .t` (X_cam = R X_world + t) and optionally `.dist`, as `core.Camera` and the cameras of a
 `sfm.BundleResult`. Images are uint8 [h, w] or [h, w, 3] (RGB) numpy arrays or device tensors."""
@@ -24,6 +27,8 @@ from .utils.homography import inv3
 logger = logging.getLogger(__name__)
 
 MAX_SIDE, MAX_PLANES, MAX_RADIUS = 16384, 4096, 7
+MAX_SGM_PLANES, MAX_PENALTY, MAX_VOLUME = 256, 4095, 1 << 32
+REGULARISATIONS = (None, "sgm")
 DEPTH_FILTERS = {"NoFiltering": None, "MildFiltering": 2.0, "ModerateFiltering": 1.0, "AggressiveFiltering": 0.5}
 
 
@@ -196,11 +201,94 @@ def _check_sweep(h0, w0, h1, w1, D, radius, min_var):
         raise ValueError(f"dense: min_var must be an integer in 0..2^26 (got {min_var})")
 
 
-def sweep(ref, src, A, B, w_first, w_step, D, radius=3, min_var=4, min_score=0.8, engine=None):
-    """`im_dense_sweep` on two grey device images: (plane, w, score) device tensors of ref's shape."""
+def _check_regularisation(regularisation, p1, p2, paths):
+    if regularisation not in REGULARISATIONS:
+        raise ValueError(f"dense: regularisation is None or 'sgm' (got {regularisation!r})")
+    if regularisation is None:
+        return
+    if int(p1) != p1 or int(p2) != p2 or not 0 <= p1 <= p2 <= MAX_PENALTY:
+        raise ValueError(f"dense: the penalties must be integers with 0 <= p1 <= p2 <= {MAX_PENALTY} (got {p1}, {p2})")
+    if paths not in (4, 8):
+        raise ValueError(f"dense: paths must be 4 or 8 (got {paths})")
+
+
+def _check_volume(h0, w0, D):
+    if int(D) != D or not 1 <= D <= MAX_SGM_PLANES:
+        raise ValueError(f"dense: semi-global aggregation holds at most {MAX_SGM_PLANES} planes (the schedule has {D}); raise downscale or max_step_px")
+    for v in (h0, w0):
+        if not 1 <= v <= MAX_SIDE:
+            raise ValueError(f"dense: image sides must be 1..{MAX_SIDE} (got {v})")
+    if h0 * w0 * int(D) > MAX_VOLUME:
+        raise ValueError(f"dense: a cost volume of {h0} x {w0} x {D} entries exceeds 2^32; raise downscale or max_step_px")
+
+
+def cost_volume(ref, src, A, B, w_first, w_step, D, radius=3, min_var=4, engine=None) -> torch.Tensor:
+    """`im_dense_costs` on two grey device images: the sweep's scores as costs, uint8 [h0, w0, D] on the device (255: the plane did not score)."""
     h0, w0 = ref.shape
     h1, w1 = src.shape
     _check_sweep(h0, w0, h1, w1, D, radius, min_var)
+    _check_volume(h0, w0, D)
+    eng = default_engine(engine)
+    dev = eng.device
+    ref, src = ref.to(dev).contiguous(), src.to(dev).contiguous()
+    A, B = np.ascontiguousarray(A, np.float64).reshape(9), np.ascontiguousarray(B, np.float64).reshape(9)
+    cost = torch.empty((h0, w0, int(D)), dtype=torch.uint8, device=dev)
+    eng.ctx.call("im_dense_costs", ptr(ref), h0, w0, ptr(src), h1, w1, A.ctypes.data, B.ctypes.data, float(w_first), float(w_step), int(D), int(radius),
+                 int(min_var), ptr(cost), eng.stream_ptr())
+    return cost
+
+
+def _volume(cost, what):
+    if not torch.is_tensor(cost) or cost.dtype != torch.uint8 or cost.ndim != 3:
+        raise ValueError(f"{what}: a uint8 [h, w, D] cost volume is expected")
+    _check_volume(*cost.shape)
+
+
+def sgm_aggregate(cost, P1: int = 16, P2: int = 128, paths: int = 8, engine=None) -> torch.Tensor:
+    """`im_dense_sgm`: the path costs of a cost volume summed over 4 or 8 directions, uint16 [h0, w0, D] on the device."""
+    _volume(cost, "sgm_aggregate")
+    _check_regularisation("sgm", P1, P2, paths)
+    eng = default_engine(engine)
+    cost = cost.to(eng.device).contiguous()
+    h0, w0, D = cost.shape
+    total = torch.empty((h0, w0, D), dtype=torch.uint16, device=eng.device)
+    eng.ctx.call("im_dense_sgm", ptr(cost), h0, w0, D, int(P1), int(P2), int(paths), ptr(total), eng.stream_ptr())
+    return total
+
+
+def sgm_choose(cost, total, w_first, w_step, min_score=0.8, engine=None):
+    """`im_dense_sgm_choose`: (plane, w, score) device tensors as `sweep` gives them, out of a cost volume and its summed path costs."""
+    _volume(cost, "sgm_choose")
+    if not torch.is_tensor(total) or total.dtype != torch.uint16 or total.shape != cost.shape:
+        raise ValueError("sgm_choose: the sums are a uint16 tensor of the cost volume's shape")
+    eng = default_engine(engine)
+    dev = eng.device
+    cost, total = cost.to(dev).contiguous(), total.to(dev).contiguous()
+    h0, w0, D = cost.shape
+    plane = torch.empty((h0, w0), dtype=torch.int16, device=dev)
+    w = torch.empty((h0, w0), dtype=torch.float64, device=dev)
+    score = torch.empty((h0, w0), dtype=torch.float32, device=dev)
+    eng.ctx.call("im_dense_sgm_choose", ptr(cost), ptr(total), h0, w0, D, float(w_first), float(w_step), float(min_score), ptr(plane), ptr(w), ptr(score),
+                 eng.stream_ptr())
+    return plane, w, score
+
+
+def sweep(ref, src, A, B, w_first, w_step, D, radius=3, min_var=4, min_score=0.8, engine=None, regularisation=None, p1=16, p2=128, paths=8):
+    """`im_dense_sweep` on two grey device images: (plane, w, score) device tensors of ref's shape. `regularisation="sgm"` takes the cost
+    volume, its semi-global aggregation with the penalties `p1 <= p2` over `paths` directions, and the choice instead; the volumes are
+    freed once the maps are chosen."""
+    h0, w0 = ref.shape
+    h1, w1 = src.shape
+    _check_sweep(h0, w0, h1, w1, D, radius, min_var)
+    _check_regularisation(regularisation, p1, p2, paths)
+    if regularisation == "sgm":
+        _check_volume(h0, w0, D)
+        eng = default_engine(engine)
+        cost = cost_volume(ref, src, A, B, w_first, w_step, D, radius, min_var, engine=eng)
+        total = sgm_aggregate(cost, p1, p2, paths, engine=eng)
+        maps = sgm_choose(cost, total, w_first, w_step, min_score, engine=eng)
+        del cost, total
+        return maps
     eng = default_engine(engine)
     dev = eng.device
     ref, src = ref.to(dev).contiguous(), src.to(dev).contiguous()
@@ -264,14 +352,17 @@ def _prepare(image, cam, downscale, eng):
 
 
 def build_depth_maps(images, cameras, depth_range=None, sparse_points=None, downscale: int = 1, radius: int = 3, min_score: float = 0.8,
-                     min_var: int = 4, max_step_px: float = 1.0, engine=None):
+                     min_var: int = 4, max_step_px: float = 1.0, engine=None, regularisation=None, p1: int = 16, p2: int = 128, paths: int = 8):
     """The depth maps of both views of a stereo pair, `chunk.buildDepthMaps` of the reference with a definition of this project's own
     (module docstring): [DepthMap of view 0, DepthMap of view 1], on the device. `depth_range` = (d_min, d_max) in view 0 (and, through the
     same points, view 1) or None: then `sparse_points` [n, 3] give it per view (`depth_range_from_points`). Images with a non-zero
-    `dist` are undistorted first (`sfm.undistort_image`)."""
+    `dist` are undistorted first (`sfm.undistort_image`). `regularisation` = None: each pixel takes its best plane by itself;
+    "sgm": semi-global aggregation of the costs with the penalties `p1 <= p2` over `paths` (4 or 8) directions decides (`sweep`), which
+    holds at most 256 planes per view."""
     if len(images) != 2 or len(cameras) != 2:
         raise ValueError("build_depth_maps: a stereo pair has two images and two cameras")
     downscale = _factor(downscale)
+    _check_regularisation(regularisation, p1, p2, paths)
     if depth_range is None and sparse_points is None:
         raise ValueError("build_depth_maps: a depth_range or sparse_points to take it from are needed")
     # everything that can be refused is refused before the first launch
@@ -283,27 +374,34 @@ def build_depth_maps(images, cameras, depth_range=None, sparse_points=None, down
     plans = []
     for v in range(2):
         schedule = plane_schedule(small[v], small[1 - v], ranges[v][0], ranges[v][1], max_step_px, shape=small_shapes[v])
+        if regularisation == "sgm":
+            _check_volume(*small_shapes[v], schedule[2])
         plans.append((schedule, sweep_matrices(small[v].K, small[1 - v].K, *relative_pose(small[v], small[1 - v]))))
+    chosen = {} if regularisation is None else dict(regularisation=regularisation, p1=p1, p2=p2, paths=paths)
     eng = default_engine(engine)
     prepared = [_prepare(im, c, downscale, eng) for im, c in zip(images, cameras)]
     maps = []
     for v in range(2):
         (w_first, w_step, D), (A, B) = plans[v]
-        plane, w, score = sweep(prepared[v][1], prepared[1 - v][1], A, B, w_first, w_step, D, radius, min_var, min_score, engine=eng)
+        plane, w, score = sweep(prepared[v][1], prepared[1 - v][1], A, B, w_first, w_step, D, radius, min_var, min_score, engine=eng, **chosen)
         maps.append(DepthMap(plane, w, score, prepared[v][0], prepared[v][1], small[v].K, small[v].R, small[v].t, (w_first, w_step, D)))
     return maps
 
 
 def build_dense_cloud(images, cameras, sparse_points=None, depth_filter: str = "ModerateFiltering", downscale: int = 1, views=(0,), save_path=None,
-                      depth_range=None, radius: int = 3, min_score: float = 0.8, min_var: int = 4, max_step_px: float = 1.0, engine=None) -> PointCloud:
+                      depth_range=None, radius: int = 3, min_score: float = 0.8, min_var: int = 4, max_step_px: float = 1.0, engine=None,
+                      regularisation=None, p1: int = 16, p2: int = 128, paths: int = 8) -> PointCloud:
     """`MetashapeProject.build_dense_cloud` of the reference with a definition of this project's own: the depth maps of the pair, their
     consistency under `depth_filter`, and the cloud of the kept pixels of `views` (view 0's points first) as a `core.PointCloud` with
-    colours, normals turned towards the camera and `confidence` (the score, float32). `save_path` writes it as PLY (`dense_{date}.ply`)."""
+    colours, normals turned towards the camera and `confidence` (the score, float32). `save_path` writes it as PLY (`dense_{date}.ply`).
+    `regularisation`, `p1`, `p2`, `paths`: as `build_depth_maps` takes them."""
     filter_tolerance(depth_filter)
+    _check_regularisation(regularisation, p1, p2, paths)
     views = tuple(views)
     if not views or any(v not in (0, 1) for v in views):
         raise ValueError(f"build_dense_cloud: views are 0 and / or 1 (got {views})")
-    maps = build_depth_maps(images, cameras, depth_range, sparse_points, downscale, radius, min_score, min_var, max_step_px, engine=engine)
+    chosen = {} if regularisation is None else dict(regularisation=regularisation, p1=p1, p2=p2, paths=paths)
+    maps = build_depth_maps(images, cameras, depth_range, sparse_points, downscale, radius, min_score, min_var, max_step_px, engine=engine, **chosen)
     eng = default_engine(engine)
     parts = []
     for v in views:

@@ -613,6 +613,30 @@ int im_dense_cloud(im_ctx* ctx, const uint8_t* d_keep, const double* d_w, const 
                    const double* h_cam, long long capacity, double* d_xyz, uint8_t* d_rgb, double* d_nrm, float* d_conf, long long* d_count,
                    void* stream);
 
+/* ---- semi-global regularisation of a depth map (csrc/dense_sgm.hip, csrc/sgm_pixel.h): the smoothness term the winner-take-all sweep
+ * above lacks, where the driver asks Metashape for filtered depth maps (`metashape.py:198-240`). A definition of this project's own
+ * (DESIGN §4), restated in tests/sgm_oracle.py: bit-identical; it is NOT Metashape's filter. All arrays in DEVICE memory unless named h_.
+ * im_dense_costs: the sweep's (valid, s) of every ref pixel and plane (same arguments, same arithmetic as im_dense_sweep), quantised:
+ * d_cost [h0][w0][D] uint8, planes contiguous, = 255 where the plane did not score, else min(254, max(0, floor((1 - s) 127))).
+ * im_dense_sgm: d_sum [h0][w0][D] uint16 = the sum over `paths` (4 or 8) directions (dy, dx) = (0,1) (0,-1) (1,0) (-1,0), then (1,1)
+ * (-1,-1) (1,-1) (-1,1), of L(p, d) = c(p, d) where q = p - (dy, dx) lies outside the image, else
+ * c(p, d) + min(L(q, d), L(q, d - 1) + P1, L(q, d + 1) + P1, m + P2) - m with m = min_k L(q, k); terms with d - 1 < 0 or d + 1 >= D are
+ * absent; an invalid cost enters as the plain value 255. 0 <= P1 <= P2 <= 4095, so L <= 4350 and the sum <= 34800. One wave per path
+ * line, four planes per lane: D <= im_dense_sgm_max_planes() = 256. Every element of d_sum is written; it need not be cleared.
+ * im_dense_sgm_choose: per pixel, among the planes with c != 255 the least sum (ties to the lower plane) k; the sub-plane offset
+ * 0.5 (S- - S+) / (S- - 2 S0 + S+) applies for 1 <= k <= D - 2 with both neighbours valid at the pixel and a positive integer denominator;
+ * d_w = w_first + (k + off) w_step; d_score = float(1 - c(p, k) / 127); d_plane = -1, w = score = 0 where no plane is valid or the
+ * score is below min_score. The three maps have the types and the meaning of im_dense_sweep's: im_dense_consistency and im_dense_cloud
+ * take them as they are.
+ * All three return -83, without launching and with the outputs untouched, for a null pointer, h or w outside 1..16384, D outside 1..256,
+ * r outside 1..7, min_var negative or above 2^26, P1 < 0, P1 > P2, P2 > 4095, paths other than 4 or 8, or h0 w0 D > 2^32. Enqueue only. */
+int im_dense_sgm_max_planes(void);
+int im_dense_costs(im_ctx* ctx, const uint8_t* d_ref, int h0, int w0, const uint8_t* d_src, int h1, int w1, const double* h_A, const double* h_B,
+                   double w_first, double w_step, int D, int r, long long min_var, uint8_t* d_cost, void* stream);
+int im_dense_sgm(im_ctx* ctx, const uint8_t* d_cost, int h0, int w0, int D, int P1, int P2, int paths, uint16_t* d_sum, void* stream);
+int im_dense_sgm_choose(im_ctx* ctx, const uint8_t* d_cost, const uint16_t* d_sum, int h0, int w0, int D, double w_first, double w_step,
+                        double min_score, int16_t* d_plane, double* d_w, float* d_score, void* stream);
+
 /* ---- volume variations (`scripts/pcd_postprocessing/volume_variations.py`; `post_processing/cloudcompare_fun.py`:
  * `DemOfDifference.compute_volume` over CloudCompare's `ComputeVolume25D`; `post_processing/open3d_fun.py`: `filter_pcd_by_polyline`);
  * csrc/dod.hip, csrc/dod_cell.h. The DEM of difference of P pairs (ground, ceil) over E clouds that lie one behind the other in d_pts
