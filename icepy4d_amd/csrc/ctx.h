@@ -131,6 +131,7 @@ struct im_ctx {
         im::Scratch icp;         // one partial of 32 sums per chunk of source points of an ICP iteration (icp.hip)
         im::Scratch ba;          // chunk partials of 448 sums, chunk cost partials and 95 doubles per point of a bundle-adjustment iteration (ba.hip)
         im::Scratch dense;       // block sums of the scan over the kept pixels of a dense cloud (dense.hip)
+        im::Scratch depth;       // per root slot: the pixel count of a component; the rim planes and the border flag of a hole (depth_clean.hip)
         im::Scratch clock[2];   // im_debug_clock_probe: per-block (cycles, 100 MHz ticks) of the attention / Winograd BX main loops
     } scratch;
     // hipSuccess: s holds at least `bytes`. A larger buffer is allocated (through dalloc: guards and `allocs` ownership as for every buffer; `name`

@@ -111,5 +111,15 @@ struct DenseCloudScratch : Carve {
     Piece<long long> sums;
     explicit DenseCloudScratch(long long n) : sums(take<long long>(blocks_of(n, SCAN_THREADS))) {}
 };
+// im_depth_components, n = h w > 0 pixels: cnt [n], the pixels of a component counted on its root's slot
+struct DepthComponentsScratch : Carve {
+    Piece<int> cnt;
+    explicit DepthComponentsScratch(long long n) : cnt(take<int>(n)) {}
+};
+// im_depth_fill_holes, n = h w > 0 pixels: lo [n], hi [n], the least and the greatest plane around a hole on its root's slot (hi with the border flag)
+struct DepthHolesScratch : Carve {
+    Piece<int> lo, hi;
+    explicit DepthHolesScratch(long long n) : lo(take<int>(n)), hi(take<int>(n)) {}
+};
 
 }  // namespace im

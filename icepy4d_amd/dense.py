@@ -9,6 +9,10 @@ score as confidence. Parity with Metashape is unpinned by construction. No host 
 `regularisation="sgm"` replaces the per-pixel choice of the sweep by a semi-global one (csrc/dense_sgm.hip, csrc/sgm_pixel.h, restated in
 tests/sgm_oracle.py): the scores as an 8-bit cost volume, min-plus path costs summed over four or eight directions, the plane of least
 sum. It is this project's own definition too, not Metashape's depth filter; the default None is the plain sweep.
+`speckle=(min_size, max_diff)` and `holes=(max_hole, max_diff)` clean each view's map behind the sweep (csrc/depth_clean.hip,
+csrc/depth_pixel.h, restated in tests/depth_oracle.py): connected components of the map labelled on the device, the small ones dropped,
+the small holes filled by interpolation. Again a definition of this project's own: neither OpenCV's `filterSpeckles` nor Metashape's
+filter; the default None makes no call.
 
 Cameras are objects with `.K .R .t` (X_cam = R X_world + t) and optionally `.dist`, as `core.Camera` and the cameras of a
 `sfm.BundleResult`. Images are uint8 [h, w] or [h, w, 3] (RGB) numpy arrays or device tensors."""
@@ -28,6 +32,7 @@ logger = logging.getLogger(__name__)
 
 MAX_SIDE, MAX_PLANES, MAX_RADIUS = 16384, 4096, 7
 MAX_SGM_PLANES, MAX_PENALTY, MAX_VOLUME = 256, 4095, 1 << 32
+MAX_PLANE_DIFF, MAX_HOLE, MAX_MIN_SIZE = 4095, 4096, (1 << 31) - 1
 REGULARISATIONS = (None, "sgm")
 DEPTH_FILTERS = {"NoFiltering": None, "MildFiltering": 2.0, "ModerateFiltering": 1.0, "AggressiveFiltering": 0.5}
 
@@ -301,6 +306,107 @@ def sweep(ref, src, A, B, w_first, w_step, D, radius=3, min_var=4, min_score=0.8
     return plane, w, score
 
 
+# ---- clean-up: components, speckles, holes -----------------------------------------------------------------------------------------------------
+def _check_count(what, name, v, hi):
+    if isinstance(v, bool) or int(v) != v or not 1 <= v <= hi:
+        raise ValueError(f"{what}: {name} must be an integer in 1..{hi} (got {v})")
+
+
+def _check_max_diff(what, max_diff):
+    if isinstance(max_diff, bool) or int(max_diff) != max_diff or not 0 <= max_diff <= MAX_PLANE_DIFF:
+        raise ValueError(f"{what}: max_diff must be an integer in 0..{MAX_PLANE_DIFF} (got {max_diff})")
+
+
+def _check_clean_up(speckle, holes):
+    """`speckle` = None | (min_size, max_diff) and `holes` = None | (max_hole, max_diff) of `build_depth_maps`, as pairs of ints."""
+    out = []
+    for name, value, first, hi in (("speckle", speckle, "min_size", MAX_MIN_SIZE), ("holes", holes, "max_hole", MAX_HOLE)):
+        if value is None:
+            out.append(None)
+            continue
+        try:
+            a, b = value
+        except (TypeError, ValueError):
+            raise ValueError(f"dense: {name} is None or ({first}, max_diff) (got {value!r})") from None
+        _check_count(f"dense: {name}", first, a, hi)
+        _check_max_diff(f"dense: {name}", b)
+        out.append((int(a), int(b)))
+    return out
+
+
+def _check_plane_map(plane, what):
+    if not torch.is_tensor(plane) or plane.dtype != torch.int16 or plane.ndim != 2:
+        raise ValueError(f"{what}: an int16 [h, w] plane map is expected")
+    for v in plane.shape:
+        if not 1 <= v <= MAX_SIDE:
+            raise ValueError(f"{what}: image sides must be 1..{MAX_SIDE} (got {v})")
+
+
+def _check_fill_schedule(schedule, what):
+    w_first, w_step, D = schedule
+    if not (np.isfinite(w_first) and np.isfinite(w_step)) or w_step == 0.0:
+        raise ValueError(f"{what}: w_first must be finite and w_step finite and not zero (got {w_first}, {w_step}); a one-plane schedule has no step to round to")
+    if int(D) != D or not 1 <= D <= MAX_PLANES:
+        raise ValueError(f"{what}: the number of planes must be 1..{MAX_PLANES} (got {D})")
+
+
+def depth_components(plane, max_diff: int = 1, holes: bool = False, engine=None):
+    """`im_depth_components` on a plane map [h, w] int16: (label, size) int32 device tensors. Pixels are neighbours across an edge.
+    `holes=False`: the members hold a plane (>= 0) and are joined when their planes differ by at most `max_diff`; `holes=True`: the members
+    hold none and are all joined. label = the least linear index of the pixel's component (-1: no member), size = its pixel count (0)."""
+    _check_plane_map(plane, "depth_components")
+    _check_max_diff("depth_components", max_diff)
+    eng = default_engine(engine)
+    plane = plane.to(eng.device).contiguous()
+    h, w = plane.shape
+    label = torch.empty((h, w), dtype=torch.int32, device=eng.device)
+    size = torch.empty((h, w), dtype=torch.int32, device=eng.device)
+    eng.ctx.call("im_depth_components", ptr(plane), h, w, 1 if holes else 0, int(max_diff), ptr(label), ptr(size), eng.stream_ptr())
+    return label, size
+
+
+def remove_speckles(m: DepthMap, min_size: int = 16, max_diff: int = 1, engine=None, return_counts: bool = False):
+    """The map without its speckles: pixels whose surface component (`depth_components`) has fewer than `min_size` pixels get plane -1,
+    w 0, score 0, as the sweep writes a dropped pixel. The three tensors are cloned; `m` is not modified. `return_counts`: also the
+    number of dropped pixels, an int64 [1] device tensor; nothing is read back."""
+    _check_plane_map(m.plane, "remove_speckles")
+    _check_count("remove_speckles", "min_size", min_size, MAX_MIN_SIZE)
+    _check_max_diff("remove_speckles", max_diff)
+    eng = default_engine(engine)
+    dev = eng.device
+    plane, w, score = m.plane.to(dev).clone().contiguous(), m.w.to(dev).clone().contiguous(), m.score.to(dev).clone().contiguous()
+    h, wd = plane.shape
+    _, size = depth_components(plane, max_diff, engine=eng)
+    count = torch.empty(1, dtype=torch.int64, device=dev)
+    eng.ctx.call("im_depth_drop_small", ptr(size), h, wd, int(min_size), ptr(plane), ptr(w), ptr(score), ptr(count), eng.stream_ptr())
+    out = m._replace(plane=plane, w=w, score=score)
+    return (out, count) if return_counts else out
+
+
+def fill_holes(m: DepthMap, max_hole: int = 64, max_diff: int = 2, engine=None, return_counts: bool = False):
+    """The map with its small holes filled: a hole (a component of pixels without a plane) of at most `max_hole` pixels that does not
+    touch the image border and whose rim spreads over at most `max_diff` planes takes, per pixel, the mean of the linear interpolations
+    between its nearest plane-holding pixels along its row and along its column; the plane is the nearest of the schedule, the score 0.
+    New tensors; `m` is not modified. `return_counts`: also the number of filled pixels, an int64 [1] device tensor."""
+    _check_plane_map(m.plane, "fill_holes")
+    _check_count("fill_holes", "max_hole", max_hole, MAX_HOLE)
+    _check_max_diff("fill_holes", max_diff)
+    _check_fill_schedule(m.schedule, "fill_holes")
+    eng = default_engine(engine)
+    dev = eng.device
+    plane, w, score = m.plane.to(dev).contiguous(), m.w.to(dev).contiguous(), m.score.to(dev).contiguous()
+    h, wd = plane.shape
+    label, size = depth_components(plane, 0, holes=True, engine=eng)
+    plane_out, w_out, score_out = torch.empty_like(plane), torch.empty_like(w), torch.empty_like(score)
+    filled = torch.empty((h, wd), dtype=torch.uint8, device=dev)
+    count = torch.empty(1, dtype=torch.int64, device=dev)
+    w_first, w_step, D = m.schedule
+    eng.ctx.call("im_depth_fill_holes", ptr(plane), ptr(w), ptr(score), ptr(label), ptr(size), h, wd, int(max_hole), int(max_diff), float(w_first),
+                 float(w_step), int(D), ptr(plane_out), ptr(w_out), ptr(score_out), ptr(filled), ptr(count), eng.stream_ptr())
+    out = m._replace(plane=plane_out, w=w_out, score=score_out)
+    return (out, count) if return_counts else out
+
+
 def consistency(map0: DepthMap, map1: DepthMap, depth_filter: str = "ModerateFiltering", engine=None) -> torch.Tensor:
     """`im_dense_consistency`: keep [h, w] uint8 on the device for the pixels of `map0` against `map1`."""
     tau = filter_tolerance(depth_filter)
@@ -352,17 +458,20 @@ def _prepare(image, cam, downscale, eng):
 
 
 def build_depth_maps(images, cameras, depth_range=None, sparse_points=None, downscale: int = 1, radius: int = 3, min_score: float = 0.8,
-                     min_var: int = 4, max_step_px: float = 1.0, engine=None, regularisation=None, p1: int = 16, p2: int = 128, paths: int = 8):
+                     min_var: int = 4, max_step_px: float = 1.0, engine=None, regularisation=None, p1: int = 16, p2: int = 128, paths: int = 8,
+                     speckle=None, holes=None):
     """The depth maps of both views of a stereo pair, `chunk.buildDepthMaps` of the reference with a definition of this project's own
     (module docstring): [DepthMap of view 0, DepthMap of view 1], on the device. `depth_range` = (d_min, d_max) in view 0 (and, through the
     same points, view 1) or None: then `sparse_points` [n, 3] give it per view (`depth_range_from_points`). Images with a non-zero
     `dist` are undistorted first (`sfm.undistort_image`). `regularisation` = None: each pixel takes its best plane by itself;
     "sgm": semi-global aggregation of the costs with the penalties `p1 <= p2` over `paths` (4 or 8) directions decides (`sweep`), which
-    holds at most 256 planes per view."""
+    holds at most 256 planes per view. `speckle` = (min_size, max_diff) drops the small components of each view's map (`remove_speckles`),
+    `holes` = (max_hole, max_diff) then fills its small holes (`fill_holes`): after the sweep, under either regularisation. None: neither."""
     if len(images) != 2 or len(cameras) != 2:
         raise ValueError("build_depth_maps: a stereo pair has two images and two cameras")
     downscale = _factor(downscale)
     _check_regularisation(regularisation, p1, p2, paths)
+    speckle, holes = _check_clean_up(speckle, holes)
     if depth_range is None and sparse_points is None:
         raise ValueError("build_depth_maps: a depth_range or sparse_points to take it from are needed")
     # everything that can be refused is refused before the first launch
@@ -376,6 +485,8 @@ def build_depth_maps(images, cameras, depth_range=None, sparse_points=None, down
         schedule = plane_schedule(small[v], small[1 - v], ranges[v][0], ranges[v][1], max_step_px, shape=small_shapes[v])
         if regularisation == "sgm":
             _check_volume(*small_shapes[v], schedule[2])
+        if holes is not None:
+            _check_fill_schedule(schedule, "dense: holes")
         plans.append((schedule, sweep_matrices(small[v].K, small[1 - v].K, *relative_pose(small[v], small[1 - v]))))
     chosen = {} if regularisation is None else dict(regularisation=regularisation, p1=p1, p2=p2, paths=paths)
     eng = default_engine(engine)
@@ -384,23 +495,34 @@ def build_depth_maps(images, cameras, depth_range=None, sparse_points=None, down
     for v in range(2):
         (w_first, w_step, D), (A, B) = plans[v]
         plane, w, score = sweep(prepared[v][1], prepared[1 - v][1], A, B, w_first, w_step, D, radius, min_var, min_score, engine=eng, **chosen)
-        maps.append(DepthMap(plane, w, score, prepared[v][0], prepared[v][1], small[v].K, small[v].R, small[v].t, (w_first, w_step, D)))
+        m = DepthMap(plane, w, score, prepared[v][0], prepared[v][1], small[v].K, small[v].R, small[v].t, (w_first, w_step, D))
+        if speckle is not None:
+            m = remove_speckles(m, *speckle, engine=eng)
+        if holes is not None:
+            m = fill_holes(m, *holes, engine=eng)
+        maps.append(m)
     return maps
 
 
 def build_dense_cloud(images, cameras, sparse_points=None, depth_filter: str = "ModerateFiltering", downscale: int = 1, views=(0,), save_path=None,
                       depth_range=None, radius: int = 3, min_score: float = 0.8, min_var: int = 4, max_step_px: float = 1.0, engine=None,
-                      regularisation=None, p1: int = 16, p2: int = 128, paths: int = 8) -> PointCloud:
+                      regularisation=None, p1: int = 16, p2: int = 128, paths: int = 8, speckle=None, holes=None) -> PointCloud:
     """`MetashapeProject.build_dense_cloud` of the reference with a definition of this project's own: the depth maps of the pair, their
     consistency under `depth_filter`, and the cloud of the kept pixels of `views` (view 0's points first) as a `core.PointCloud` with
     colours, normals turned towards the camera and `confidence` (the score, float32). `save_path` writes it as PLY (`dense_{date}.ply`).
-    `regularisation`, `p1`, `p2`, `paths`: as `build_depth_maps` takes them."""
+    `regularisation`, `p1`, `p2`, `paths`, `speckle`, `holes`: as `build_depth_maps` takes them; the clean-up comes before the
+    consistency check, and a filled pixel enters the cloud with confidence 0."""
     filter_tolerance(depth_filter)
     _check_regularisation(regularisation, p1, p2, paths)
+    _check_clean_up(speckle, holes)
     views = tuple(views)
     if not views or any(v not in (0, 1) for v in views):
         raise ValueError(f"build_dense_cloud: views are 0 and / or 1 (got {views})")
     chosen = {} if regularisation is None else dict(regularisation=regularisation, p1=p1, p2=p2, paths=paths)
+    if speckle is not None:
+        chosen["speckle"] = speckle
+    if holes is not None:
+        chosen["holes"] = holes
     maps = build_depth_maps(images, cameras, depth_range, sparse_points, downscale, radius, min_score, min_var, max_step_px, engine=engine, **chosen)
     eng = default_engine(engine)
     parts = []

@@ -637,6 +637,39 @@ int im_dense_sgm(im_ctx* ctx, const uint8_t* d_cost, int h0, int w0, int D, int 
 int im_dense_sgm_choose(im_ctx* ctx, const uint8_t* d_cost, const uint16_t* d_sum, int h0, int w0, int D, double w_first, double w_step,
                         double min_score, int16_t* d_plane, double* d_w, float* d_score, void* stream);
 
+/* ---- depth-map clean-up: connected components, speckle removal and hole filling (csrc/depth_clean.hip, csrc/depth_pixel.h), where the
+ * driver asks Metashape for filtered depth maps (`metashape.py:198-240`). A definition of this project's own, restated in
+ * tests/depth_oracle.py: bit-identical; it is NOT OpenCV's filterSpeckles and NOT Metashape's filter. All arrays in DEVICE memory.
+ * Pixels are neighbours when they share an edge (4-connectivity). d_plane [h][w] int16 is the sweep's map; a pixel holds a plane when
+ * plane >= 0. mode 0 (surfaces): the members are the pixels that hold a plane, two neighbouring members are joined when
+ * |plane_p - plane_q| <= max_diff (integers). mode 1 (holes): the members hold no plane, any two neighbouring members are joined.
+ * im_depth_components: the connected components of the join graph (joining is transitive: 3-4-5 is one component at max_diff = 1).
+ * d_label [h][w] int32 = the least linear index y w + x of the pixel's component, -1 for a non-member; d_size [h][w] int32 = the number of
+ * pixels of that component, 0 for a non-member. A union-find over d_label in four launches (tiles of im_depth_tile_w() x im_depth_tile_h()
+ * pixels in LDS, the joins across tile edges, the roots and their counts, the sizes); the tile is no part of the definition.
+ * im_depth_drop_small: in place on the three maps; d_size is the mode-0 size of d_plane. A pixel that holds a plane and whose component
+ * has size < min_size gets plane = -1, w = 0, score = 0 (what the sweep writes for a dropped pixel); every other pixel is untouched.
+ * *d_count (int64) = the number of pixels dropped. min_size = 1 drops nothing.
+ * im_depth_fill_holes: d_label and d_size are the mode-1 results for the same d_plane. A hole qualifies when none of its pixels lies in
+ * the first or last row or column, its size is at most max_hole, and hi - lo <= max_diff with lo / hi the least / greatest plane over the
+ * plane-holding pixels that neighbour any of its pixels. A pixel (x, y) of a qualifying hole has the nearest plane-holding pixels xl < x < xr
+ * in its row and yu < y < yd in its column; in float64, exactly these operations in this order, no contraction:
+ *   a = w[y][xl] + (w[y][xr] - w[y][xl]) * (double(x - xl) / double(xr - xl)),  b = w[yu][x] + (w[yd][x] - w[yu][x]) * (double(y - yu) / double(yd - yu)),
+ *   w_out = 0.5 * (a + b),  plane_out = min(D - 1, max(0, rint((w_out - w_first) / w_step))) (ties to even),  score_out = 0 (a filled pixel).
+ * Every other pixel is copied through. d_filled [h][w] uint8 = 1 on the filled pixels, 0 elsewhere; *d_count (int64) = their number. The
+ * outputs are arrays of their own: a filled pixel must never be read as a rim pixel by another thread.
+ * All three return -83, without launching and with the outputs untouched, for a null pointer, h or w outside 1..16384, mode other than 0
+ * or 1, max_diff outside 0..4095, min_size < 1, max_hole outside 1..4096, D outside 1..4096, w_first not finite, w_step not finite or
+ * zero, or (im_depth_fill_holes) an output map that is its input. Enqueue only. */
+int im_depth_tile_w(void);
+int im_depth_tile_h(void);
+int im_depth_components(im_ctx* ctx, const int16_t* d_plane, int h, int w, int mode, int max_diff, int* d_label, int* d_size, void* stream);
+int im_depth_drop_small(im_ctx* ctx, const int* d_size, int h, int w, int min_size, int16_t* d_plane, double* d_w, float* d_score, long long* d_count,
+                        void* stream);
+int im_depth_fill_holes(im_ctx* ctx, const int16_t* d_plane, const double* d_w, const float* d_score, const int* d_label, const int* d_size, int h, int w,
+                        int max_hole, int max_diff, double w_first, double w_step, int D, int16_t* d_plane_out, double* d_w_out, float* d_score_out,
+                        uint8_t* d_filled, long long* d_count, void* stream);
+
 /* ---- volume variations (`scripts/pcd_postprocessing/volume_variations.py`; `post_processing/cloudcompare_fun.py`:
  * `DemOfDifference.compute_volume` over CloudCompare's `ComputeVolume25D`; `post_processing/open3d_fun.py`: `filter_pcd_by_polyline`);
  * csrc/dod.hip, csrc/dod_cell.h. The DEM of difference of P pairs (ground, ceil) over E clouds that lie one behind the other in d_pts
