@@ -4,7 +4,8 @@ parity of either with an Open3D binary is unpinned (see that module).
 
 PLY files are `binary_little_endian 1.0` with `double x y z`, then `uchar red green blue` when colours exist (round(c * 255) clipped to
 0..255), then `double nx ny nz` when normals exist: the layout Open3D documents for its default writer. Byte parity with a file written
-by Open3D is unpinned. The reader takes that layout and its float / ascii variants. `.las` needs laspy, which is not a dependency:
+by Open3D is unpinned. `write_ply(scalars=...)` adds `float confidence` and / or `uchar views` behind them on request; the reader skips
+properties it does not know, these two included. The reader takes that layout and its float / ascii variants. `.las` needs laspy, which is not a dependency:
 reading and writing it raise NotImplementedError."""
 import logging
 from pathlib import Path
@@ -18,12 +19,16 @@ _PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short":
               "int": "i4", "int32": "i4", "uint": "u4", "uint32": "u4", "float": "f4", "float32": "f4", "double": "f8", "float64": "f8"}
 
 
-def ply_header(n: int, colors: bool, normals: bool) -> bytes:
+PLY_SCALARS = {"confidence": ("float", "<f4"), "views": ("uchar", "u1")}      # per-point attributes `write_ply(scalars=...)` may name: PLY type, numpy type
+
+
+def ply_header(n: int, colors: bool, normals: bool, scalars=()) -> bytes:
     lines = ["ply", "format binary_little_endian 1.0", f"element vertex {n}", "property double x", "property double y", "property double z"]
     if colors:
         lines += ["property uchar red", "property uchar green", "property uchar blue"]
     if normals:
         lines += ["property double nx", "property double ny", "property double nz"]
+    lines += [f"property {t} {name}" for name, t in scalars]
     return ("\n".join(lines + ["end_header"]) + "\n").encode("ascii")
 
 
@@ -81,7 +86,8 @@ class PointCloud:
         self.points = np.zeros((0, 3), np.float64)
         self.colors = None
         self.normals = None
-        self.confidence = None            # [n] float32 where the producer has one (`dense.build_dense_cloud`); not written to PLY
+        self.confidence = None            # [n] float32 where the producer has one (`dense.build_dense_cloud`); written to PLY on request (`write_ply(scalars=...)`)
+        self.views = None                 # [n] uint8, the number of depth maps that agreed on the point (`dense.build_dense_cloud(fuse=...)`); likewise
         if isinstance(points3d, np.ndarray):
             self.from_numpy(points3d, points_col)
         elif pcd_path is not None:
@@ -136,6 +142,9 @@ class PointCloud:
             self.colors = self.colors[ind]
         if self.normals is not None:
             self.normals = self.normals[ind]
+        for name in PLY_SCALARS:                              # the per-point scalars stay aligned with the points
+            if getattr(self, name) is not None:
+                setattr(self, name, getattr(self, name)[ind])
         if self._verbose:
             logger.info("Point cloud filtered by Statistical Oulier Removal")
 
@@ -170,16 +179,40 @@ class PointCloud:
         out.normals = normals
         return out
 
-    def write_ply(self, path: Union[str, Path]) -> bool:
-        """Write point cloud to disk as .ply format (module docstring)."""
-        Path(path).parent.mkdir(parents=True, exist_ok=True)
+    @staticmethod
+    def check_scalars(scalars) -> tuple:
+        """The names of `write_ply(scalars=...)` as a tuple; a name that is none of `PLY_SCALARS`, or one named twice, raises ValueError."""
+        if isinstance(scalars, str):
+            scalars = (scalars,)
+        scalars = tuple(scalars)
+        for s in scalars:
+            if s not in PLY_SCALARS:
+                raise ValueError(f"PointCloud: unknown per-point scalar {s!r}; the PLY writer knows {sorted(PLY_SCALARS)}")
+        if len(set(scalars)) != len(scalars):
+            raise ValueError(f"PointCloud: a per-point scalar is named twice in {scalars}")
+        return scalars
+
+    def write_ply(self, path: Union[str, Path], scalars=()) -> bool:
+        """Write point cloud to disk as .ply format (module docstring). `scalars` names per-point attributes to write behind the other
+        properties, in the order given: "confidence" (`float`) and / or "views" (`uchar`); the cloud must hold them, one per point."""
+        scalars = self.check_scalars(scalars)
         n = len(self)
+        extra = []
+        for s in scalars:
+            a = getattr(self, s)
+            if a is None or np.shape(a) != (n,):
+                raise ValueError(f"PointCloud.write_ply: this cloud holds no {s!r} per point")
+            extra.append((s, PLY_SCALARS[s][1], np.asarray(a)))
+        Path(path).parent.mkdir(parents=True, exist_ok=True)
         fields = [("x", "<f8"), ("y", "<f8"), ("z", "<f8")]
         if self.colors is not None:
             fields += [("red", "u1"), ("green", "u1"), ("blue", "u1")]
         if self.normals is not None:
             fields += [("nx", "<f8"), ("ny", "<f8"), ("nz", "<f8")]
+        fields += [(s, t) for s, t, _ in extra]
         rec = np.zeros(n, dtype=np.dtype(fields))
+        for s, _, a in extra:
+            rec[s] = a
         for j, a in enumerate("xyz"):
             rec[a] = self.points[:, j]
         if self.colors is not None:
@@ -190,7 +223,7 @@ class PointCloud:
             for j, a in enumerate(("nx", "ny", "nz")):
                 rec[a] = self.normals[:, j]
         with open(path, "wb") as f:
-            f.write(ply_header(n, self.colors is not None, self.normals is not None))
+            f.write(ply_header(n, self.colors is not None, self.normals is not None, [(s, PLY_SCALARS[s][0]) for s in scalars]))
             f.write(rec.tobytes())
         return True
 

@@ -13,6 +13,11 @@ sum. It is this project's own definition too, not Metashape's depth filter; the 
 csrc/depth_pixel.h, restated in tests/depth_oracle.py): connected components of the map labelled on the device, the small ones dropped,
 the small holes filled by interpolation. Again a definition of this project's own: neither OpenCV's `filterSpeckles` nor Metashape's
 filter; the default None makes no call.
+`fuse=(tol, min_views)` on `build_dense_cloud` fuses the two views' maps into one cloud (csrc/dense_fuse.hip, csrc/fuse_pixel.h, restated
+in tests/fuse_oracle.py): a kept pixel of the base view is linked to the kept pixel of the other view it falls on, a linked pixel gives one
+point placed by both measurements, the other view adds only what the base does not represent, and every point carries the number of
+views that agreed on it. Once more a definition of this project's own, not Metashape's merge of its depth maps: parity with Metashape
+is unpinned by construction; the default None makes no call and concatenates the views' clouds as before.
 
 Cameras are objects with `.K .R .t` (X_cam = R X_world + t) and optionally `.dist`, as `core.Camera` and the cameras of a
 `sfm.BundleResult`. Images are uint8 [h, w] or [h, w, 3] (RGB) numpy arrays or device tensors."""
@@ -425,6 +430,68 @@ def consistency(map0: DepthMap, map1: DepthMap, depth_filter: str = "ModerateFil
     return keep
 
 
+def _check_fuse(fuse):
+    """`fuse` = None | (tol, min_views) of `build_dense_cloud`, as (float, int)."""
+    if fuse is None:
+        return None
+    try:
+        tol, min_views = fuse
+    except (TypeError, ValueError):
+        raise ValueError(f"dense: fuse is None or (tol, min_views) (got {fuse!r})") from None
+    _check_fuse_tol("dense: fuse", tol)
+    if isinstance(min_views, bool) or min_views not in (1, 2):
+        raise ValueError(f"dense: fuse: min_views must be 1 or 2 (got {min_views!r})")
+    return float(tol), int(min_views)
+
+
+def _check_fuse_tol(what, tol):
+    if isinstance(tol, (bool, str)) or not isinstance(tol, (int, float, np.integer, np.floating)) or not tol >= 0.0:
+        raise ValueError(f"{what}: tol must be a number of plane steps >= 0 (got {tol!r})")
+
+
+def _pose_between(a: DepthMap, b: DepthMap) -> np.ndarray:
+    """h_pose [30] = inv(Ka), R, t, Kb with Xb = R Xa + t, as `consistency` builds it."""
+    R = b.R @ a.R.T
+    t = b.t - R @ a.t
+    return np.ascontiguousarray(np.concatenate([inv3(a.K).reshape(9), R.reshape(9), t, b.K.reshape(9)]))
+
+
+def fuse(map_a: DepthMap, keep_a: torch.Tensor, map_b: DepthMap, keep_b: torch.Tensor, tol: float = 1.0, engine=None):
+    """`im_dense_fuse_link` and `im_dense_fuse_rest` (csrc/dense_fuse.hip, csrc/fuse_pixel.h, restated in tests/fuse_oracle.py): the two maps of a
+    pair as one. A kept pixel of the base view `map_a` links to the kept pixel of `map_b` its point falls on when that pixel's inverse depth
+    agrees within `tol` plane steps of map_b's schedule; a linked pixel takes the mean of both measurements along its own ray, weighted by
+    the scores, and the greater score. Returns (the fused DepthMap of view a, views [ha, wa] uint8 = 2 linked / 1 kept only / 0 not kept,
+    link [ha, wa] int32 = the linear index of the target or -1, rest [hb, wb] uint8 = 1 on the kept pixels of view b that no pixel
+    claimed and that do not link into view a themselves: what view a does not represent), all on the device. The plane of a fused pixel
+    is left as it was. A definition of this project's own, not Metashape's merge; parity with Metashape is unpinned by construction."""
+    _check_fuse_tol("fuse", tol)
+    (ha, wa), (hb, wb) = map_a.plane.shape, map_b.plane.shape
+    for v in (ha, wa, hb, wb):
+        if not 1 <= v <= MAX_SIDE:
+            raise ValueError(f"fuse: image sides must be 1..{MAX_SIDE} (got {v})")
+    for keep, shape in ((keep_a, (ha, wa)), (keep_b, (hb, wb))):
+        if not torch.is_tensor(keep) or keep.dtype != torch.uint8 or tuple(keep.shape) != shape:
+            raise ValueError("fuse: a keep mask is a uint8 tensor of its map's shape")
+    eng = default_engine(engine)
+    dev = eng.device
+    w_a, s_a, k_a = map_a.w.to(dev).contiguous(), map_a.score.to(dev).contiguous(), keep_a.to(dev).contiguous()
+    w_b, s_b, k_b = map_b.w.to(dev).contiguous(), map_b.score.to(dev).contiguous(), keep_b.to(dev).contiguous()
+    link = torch.empty((ha, wa), dtype=torch.int32, device=dev)
+    w_out, score_out = torch.empty_like(w_a), torch.empty_like(s_a)
+    views = torch.empty((ha, wa), dtype=torch.uint8, device=dev)
+    claimed = torch.empty((hb, wb), dtype=torch.uint8, device=dev)
+    rest = torch.empty((hb, wb), dtype=torch.uint8, device=dev)
+    ab, ba = _pose_between(map_a, map_b), _pose_between(map_b, map_a)
+    eng.ctx.call("im_dense_fuse_link", ptr(k_a), ptr(w_a), ptr(s_a), ha, wa, ptr(k_b), ptr(w_b), ptr(s_b), hb, wb, ab.ctypes.data,
+                 float(tol * abs(map_b.schedule[1])), ptr(link), ptr(w_out), ptr(score_out), ptr(views), ptr(claimed), eng.stream_ptr())
+    eng.ctx.call("im_dense_fuse_rest", ptr(k_b), ptr(w_b), hb, wb, ptr(k_a), ptr(w_a), ha, wa, ba.ctypes.data, float(tol * abs(map_a.schedule[1])),
+                 ptr(claimed), ptr(rest), eng.stream_ptr())
+    return map_a._replace(w=w_out, score=score_out), views, link, rest
+
+
+_fuse_maps = fuse            # `build_dense_cloud` has a parameter of the same name
+
+
 def cloud_of(m: DepthMap, keep: torch.Tensor, engine=None):
     """`im_dense_cloud`: (points [n, 3] float64, rgb [n, 3] uint8, normals [n, 3] float64, confidence [n] float32) device tensors of the kept
     pixels of one map in row-major order. One count is read back."""
@@ -506,18 +573,31 @@ def build_depth_maps(images, cameras, depth_range=None, sparse_points=None, down
 
 def build_dense_cloud(images, cameras, sparse_points=None, depth_filter: str = "ModerateFiltering", downscale: int = 1, views=(0,), save_path=None,
                       depth_range=None, radius: int = 3, min_score: float = 0.8, min_var: int = 4, max_step_px: float = 1.0, engine=None,
-                      regularisation=None, p1: int = 16, p2: int = 128, paths: int = 8, speckle=None, holes=None) -> PointCloud:
+                      regularisation=None, p1: int = 16, p2: int = 128, paths: int = 8, speckle=None, holes=None, fuse=None,
+                      ply_scalars=()) -> PointCloud:
     """`MetashapeProject.build_dense_cloud` of the reference with a definition of this project's own: the depth maps of the pair, their
     consistency under `depth_filter`, and the cloud of the kept pixels of `views` (view 0's points first) as a `core.PointCloud` with
-    colours, normals turned towards the camera and `confidence` (the score, float32). `save_path` writes it as PLY (`dense_{date}.ply`).
+    colours, normals turned towards the camera and `confidence` (the score, float32). `save_path` writes it as PLY (`dense_{date}.ply`),
+    with the per-point scalars named in `ply_scalars` ("confidence", "views") behind the other properties.
     `regularisation`, `p1`, `p2`, `paths`, `speckle`, `holes`: as `build_depth_maps` takes them; the clean-up comes before the
-    consistency check, and a filled pixel enters the cloud with confidence 0."""
+    consistency check, and a filled pixel enters the cloud with confidence 0.
+    `fuse` = None: the clouds of `views` one behind the other, a surface that both views see twice. `fuse` = (tol, min_views) fuses the two
+    maps instead (the module-level `fuse`; `views` must name both views, the first is the base): `depth_filter` still decides both keep
+    masks first, then the base view gives one point per kept pixel with at least `min_views` (1 or 2) views, from the fused map, and with
+    min_views = 1 the pixels of the other view that the base does not represent follow. The cloud's `views` (uint8, 2 or 1) says how many
+    depth maps agreed on a point, as Metashape's point confidence counts them; the rule is this project's own, not Metashape's."""
     filter_tolerance(depth_filter)
     _check_regularisation(regularisation, p1, p2, paths)
     _check_clean_up(speckle, holes)
+    fuse = _check_fuse(fuse)
+    ply_scalars = PointCloud.check_scalars(ply_scalars)
     views = tuple(views)
     if not views or any(v not in (0, 1) for v in views):
         raise ValueError(f"build_dense_cloud: views are 0 and / or 1 (got {views})")
+    if fuse is not None and views not in ((0, 1), (1, 0)):
+        raise ValueError(f"build_dense_cloud: fuse needs both views, the base first: views=(0, 1) or (1, 0) (got {views})")
+    if fuse is None and "views" in ply_scalars:
+        raise ValueError("build_dense_cloud: ply_scalars names 'views', which only a fused cloud has (fuse=(tol, min_views))")
     chosen = {} if regularisation is None else dict(regularisation=regularisation, p1=p1, p2=p2, paths=paths)
     if speckle is not None:
         chosen["speckle"] = speckle
@@ -525,23 +605,44 @@ def build_dense_cloud(images, cameras, sparse_points=None, depth_filter: str = "
         chosen["holes"] = holes
     maps = build_depth_maps(images, cameras, depth_range, sparse_points, downscale, radius, min_score, min_var, max_step_px, engine=engine, **chosen)
     eng = default_engine(engine)
-    parts = []
-    for v in views:
-        keep = consistency(maps[v], maps[1 - v], depth_filter, engine=eng)
-        parts.append(cloud_of(maps[v], keep, engine=eng))
+    parts, seen = [], None
+    if fuse is None:
+        for v in views:
+            keep = consistency(maps[v], maps[1 - v], depth_filter, engine=eng)
+            parts.append(cloud_of(maps[v], keep, engine=eng))
+    else:
+        (tol, min_views), (a, b) = fuse, views
+        keep_a = consistency(maps[a], maps[b], depth_filter, engine=eng)
+        keep_b = consistency(maps[b], maps[a], depth_filter, engine=eng)
+        fused, count, _, rest = _fuse_maps(maps[a], keep_a, maps[b], keep_b, tol, engine=eng)
+        mask = (count >= min_views).to(torch.uint8)
+        parts.append(cloud_of(fused, mask, engine=eng))
+        seen = [count[mask != 0]]                             # row-major, the order of the scan
+        if min_views == 1:
+            parts.append(cloud_of(maps[b], rest, engine=eng))
+            seen.append(torch.ones(len(parts[1][0]), dtype=torch.uint8, device=eng.device))
     xyz, rgb, nrm, conf = (torch.cat([p[i] for p in parts]).cpu().numpy() for i in range(4))
     pcd = PointCloud(points3d=xyz, points_col=rgb.astype(np.float64) / 255.0)
     pcd.normals = nrm
     pcd.confidence = conf
+    if seen is not None:
+        pcd.views = torch.cat(seen).cpu().numpy()
     if save_path is not None:
-        pcd.write_ply(Path(save_path))
+        if ply_scalars:
+            pcd.write_ply(Path(save_path), scalars=ply_scalars)
+        else:
+            pcd.write_ply(Path(save_path))
     return pcd
 
 
-def dense_series(images, cameras, sparse_points=None, out_dir=None, dates=None, **options) -> list:
+def dense_series(images, cameras, sparse_points=None, out_dir=None, dates=None, fuse=None, **options) -> list:
     """`build_dense_cloud` for every epoch of a sequence: `images` a list of E pairs, `cameras` one pair, a list of E pairs or a list of E
     `sfm.BundleResult` (as `bundle_adjust_epochs` returns them: their cameras and, unless `sparse_points` is given, their points are
-    taken), `sparse_points` None, one array or a list of E. With `out_dir`, epoch e is written to `dense_{dates[e]}.ply` (default e)."""
+    taken), `sparse_points` None, one array or a list of E. With `out_dir`, epoch e is written to `dense_{dates[e]}.ply` (default e).
+    `fuse` = (tol, min_views) fuses every epoch's two maps into one cloud (`build_dense_cloud`; `views=(0, 1)` or `(1, 0)` must come with
+    it); `options` are `build_dense_cloud`'s other ones, `ply_scalars` among them, handed down as they are."""
+    if fuse is not None:
+        options["fuse"] = fuse
     E = len(images)
     results = list(cameras) if len(cameras) == E and all(hasattr(c, "cameras") and hasattr(c, "points3d") for c in cameras) else None
     if results is not None:

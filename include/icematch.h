@@ -670,6 +670,32 @@ int im_depth_fill_holes(im_ctx* ctx, const int16_t* d_plane, const double* d_w, 
                         int max_hole, int max_diff, double w_first, double w_step, int D, int16_t* d_plane_out, double* d_w_out, float* d_score_out,
                         uint8_t* d_filled, long long* d_count, void* stream);
 
+/* ---- fusion of the two depth maps: one point per surface sample, placed by both views (csrc/dense_fuse.hip, csrc/fuse_pixel.h), where
+ * the driver asks Metashape for `buildDenseCloud(point_confidence=True)` (`metashape.py:198-240`). A definition of this project's own
+ * (DESIGN §4), restated in tests/fuse_oracle.py: bit-identical; it is NOT Metashape's merge, and parity with Metashape is unpinned by
+ * construction. All arrays in DEVICE memory but the poses. View a is the base, view b the other one; keep masks are uint8, non-zero = kept,
+ * as im_dense_consistency writes them. h_pose [30] = inv(Ka), R, t, Kb with Xb = R Xa + t (the layout of im_dense_consistency); tol >= 0
+ * is an inverse depth of the view linked INTO. float64, exactly these operations in this order, no contraction.
+ * The link of kept pixel p = (u, v) of view a: Xa = inv(Ka) (u, v, 1) / w_a[p], Xb = R Xa + t as im_dense_consistency computes them; it
+ * fails unless Xb.z > 0; j = (rint(px / pz), rint(py / pz)) of Kb Xb; it fails unless j lies inside view b (a NaN fails) and keep_b[j] != 0,
+ * and unless |w_b[j] - 1 / Xb.z| <= tol. link[p] = j as a linear index, else -1; -1 where keep_a[p] == 0.
+ * The second measurement on p's ray: d_i = (Ki[3i] u + Ki[3i+1] v) + Ki[3i+2], g = (R[6] d_0 + R[7] d_1) + R[8] d_2,
+ * w' = g / (1.0 / w_b[j] - t[2]); usable when w' is finite and > 0.
+ * im_dense_fuse_link: clears d_claimed [hb][wb], then per pixel p of view a. Linked: a = max(double(score_a[p]), 0),
+ * b = max(double(score_b[j]), 0); if w' is usable, w_out = (a w + b w') / (a + b) when a + b > 0, else 0.5 (w + w'), and
+ * score_out = max(score_a[p], score_b[j]); if it is not, w_out = w and score_out = score_a[p]; either way views[p] = 2 and claimed[j] = 1.
+ * Kept and unlinked: copied through with views = 1. Not kept: w_out = 0, score_out = 0, views = 0. Several p may claim one j; each keeps
+ * its own point, and the stores of the same byte need no atomic.
+ * im_dense_fuse_rest: h_pose_ba is the inverted pose (inv(Kb), R^T, -R^T t, Ka), tol_a an inverse depth of view a. rest[q] = 1 iff
+ * keep_b[q] != 0, claimed[q] == 0 and the link of q into view a fails: a surface that view a does not represent; else 0.
+ * Both write every element of every output, and return -83, without launching and with the outputs untouched, for a null pointer, a side
+ * outside 1..16384, a negative or NaN tolerance, or an output that is one of the inputs. Enqueue only. */
+int im_dense_fuse_link(im_ctx* ctx, const uint8_t* d_keep_a, const double* d_w_a, const float* d_score_a, int ha, int wa, const uint8_t* d_keep_b,
+                       const double* d_w_b, const float* d_score_b, int hb, int wb, const double* h_pose, double tol, int* d_link, double* d_w_out,
+                       float* d_score_out, uint8_t* d_views, uint8_t* d_claimed, void* stream);
+int im_dense_fuse_rest(im_ctx* ctx, const uint8_t* d_keep_b, const double* d_w_b, int hb, int wb, const uint8_t* d_keep_a, const double* d_w_a, int ha,
+                       int wa, const double* h_pose_ba, double tol_a, const uint8_t* d_claimed, uint8_t* d_rest, void* stream);
+
 /* ---- volume variations (`scripts/pcd_postprocessing/volume_variations.py`; `post_processing/cloudcompare_fun.py`:
  * `DemOfDifference.compute_volume` over CloudCompare's `ComputeVolume25D`; `post_processing/open3d_fun.py`: `filter_pcd_by_polyline`);
  * csrc/dod.hip, csrc/dod_cell.h. The DEM of difference of P pairs (ground, ceil) over E clouds that lie one behind the other in d_pts
