@@ -20,11 +20,15 @@ namespace {
 constexpr int DENSE_MAX_SIDE = 16384, DENSE_MAX_PLANES = 4096, DENSE_MAX_RADIUS = 7;
 constexpr int DENSE_TILE_W = 64, DENSE_TILE_H = 16;      // the ref pixels one block of the sweep owns (not part of the definition)
 
-// H = A + w_k B entry by entry, w_k = w_first + k w_step: the homography of plane k (inverse depth w_k) from ref pixels to src pixels
+// H = A + w B entry by entry: the homography of the plane of inverse depth w from ref pixels to src pixels
+__device__ __forceinline__ void dense_plane_at(const double* A, const double* B, double w, double* H) {
+#pragma clang fp contract(off)
+    for (int i = 0; i < 9; ++i) H[i] = A[i] + w * B[i];
+}
+// plane k of the schedule: w_k = w_first + k w_step
 __device__ __forceinline__ void dense_plane(const double* A, const double* B, double w_first, double w_step, int k, double* H) {
 #pragma clang fp contract(off)
-    const double wk = w_first + (double)k * w_step;
-    for (int i = 0; i < 9; ++i) H[i] = A[i] + wk * B[i];
+    dense_plane_at(A, B, w_first + (double)k * w_step, H);
 }
 
 // The warped value of ref pixel (u, v): false if z <= 0 (or NaN), a coordinate is not finite or one of the four taps lies outside src

@@ -18,6 +18,10 @@ in tests/fuse_oracle.py): a kept pixel of the base view is linked to the kept pi
 point placed by both measurements, the other view adds only what the base does not represent, and every point carries the number of
 views that agreed on it. Once more a definition of this project's own, not Metashape's merge of its depth maps: parity with Metashape
 is unpinned by construction; the default None makes no call and concatenates the views' clouds as before.
+`refine=(passes, fit_radius)` refines each view's map over slanted windows behind the clean-up (csrc/dense_refine.hip, csrc/refine_pixel.h,
+restated in tests/refine_oracle.py): the sweep warps every sample of a window with the centre's inverse depth, which a surface seen
+obliquely does not have; a pass fits the slant of every pixel to the map and searches a few sub-plane candidates whose window follows
+it. A definition of this project's own as well, parity with Metashape unpinned by construction; the default None makes no call.
 
 Cameras are objects with `.K .R .t` (X_cam = R X_world + t) and optionally `.dist`, as `core.Camera` and the cameras of a
 `sfm.BundleResult`. Images are uint8 [h, w] or [h, w, 3] (RGB) numpy arrays or device tensors."""
@@ -38,6 +42,7 @@ logger = logging.getLogger(__name__)
 MAX_SIDE, MAX_PLANES, MAX_RADIUS = 16384, 4096, 7
 MAX_SGM_PLANES, MAX_PENALTY, MAX_VOLUME = 256, 4095, 1 << 32
 MAX_PLANE_DIFF, MAX_HOLE, MAX_MIN_SIZE = 4095, 4096, (1 << 31) - 1
+MAX_FIT_RADIUS, MAX_SLANT_DIFF, MAX_SPAN, MAX_SUB, MAX_REFINE_PASSES = 7, 64.0, 4, 8, 16
 REGULARISATIONS = (None, "sgm")
 DEPTH_FILTERS = {"NoFiltering": None, "MildFiltering": 2.0, "ModerateFiltering": 1.0, "AggressiveFiltering": 0.5}
 
@@ -412,6 +417,119 @@ def fill_holes(m: DepthMap, max_hole: int = 64, max_diff: int = 2, engine=None, 
     return (out, count) if return_counts else out
 
 
+# ---- slanted-window refinement ----------------------------------------------------------------------------------------------------------------
+REFINE_OPTIONS = ("passes", "fit_radius", "max_diff", "min_count", "span", "sub")
+
+
+def _check_int(what, name, v, lo, hi):
+    try:
+        ok = not isinstance(v, (bool, str)) and int(v) == v and lo <= v <= hi
+    except (TypeError, ValueError, OverflowError):                                # None, a NaN, an infinity
+        ok = False
+    if not ok:
+        raise ValueError(f"{what}: {name} must be an integer in {lo}..{hi} (got {v!r})")
+
+
+def _check_slant(what, fit_radius, max_diff, min_count):
+    _check_int(what, "fit_radius", fit_radius, 1, MAX_FIT_RADIUS)
+    if isinstance(max_diff, (bool, str)) or not isinstance(max_diff, (int, float, np.integer, np.floating)) or not 0.0 < max_diff <= MAX_SLANT_DIFF:
+        raise ValueError(f"{what}: max_diff must be a number of plane steps in (0, {MAX_SLANT_DIFF:g}] (got {max_diff!r})")
+    _check_int(what, "min_count", min_count, 3, 225)
+
+
+def _check_refine_options(what, passes, fit_radius, max_diff, min_count, span, sub):
+    _check_int(what, "passes", passes, 1, MAX_REFINE_PASSES)
+    _check_slant(what, fit_radius, max_diff, min_count)
+    _check_int(what, "span", span, 1, MAX_SPAN)
+    _check_int(what, "sub", sub, 1, MAX_SUB)
+
+
+def _check_refine(refine):
+    """`refine` = None | (passes, fit_radius) | a dict of `refine_slanted`'s options but `radius` and `min_var`, which are the call's own:
+    None, or the checked options as a dict."""
+    if refine is None:
+        return None
+    if isinstance(refine, dict):
+        unknown = sorted(set(refine) - set(REFINE_OPTIONS))
+        if unknown:
+            raise ValueError(f"dense: refine: unknown options {unknown}; a dict of {list(REFINE_OPTIONS)} is expected (radius and min_var are the call's own)")
+        options = dict(refine)
+    else:
+        try:
+            passes, fit_radius = refine
+        except (TypeError, ValueError):
+            raise ValueError(f"dense: refine is None, (passes, fit_radius) or a dict of {list(REFINE_OPTIONS)} (got {refine!r})") from None
+        options = dict(passes=passes, fit_radius=fit_radius)
+    full = dict(passes=2, fit_radius=4, max_diff=2.0, min_count=6, span=1, sub=4)
+    full.update(options)
+    _check_refine_options("dense: refine", **full)
+    return full
+
+
+def _check_map(m, what):
+    _check_plane_map(m.plane, what)
+    if not torch.is_tensor(m.w) or m.w.dtype != torch.float64 or m.w.shape != m.plane.shape:
+        raise ValueError(f"{what}: w is a float64 tensor of the plane map's shape")
+    if not torch.is_tensor(m.score) or m.score.dtype != torch.float32 or m.score.shape != m.plane.shape:
+        raise ValueError(f"{what}: score is a float32 tensor of the plane map's shape")
+    w_step = m.schedule[1]
+    if not np.isfinite(w_step) or w_step == 0.0:
+        raise ValueError(f"{what}: the schedule's w_step must be finite and not zero (got {w_step}); a one-plane schedule has no step to search along")
+
+
+def slant_map(m: DepthMap, fit_radius: int = 4, max_diff: float = 2.0, min_count: int = 6, engine=None):
+    """`im_dense_slant` (csrc/dense_refine.hip, csrc/refine_pixel.h, restated in tests/refine_oracle.py): (slant [h, w, 2] float64, fitted [h, w]
+    uint8) on the device. The slant of a kept pixel, in plane steps per pixel along (u, v), is the least-squares plane through the inverse
+    depths of the kept pixels of its (2 fit_radius + 1)^2 neighbourhood that lie within `max_diff` plane steps of its own, out of exact
+    integer sums; fitted where at least `min_count` of them count and they do not lie on one line, zero elsewhere."""
+    _check_map(m, "slant_map")
+    _check_slant("slant_map", fit_radius, max_diff, min_count)
+    eng = default_engine(engine)
+    dev = eng.device
+    plane, w = m.plane.to(dev).contiguous(), m.w.to(dev).contiguous()
+    h, wd = plane.shape
+    slant = torch.empty((h, wd, 2), dtype=torch.float64, device=dev)
+    fitted = torch.empty((h, wd), dtype=torch.uint8, device=dev)
+    eng.ctx.call("im_dense_slant", ptr(plane), ptr(w), h, wd, float(m.schedule[1]), int(fit_radius), float(max_diff), int(min_count), ptr(slant), ptr(fitted),
+                 eng.stream_ptr())
+    return slant, fitted
+
+
+def refine_slanted(m: DepthMap, other: DepthMap, passes: int = 2, fit_radius: int = 4, max_diff: float = 2.0, min_count: int = 6, span: int = 1,
+                   sub: int = 4, radius: int = 3, min_var: int = 4, engine=None, return_taken: bool = False):
+    """The map `m` with its inverse depths refined over slanted windows against the view of `other` (of which only the grey image, K and the
+    pose are read): `passes` times `slant_map`, then `im_dense_refine`. Every kept pixel whose window of `radius` lies inside the image
+    searches the candidates -span .. span plane steps around its inverse depth, `sub` per step, each scored like the sweep but over a
+    window whose samples follow the pixel's slant; the best one (with the sweep's parabola between its neighbours) is taken where it
+    scores strictly more than the pixel does now, so no score falls. `plane` is left as it was: it stays the label that the clean-up
+    segments, `w` carries the measurement. New tensors; `m` is not modified. `return_taken`: also the last pass's mask [h, w] uint8.
+    A definition of this project's own, not Metashape's matcher; parity with Metashape is unpinned by construction."""
+    _check_map(m, "refine_slanted")
+    _check_refine_options("refine_slanted", passes, fit_radius, max_diff, min_count, span, sub)
+    for g, name in ((m.grey, "the map's"), (other.grey, "the other view's")):
+        if not torch.is_tensor(g) or g.dtype != torch.uint8 or g.ndim != 2:
+            raise ValueError(f"refine_slanted: {name} grey image is a uint8 [h, w] tensor")
+    if m.grey.shape != m.plane.shape:
+        raise ValueError("refine_slanted: the map's grey image has the map's shape")
+    (h0, w0), (h1, w1) = m.grey.shape, other.grey.shape
+    _check_sweep(h0, w0, h1, w1, 1, radius, min_var)
+    R = other.R @ m.R.T
+    A, B = sweep_matrices(m.K, other.K, R, other.t - R @ m.t)
+    eng = default_engine(engine)
+    dev = eng.device
+    ref, src = m.grey.to(dev).contiguous(), other.grey.to(dev).contiguous()
+    plane, w, score = m.plane.to(dev).contiguous(), m.w.to(dev).contiguous(), m.score.to(dev).contiguous()
+    out, taken = m._replace(plane=plane, w=w, score=score), None
+    for _ in range(int(passes)):
+        slant, _ = slant_map(out, fit_radius, max_diff, min_count, engine=eng)
+        w_out, score_out = torch.empty_like(w), torch.empty_like(score)
+        taken = torch.empty((h0, w0), dtype=torch.uint8, device=dev)
+        eng.ctx.call("im_dense_refine", ptr(ref), h0, w0, ptr(src), h1, w1, A.ctypes.data, B.ctypes.data, ptr(plane), ptr(out.w), ptr(out.score), ptr(slant),
+                     float(m.schedule[1]), int(radius), int(min_var), int(span), int(sub), ptr(w_out), ptr(score_out), ptr(taken), eng.stream_ptr())
+        out = out._replace(w=w_out, score=score_out)
+    return (out, taken) if return_taken else out
+
+
 def consistency(map0: DepthMap, map1: DepthMap, depth_filter: str = "ModerateFiltering", engine=None) -> torch.Tensor:
     """`im_dense_consistency`: keep [h, w] uint8 on the device for the pixels of `map0` against `map1`."""
     tau = filter_tolerance(depth_filter)
@@ -526,19 +644,23 @@ def _prepare(image, cam, downscale, eng):
 
 def build_depth_maps(images, cameras, depth_range=None, sparse_points=None, downscale: int = 1, radius: int = 3, min_score: float = 0.8,
                      min_var: int = 4, max_step_px: float = 1.0, engine=None, regularisation=None, p1: int = 16, p2: int = 128, paths: int = 8,
-                     speckle=None, holes=None):
+                     speckle=None, holes=None, refine=None):
     """The depth maps of both views of a stereo pair, `chunk.buildDepthMaps` of the reference with a definition of this project's own
     (module docstring): [DepthMap of view 0, DepthMap of view 1], on the device. `depth_range` = (d_min, d_max) in view 0 (and, through the
     same points, view 1) or None: then `sparse_points` [n, 3] give it per view (`depth_range_from_points`). Images with a non-zero
     `dist` are undistorted first (`sfm.undistort_image`). `regularisation` = None: each pixel takes its best plane by itself;
     "sgm": semi-global aggregation of the costs with the penalties `p1 <= p2` over `paths` (4 or 8) directions decides (`sweep`), which
     holds at most 256 planes per view. `speckle` = (min_size, max_diff) drops the small components of each view's map (`remove_speckles`),
-    `holes` = (max_hole, max_diff) then fills its small holes (`fill_holes`): after the sweep, under either regularisation. None: neither."""
+    `holes` = (max_hole, max_diff) then fills its small holes (`fill_holes`): after the sweep, under either regularisation. None: neither.
+    `refine` = (passes, fit_radius) or a dict of `refine_slanted`'s options (passes, fit_radius, max_diff, min_count, span, sub) then refines
+    each view's map over slanted windows (`refine_slanted`), with this call's `radius` and `min_var`; a filled pixel has score 0, so any
+    valid candidate is taken there and the pixel gains a measured confidence. None: no call, and the maps are what they were."""
     if len(images) != 2 or len(cameras) != 2:
         raise ValueError("build_depth_maps: a stereo pair has two images and two cameras")
     downscale = _factor(downscale)
     _check_regularisation(regularisation, p1, p2, paths)
     speckle, holes = _check_clean_up(speckle, holes)
+    refine = _check_refine(refine)
     if depth_range is None and sparse_points is None:
         raise ValueError("build_depth_maps: a depth_range or sparse_points to take it from are needed")
     # everything that can be refused is refused before the first launch
@@ -554,6 +676,8 @@ def build_depth_maps(images, cameras, depth_range=None, sparse_points=None, down
             _check_volume(*small_shapes[v], schedule[2])
         if holes is not None:
             _check_fill_schedule(schedule, "dense: holes")
+        if refine is not None:
+            _check_fill_schedule(schedule, "dense: refine")
         plans.append((schedule, sweep_matrices(small[v].K, small[1 - v].K, *relative_pose(small[v], small[1 - v]))))
     chosen = {} if regularisation is None else dict(regularisation=regularisation, p1=p1, p2=p2, paths=paths)
     eng = default_engine(engine)
@@ -568,19 +692,21 @@ def build_depth_maps(images, cameras, depth_range=None, sparse_points=None, down
         if holes is not None:
             m = fill_holes(m, *holes, engine=eng)
         maps.append(m)
+    if refine is not None:                        # of the other view only the image and the camera are read: the order does not matter
+        maps = [refine_slanted(maps[v], maps[1 - v], radius=radius, min_var=min_var, engine=eng, **refine) for v in range(2)]
     return maps
 
 
 def build_dense_cloud(images, cameras, sparse_points=None, depth_filter: str = "ModerateFiltering", downscale: int = 1, views=(0,), save_path=None,
                       depth_range=None, radius: int = 3, min_score: float = 0.8, min_var: int = 4, max_step_px: float = 1.0, engine=None,
                       regularisation=None, p1: int = 16, p2: int = 128, paths: int = 8, speckle=None, holes=None, fuse=None,
-                      ply_scalars=()) -> PointCloud:
+                      ply_scalars=(), refine=None) -> PointCloud:
     """`MetashapeProject.build_dense_cloud` of the reference with a definition of this project's own: the depth maps of the pair, their
     consistency under `depth_filter`, and the cloud of the kept pixels of `views` (view 0's points first) as a `core.PointCloud` with
     colours, normals turned towards the camera and `confidence` (the score, float32). `save_path` writes it as PLY (`dense_{date}.ply`),
     with the per-point scalars named in `ply_scalars` ("confidence", "views") behind the other properties.
-    `regularisation`, `p1`, `p2`, `paths`, `speckle`, `holes`: as `build_depth_maps` takes them; the clean-up comes before the
-    consistency check, and a filled pixel enters the cloud with confidence 0.
+    `regularisation`, `p1`, `p2`, `paths`, `speckle`, `holes`, `refine`: as `build_depth_maps` takes them; the clean-up and the refinement
+    come before the consistency check, and a filled pixel enters the cloud with confidence 0 unless the refinement measured it.
     `fuse` = None: the clouds of `views` one behind the other, a surface that both views see twice. `fuse` = (tol, min_views) fuses the two
     maps instead (the module-level `fuse`; `views` must name both views, the first is the base): `depth_filter` still decides both keep
     masks first, then the base view gives one point per kept pixel with at least `min_views` (1 or 2) views, from the fused map, and with
@@ -589,6 +715,7 @@ def build_dense_cloud(images, cameras, sparse_points=None, depth_filter: str = "
     filter_tolerance(depth_filter)
     _check_regularisation(regularisation, p1, p2, paths)
     _check_clean_up(speckle, holes)
+    _check_refine(refine)
     fuse = _check_fuse(fuse)
     ply_scalars = PointCloud.check_scalars(ply_scalars)
     views = tuple(views)
@@ -603,6 +730,8 @@ def build_dense_cloud(images, cameras, sparse_points=None, depth_filter: str = "
         chosen["speckle"] = speckle
     if holes is not None:
         chosen["holes"] = holes
+    if refine is not None:
+        chosen["refine"] = refine
     maps = build_depth_maps(images, cameras, depth_range, sparse_points, downscale, radius, min_score, min_var, max_step_px, engine=engine, **chosen)
     eng = default_engine(engine)
     parts, seen = [], None
@@ -635,14 +764,17 @@ def build_dense_cloud(images, cameras, sparse_points=None, depth_filter: str = "
     return pcd
 
 
-def dense_series(images, cameras, sparse_points=None, out_dir=None, dates=None, fuse=None, **options) -> list:
+def dense_series(images, cameras, sparse_points=None, out_dir=None, dates=None, fuse=None, refine=None, **options) -> list:
     """`build_dense_cloud` for every epoch of a sequence: `images` a list of E pairs, `cameras` one pair, a list of E pairs or a list of E
     `sfm.BundleResult` (as `bundle_adjust_epochs` returns them: their cameras and, unless `sparse_points` is given, their points are
     taken), `sparse_points` None, one array or a list of E. With `out_dir`, epoch e is written to `dense_{dates[e]}.ply` (default e).
     `fuse` = (tol, min_views) fuses every epoch's two maps into one cloud (`build_dense_cloud`; `views=(0, 1)` or `(1, 0)` must come with
-    it); `options` are `build_dense_cloud`'s other ones, `ply_scalars` among them, handed down as they are."""
+    it); `refine` = (passes, fit_radius) or a dict refines every epoch's maps over slanted windows (`refine_slanted`); `options` are
+    `build_dense_cloud`'s other ones, `ply_scalars` among them, handed down as they are."""
     if fuse is not None:
         options["fuse"] = fuse
+    if refine is not None:
+        options["refine"] = refine
     E = len(images)
     results = list(cameras) if len(cameras) == E and all(hasattr(c, "cameras") and hasattr(c, "points3d") for c in cameras) else None
     if results is not None:

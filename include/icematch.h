@@ -696,6 +696,34 @@ int im_dense_fuse_link(im_ctx* ctx, const uint8_t* d_keep_a, const double* d_w_a
 int im_dense_fuse_rest(im_ctx* ctx, const uint8_t* d_keep_b, const double* d_w_b, int hb, int wb, const uint8_t* d_keep_a, const double* d_w_a, int ha,
                        int wa, const double* h_pose_ba, double tol_a, const uint8_t* d_claimed, uint8_t* d_rest, void* stream);
 
+/* ---- slanted-window refinement of a depth map (csrc/dense_refine.hip, csrc/refine_pixel.h): im_dense_sweep warps every sample of a window
+ * with the centre's inverse depth (fronto-parallel); this pass lets the window follow the surface's slant. A definition of this project's
+ * own, restated in tests/refine_oracle.py: bit-identical; it is NOT Metashape's matcher, and parity with Metashape is unpinned
+ * by construction. All arrays in DEVICE memory unless named h_. A map is (d_plane int16, d_w float64, d_score float32) as im_dense_sweep
+ * writes it, with the step w_step of its schedule; a pixel is kept when plane >= 0. Slants are in plane steps per pixel.
+ * im_dense_slant: per kept pixel i, over the kept pixels j of its (2 fit_radius + 1)^2 neighbourhood inside the map (i included):
+ * d = (w_j - w_i) / w_step; j counts when fabs(d) <= max_diff (a NaN fails), at the integer height q = llrint(1024 d). Exact int64 sums over
+ * the counting j of 1, dx, dy, dx^2, dy^2, dx dy, q, q dx, q dy give a11 = n Sxx - Sx^2, a22 = n Syy - Sy^2, a12 = n Sxy - Sx Sy,
+ * b1 = n Sqx - Sx Sq, b2 = n Sqy - Sy Sq, det = a11 a22 - a12^2. Fitted when n >= min_count and det > 0:
+ * gu = (double(a22 b1 - a12 b2) / double(det)) / 1024, gv = (double(a11 b2 - a12 b1) / double(det)) / 1024; else gu = gv = 0.
+ * d_slant [h][w][2] float64 = (gu, gv), d_fitted [h][w] uint8; a dropped pixel gets zeros. Every element is written.
+ * im_dense_refine: ref, src, h_A, h_B, r and min_var as im_dense_sweep takes them. A pixel (u, v) is refined when it is kept and its window
+ * of radius r lies inside ref; every other pixel is copied through. Candidates c = -span sub .. span sub; sample (dx, dy) of candidate c is
+ * im_dense_sweep's sample of ref pixel (u + dx, v + dy) under H = A + w_s B, w_s = w_i + t w_step, t = double(c) / double(sub) + (gu dx + gv dy).
+ * A candidate with an invalid sample is invalid; else it scores the sweep's s of the integer window sums. The best is chosen in the order
+ * 0, -1, +1, -2, +2, ..., a later candidate replacing it only on a strictly greater score; off is the sweep's parabola over the best's two
+ * neighbours when both lie in the range, both are valid and the denominator is negative. Taken when s0 > double(score_i), strictly:
+ * w_out = w_i + ((double(c) + off) / double(sub)) w_step, score_out = float(s0); else w_out = w_i, score_out = score_i. d_plane is never
+ * changed. d_taken [h0][w0] uint8. The outputs are arrays of their own; every element is written; no score falls.
+ * Both return -83, without launching and with the outputs untouched, for a null pointer, a side outside 1..16384, fit_radius or r outside
+ * 1..7, max_diff not in (0, 64], min_count outside 3..225, span outside 1..4, sub outside 1..8, min_var outside 0..2^26, or a w_step that
+ * is zero or not finite. One block per im_dense_tile_w() x im_dense_tile_h() pixels; the tile is no part of the definition. Enqueue only. */
+int im_dense_slant(im_ctx* ctx, const int16_t* d_plane, const double* d_w, int h, int w, double w_step, int fit_radius, double max_diff, int min_count,
+                   double* d_slant, uint8_t* d_fitted, void* stream);
+int im_dense_refine(im_ctx* ctx, const uint8_t* d_ref, int h0, int w0, const uint8_t* d_src, int h1, int w1, const double* h_A, const double* h_B,
+                    const int16_t* d_plane, const double* d_w, const float* d_score, const double* d_slant, double w_step, int r, long long min_var, int span,
+                    int sub, double* d_w_out, float* d_score_out, uint8_t* d_taken, void* stream);
+
 /* ---- volume variations (`scripts/pcd_postprocessing/volume_variations.py`; `post_processing/cloudcompare_fun.py`:
  * `DemOfDifference.compute_volume` over CloudCompare's `ComputeVolume25D`; `post_processing/open3d_fun.py`: `filter_pcd_by_polyline`);
  * csrc/dod.hip, csrc/dod_cell.h. The DEM of difference of P pairs (ground, ceil) over E clouds that lie one behind the other in d_pts
