@@ -131,6 +131,9 @@ SIGNATURES = {
     "im_dense_fuse_rest": [_P, _P, _P, _I, _I, _P, _P, _I, _I, _P, _D, _P, _P, _P],
     "im_dense_slant": [_P, _P, _P, _I, _I, _D, _I, _D, _I, _P, _P, _P],
     "im_dense_refine": [_P, _P, _I, _I, _P, _I, _I, _P, _P, _P, _P, _P, _P, _D, _I, _L, _I, _I, _P, _P, _P, _P],
+    "im_flow_match": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _L, _D, _P, _P, _P, _P, _P, _P],
+    "im_flow_check": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _D, _P, _P],
+    "im_flow_lift": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _I, _I, _P, _D, _D, _P, _P, _P, _P],
     "im_depth_tile_w": [],
     "im_depth_tile_h": [],
     "im_depth_components": [_P, _P, _I, _I, _I, _I, _P, _P, _P],

@@ -724,6 +724,36 @@ int im_dense_refine(im_ctx* ctx, const uint8_t* d_ref, int h0, int w0, const uin
                     const int16_t* d_plane, const double* d_w, const float* d_score, const double* d_slant, double w_step, int r, long long min_var, int span,
                     int sub, double* d_w_out, float* d_score_out, uint8_t* d_taken, void* stream);
 
+/* ---- dense surface displacement between two epochs (csrc/dense_flow.hip, csrc/flow_pixel.h): the pixel of one camera's image at epoch B
+ * that shows what a pixel of its image at epoch A shows, and both ends lifted to world points through each epoch's own depth map and pose.
+ * The reference has no such step (its velocities come from tracked keypoints): a definition of this project's own, restated
+ * in tests/flow_oracle.py: bit-identical. Parity with any image-correlation package is unpinned. All arrays in DEVICE memory unless named h_.
+ * im_flow_match: d_a, d_b [h][w] uint8. A candidate (dx, dy), |dx|, |dy| <= search, compares the (2 r + 1)^2 window of a centred on (u, v)
+ * with the window of b centred on (u + prior_u + dx, v + prior_v + dy); it is invalid if either window leaves its image. With n = (2 r + 1)^2
+ * and the exact integer sums: VA = n saa - sa^2, VB = n sbb - sb^2, C = n sab - sa sb; invalid if VA < n^2 min_var, VB < n^2 min_var, VA <= 0
+ * or VB <= 0, else s = double(C) / sqrt(double(VA) double(VB)). Candidates are visited in ascending (dx^2 + dy^2, dy, dx), a later one replacing
+ * the best only on a strictly greater score. The pixel is invalid if no candidate scored or the best is below min_score. Along x (and y
+ * likewise): if both neighbours (dx - 1, dy), (dx + 1, dy) lie in the search range and score, and den = (sm - 2 s0) + sp < 0, then
+ * off = (0.5 (sm - sp)) / den, else 0. d_du = double(prior_u + dx) + offx, d_dv likewise (float64), d_score = float(s0), d_valid uint8; zeros
+ * where invalid or where d_ask [h][w] uint8 (NULL = every pixel) is 0. One block per im_dense_tile_w() x im_dense_tile_h() pixels.
+ * im_flow_check: a valid forward pixel (u, v) is kept when j = (rint(u + du), rint(v + dv)) lies inside the image, the backward field is
+ * valid at j and (du + du_b[j])^2 + (dv + dv_b[j])^2 <= tol^2; a NaN fails. d_keep [h][w] uint8.
+ * im_flow_lift: h_cam_a, h_cam_b [21] = inv(K), R, t as im_dense_cloud takes them. A pixel is lifted when d_keep, d_valid are set and
+ * d_plane_a >= 0. P = the world point of (u, v, w_a). With x = u + du, y = v + dv: the four taps floor(x) .. floor(x) + 1, floor(y) ..
+ * floor(y) + 1 must lie inside map b [hb][wb] (a tap of weight zero included), have plane_b >= 0 and keep_b set, and their inverse depths
+ * span at most max_diff |w_step_b|; w = top + ty (bot - top), top = w00 + tx (w01 - w00), bot = w10 + tx (w11 - w10). Q = the world point
+ * of (x, y, w) through camera b, D = Q - P. d_P, d_D [h][w][3] float64, d_ok [h][w] uint8; zeros where not lifted.
+ * All write every element of every output, and return -83, without launching and with the outputs untouched, for a null required pointer,
+ * a side outside 1..16384, r outside 1..15, search outside 0..16, a prior outside -4096..4096, min_var outside 0..2^26, a min_score that
+ * is not finite, a tol or max_diff that is not finite or not > 0, or a w_step_b that is zero or not finite. Enqueue only. */
+int im_flow_match(im_ctx* ctx, const uint8_t* d_a, const uint8_t* d_b, int h, int w, int r, int search, int prior_u, int prior_v, long long min_var,
+                  double min_score, const uint8_t* d_ask, double* d_du, double* d_dv, float* d_score, uint8_t* d_valid, void* stream);
+int im_flow_check(im_ctx* ctx, const double* d_du, const double* d_dv, const uint8_t* d_valid, const double* d_du_b, const double* d_dv_b,
+                  const uint8_t* d_valid_b, int h, int w, double tol, uint8_t* d_keep, void* stream);
+int im_flow_lift(im_ctx* ctx, const double* d_du, const double* d_dv, const uint8_t* d_valid, const uint8_t* d_keep, const int16_t* d_plane_a,
+                 const double* d_w_a, int h, int w, const double* h_cam_a, const int16_t* d_plane_b, const double* d_w_b, const uint8_t* d_keep_b, int hb,
+                 int wb, const double* h_cam_b, double w_step_b, double max_diff, double* d_P, double* d_D, uint8_t* d_ok, void* stream);
+
 /* ---- volume variations (`scripts/pcd_postprocessing/volume_variations.py`; `post_processing/cloudcompare_fun.py`:
  * `DemOfDifference.compute_volume` over CloudCompare's `ComputeVolume25D`; `post_processing/open3d_fun.py`: `filter_pcd_by_polyline`);
  * csrc/dod.hip, csrc/dod_cell.h. The DEM of difference of P pairs (ground, ceil) over E clouds that lie one behind the other in d_pts
