@@ -3,7 +3,8 @@
 // is not reproduced: every quantity has a definition of this project's own (dense_pixel.h) and is pinned bit for bit against
 // tests/dense_oracle.py. Parity with Metashape is unpinned by construction.
 //
-//   dense_sweep_kernel        one block of 256 threads per 64 x 16 tile of ref pixels. The ref bytes of the tile and its halo of r are staged in
+//   dense_sweep_kernel        one block of 256 threads per 64 x 16 tile of ref pixels (the tile, its staging and the scoring of one plane are
+//                             dense_tile.h's, shared with dense_costs_kernel). The ref bytes of the tile and its halo of r are staged in
 //                             LDS once; then, for every plane inside the kernel: (A) each thread warps its share of tile + halo into LDS,
 //                             (B) the rows are box-summed over 2 r + 1 columns into 8-byte partials (sum b^2; sum b, the invalid count and
 //                             sum a b packed in the other 8 bytes), rows of 64 consecutive entries, one per lane: ds_read_b64 / ds_write_b64
@@ -11,23 +12,16 @@
 //                             keeps the running best, its predecessor and its successor in registers. No cost volume reaches memory.
 //   dense_consistency_kernel  one thread per pixel of map 0
 //   DenseCloudScan            mark = the keep byte, scan.h's three kernels, and the scan's write is the scatter of point, colour, normal, confidence
+// The host checks shared with the other dense stages are dense_host.h's.
 // All sums are integers: the order of execution does not matter. No atomics. Enqueue only.
 #include "common.h"
 #include "ctx.h"
 #include "stage_scratch.h"
-#include "dense_pixel.h"
+#include "dense_tile.h"
+#include "dense_host.h"
 
 namespace im {
 namespace {
-
-constexpr int DENSE_REFUSED = -83;
-constexpr int TW = DENSE_TILE_W, TH = DENSE_TILE_H, DENSE_BLOCK = 256;
-constexpr int HW = TW + 2 * DENSE_MAX_RADIUS, HH = TH + 2 * DENSE_MAX_RADIUS;      // 78 x 30 with the largest halo
-constexpr int PIX = TW * TH / DENSE_BLOCK;                                        // pixels of the tile per thread
-constexpr unsigned INV_BIT = 1u << 31;
-static_assert(TW == 64 && TW * TH % DENSE_BLOCK == 0, "a row of partials is one entry per lane; whole rounds of the block cover the tile");
-// sum b over 15 samples < 2^22 and the invalid count <= 15 share 32 bits; sum a b over 15 samples < 2^30
-static_assert(15LL * 261120 < (1LL << 22) && 15LL * 255 * 261120 < (1LL << 31), "the packed row partials");
 
 #include "scan.h"
 
@@ -39,107 +33,48 @@ struct DenseSweepArgs {
     int16_t* plane; double* w; float* score;
 };
 
-__global__ __launch_bounds__(DENSE_BLOCK) void dense_sweep_kernel(DenseSweepArgs a) {
-    __shared__ uint8_t s_a[HH * HW];                  // ref bytes of tile + halo (0 outside ref)
-    __shared__ unsigned s_b[HH * HW];                 // the plane's warped values, INV_BIT where invalid
-    __shared__ unsigned long long s_bb[HH * TW];      // row partials: sum b^2
-    __shared__ uint2 s_px[HH * TW];                   //               x = sum b | invalid count << 22, y = sum a b
+__global__ __launch_bounds__(TILE_BLOCK) void dense_sweep_kernel(DenseSweepArgs a) {
+    __shared__ PlaneLds L;                            // dense_tile.h: ref bytes, the plane's samples, the two rows of partials
     __shared__ double s_AB[18];                       // A and B
-    const int t = threadIdx.x, r = a.r, side = 2 * r + 1;
-    const int x0 = blockIdx.x * TW, y0 = blockIdx.y * TH;
-    const int hw = TW + 2 * r, hh = TH + 2 * r;       // the halo region of this radius, rows of hw entries
+    const int t = threadIdx.x, r = a.r;
 
-    // pixels of this thread: p = t + 256 j -> column p % 64 (one per lane), row p / 64
     int16_t* const o_plane = a.plane; double* const o_w = a.w; float* const o_score = a.score;
     // a tile none of whose pixels has its window inside ref: every pixel is invalid for every plane
-    const bool any = x0 + TW > r && x0 < a.w0 - r && y0 + TH > r && y0 < a.h0 - r;
-    if (!any) {
+    if (!tile_any_window_inside(a.h0, a.w0, r)) {
 #pragma unroll
         for (int j = 0; j < PIX; ++j) {
-            const int p = t + DENSE_BLOCK * j, u = x0 + (p & (TW - 1)), v = y0 + p / TW;
-            if (u < a.w0 && v < a.h0) {
-                const long i = (long)v * a.w0 + u;
+            const TilePixel q = tile_pixel(j);
+            if (q.inside(a.h0, a.w0)) {
+                const long i = q.at(a.w0);
                 o_plane[i] = -1; o_w[i] = 0.0; o_score[i] = 0.0f;
             }
         }
         return;
     }
 
-    for (int i = t; i < hh * hw; i += DENSE_BLOCK) {
-        const int u = x0 - r + i % hw, v = y0 - r + i / hw;
-        s_a[i] = (u >= 0 && u < a.w0 && v >= 0 && v < a.h0) ? a.ref[(long)v * a.w0 + u] : (uint8_t)0;
-    }
+    tile_stage_bytes(L.a, a.ref, a.h0, a.w0, r);
     if (t < 9) { s_AB[t] = a.A[t]; s_AB[9 + t] = a.B[t]; }      // read per plane from LDS: 36 scalar registers less to hold
     __syncthreads();
 
-    const long long n = (long long)side * side;
-    long long sa[PIX], saa[PIX];
-    unsigned outside[PIX];              // 1: the window leaves ref; starts the count of invalid samples (a word, not a bool: see DenseBest)
+    PlaneRef R;
+    plane_ref_sums(L, a.h0, a.w0, r, R);
     DenseBest best[PIX];
 #pragma unroll
-    for (int j = 0; j < PIX; ++j) {
-        const int p = t + DENSE_BLOCK * j, c = p & (TW - 1), row = p / TW, u = x0 + c, v = y0 + row;
-        outside[j] = (u >= r && u < a.w0 - r && v >= r && v < a.h0 - r) ? 0u : 1u;
-        dense_best_init(best[j]);
-        long long s1 = 0, s2 = 0;
-        if (!outside[j])
-            for (int dy = 0; dy < side; ++dy)
-                for (int dx = 0; dx < side; ++dx) {
-                    const int av = s_a[(row + dy) * hw + c + dx];
-                    s1 += av; s2 += av * av;
-                }
-        sa[j] = s1; saa[j] = s2;
-    }
+    for (int j = 0; j < PIX; ++j) dense_best_init(best[j]);
 
     for (int k = 0; k < a.D; ++k) {
         double H[9];
         dense_plane(s_AB, s_AB + 9, a.w_first, a.w_step, k, H);
-        // (A) the samples of tile + halo
-        for (int i = t; i < hh * hw; i += DENSE_BLOCK) {
-            const int u = x0 - r + i % hw, v = y0 - r + i / hw;
-            int b = 0;
-            const bool ok = u >= 0 && u < a.w0 && v >= 0 && v < a.h0 && dense_sample(a.src, a.h1, a.w1, H, u, v, b);
-            s_b[i] = ok ? (unsigned)b : INV_BIT;
-        }
-        __syncthreads();
-        // (B) rows: 2 r + 1 columns
-        for (int i = t; i < hh * TW; i += DENSE_BLOCK) {
-            const int c = i & (TW - 1), row = i / TW;
-            unsigned sb = 0, sab = 0, inv = 0;
-            unsigned long long sbb = 0;
-            for (int dx = 0; dx < side; ++dx) {
-                const unsigned q = s_b[row * hw + c + dx];
-                const unsigned b = q & ~INV_BIT;
-                inv += q >> 31;
-                sb += b; sab += b * s_a[row * hw + c + dx]; sbb += (unsigned long long)b * b;
-            }
-            s_bb[i] = sbb;
-            s_px[i] = make_uint2(sb | (inv << 22), sab);
-        }
-        __syncthreads();
-        // (C) columns: 2 r + 1 rows of partials, the score, the running best
-#pragma unroll
-        for (int j = 0; j < PIX; ++j) {
-            const int p = t + DENSE_BLOCK * j, c = p & (TW - 1), row = p / TW;
-            long long sb = 0, sbb = 0, sab = 0;
-            unsigned inv = outside[j];
-            for (int dy = 0; dy < side; ++dy) {
-                const uint2 q = s_px[(row + dy) * TW + c];
-                sb += q.x & ((1u << 22) - 1); inv += q.x >> 22; sab += q.y;
-                sbb += (long long)s_bb[(row + dy) * TW + c];
-            }
-            double s = 0.0;
-            const bool valid = inv == 0 && dense_score(n, sa[j], saa[j], sb, sbb, sab, a.min_var, s);
-            dense_best_step(best[j], k, valid, s);
-        }
-        // the next plane's (A) writes s_b only, which (B) has finished reading; its barrier orders (C) before the next (B)
+        // the score of plane k at every pixel, and the running best of this thread's pixels
+        plane_scores(L, R, a.src, a.h0, a.w0, a.h1, a.w1, r, a.min_var, H,
+                     [&](int j, const TilePixel&, bool valid, double s) { dense_best_step(best[j], k, valid, s); });
     }
 
 #pragma unroll
     for (int j = 0; j < PIX; ++j) {
-        const int p = t + DENSE_BLOCK * j, u = x0 + (p & (TW - 1)), v = y0 + p / TW;
-        if (u < a.w0 && v < a.h0) {
-            const long i = (long)v * a.w0 + u;
+        const TilePixel q = tile_pixel(j);
+        if (q.inside(a.h0, a.w0)) {
+            const long i = q.at(a.w0);
             int16_t plane; double w; float score;
             dense_best_finish(best[j], a.D, a.w_first, a.w_step, a.min_score, plane, w, score);
             o_plane[i] = plane; o_w[i] = w; o_score[i] = score;
@@ -187,13 +122,6 @@ struct DenseCloudScan {
     }
 };
 
-bool finite_all(const double* p, int n) {
-    for (int i = 0; i < n; ++i)
-        if (!std::isfinite(p[i])) return false;
-    return true;
-}
-bool bad_side(int v) { return v < 1 || v > DENSE_MAX_SIDE; }
-
 }  // namespace
 }  // namespace im
 
@@ -217,8 +145,8 @@ int im_dense_sweep(im_ctx* ctx, const uint8_t* d_ref, int h0, int w0, const uint
     if (min_var > (1LL << 26)) return ctx->fail(DENSE_REFUSED, "im_dense_sweep: min_var must be at most 2^26");
     hipStream_t s = (hipStream_t)stream;
     DenseSweepArgs a{d_ref, d_src, h0, w0, h1, w1, D, r, {}, {}, w_first, w_step, min_score, min_var, d_plane, d_w, d_score};
-    for (int i = 0; i < 9; ++i) { a.A[i] = h_A[i]; a.B[i] = h_B[i]; }
-    IM_LAUNCH(ctx, "dense_sweep", s, launch(dense_sweep_kernel, dim3((unsigned)blocks_of(w0, TW), (unsigned)blocks_of(h0, TH)), DENSE_BLOCK, 0, s, a));
+    copy_matrices(h_A, h_B, a.A, a.B);
+    IM_LAUNCH(ctx, "dense_sweep", s, launch(dense_sweep_kernel, dim3((unsigned)blocks_of(w0, TW), (unsigned)blocks_of(h0, TH)), TILE_BLOCK, 0, s, a));
     IM_GUARD_CHECK(ctx, s, "im_dense_sweep");
     return 0;
 }

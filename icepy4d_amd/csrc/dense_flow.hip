@@ -3,8 +3,9 @@
 // each epoch's own depth map and pose. The reference has no such step: every quantity has a definition of this project's own
 // (flow_pixel.h) and is pinned bit for bit against tests/flow_oracle.py. Parity with any image-correlation package is unpinned.
 //
-//   flow_match_kernel   one block of 256 threads per 64 x 16 tile of pixels of a (the sweep's block). Staged in LDS once: the bytes of the tile
-//                       of a with its halo of r, the bytes of the region of b that the tile's candidates read (the tile moved by the prior,
+//   flow_match_kernel   one block of 256 threads per 64 x 16 tile of pixels of a (the sweep's block: the tile, the map from a thread to its
+//                       pixels and the staging loop are dense_tile.h's; the score and the window sums dense_pixel.h's). Staged in LDS once:
+//                       the bytes of the tile of a with its halo of r, the bytes of the region of b that the tile's candidates read (the tile moved by the prior,
 //                       with a halo of r + S), and for every position of b at which a candidate's window can be centred its sum and sum
 //                       of squares (or a mark that the window leaves b). A pixel's own sums of a live in registers. Then, per
 //                       candidate (dx, dy): (B) the rows of a * b are box-summed over 2 r + 1 columns into 4-byte partials, rows of 64
@@ -17,15 +18,13 @@
 #include "common.h"
 #include "ctx.h"
 #include "flow_pixel.h"
+#include "dense_tile.h"
+#include "dense_host.h"
 
 namespace im {
 namespace {
 
-constexpr int FLOW_REFUSED = -83;
-constexpr int TW = DENSE_TILE_W, TH = DENSE_TILE_H, FLOW_BLOCK = 256;
-constexpr int PIX = TW * TH / FLOW_BLOCK;                                         // pixels of the tile per thread
 constexpr unsigned NO_WINDOW = 0xffffffffu;                                       // s_sb.x of a position whose window leaves b
-static_assert(TW == 64 && TW * TH % FLOW_BLOCK == 0, "a row of partials is one entry per lane; whole rounds of the block cover the tile");
 // a row partial is the sum of 31 products of two bytes at the most
 static_assert(31LL * 255 * 255 < (1LL << 32), "the row partials");
 
@@ -52,7 +51,7 @@ struct FlowMatchArgs {
     double* du; double* dv; float* score; uint8_t* valid;
 };
 
-__global__ __launch_bounds__(FLOW_BLOCK) void flow_match_kernel(FlowMatchArgs a) {
+__global__ __launch_bounds__(TILE_BLOCK) void flow_match_kernel(FlowMatchArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     const int t = threadIdx.x, r = a.r, S = a.S, side = 2 * r + 1;
     const FlowLds L(r, S);
@@ -60,15 +59,14 @@ __global__ __launch_bounds__(FLOW_BLOCK) void flow_match_kernel(FlowMatchArgs a)
     uint8_t* const s_b = lds + L.b;
     uint2* const s_sb = reinterpret_cast<uint2*>(lds + L.sb);
     unsigned* const s_row = reinterpret_cast<unsigned*>(lds + L.row);
-    const int x0 = blockIdx.x * TW, y0 = blockIdx.y * TH;
+    const int x0 = tile_x0(), y0 = tile_y0();
     const int bx0 = x0 + a.pu - S - r, by0 = y0 + a.pv - S - r;                    // the first byte of the staged region of b
 
-    // pixels of this thread: p = t + 256 j -> column p % 64 (one per lane), row p / 64
     unsigned todo = 0;                      // bit j: pixel j lies in the image, is asked for and has its window inside a
 #pragma unroll
     for (int j = 0; j < PIX; ++j) {
-        const int p = t + FLOW_BLOCK * j, u = x0 + (p & (TW - 1)), v = y0 + p / TW;
-        if (u < a.w && v < a.h && (a.ask == nullptr || a.ask[(long)v * a.w + u] != 0) && flow_inside(u, v, r, a.h, a.w)) todo |= 1u << j;
+        const TilePixel q = tile_pixel(j);
+        if (q.inside(a.h, a.w) && (a.ask == nullptr || a.ask[q.at(a.w)] != 0) && window_inside(q.u, q.v, r, a.h, a.w)) todo |= 1u << j;
     }
     // no candidate of any pixel of the tile has its window inside b: the centres x0 + pu - S .. x0 + pu + S + 63 miss r .. w - 1 - r (or y)
     const bool some_b = x0 + a.pu + S + TW > r && x0 + a.pu - S < a.w - r && y0 + a.pv + S + TH > r && y0 + a.pv - S < a.h - r;
@@ -76,35 +74,29 @@ __global__ __launch_bounds__(FLOW_BLOCK) void flow_match_kernel(FlowMatchArgs a)
     if (!work) {                            // nothing asked for (or nothing that can score): zeros, at once
 #pragma unroll
         for (int j = 0; j < PIX; ++j) {
-            const int p = t + FLOW_BLOCK * j, u = x0 + (p & (TW - 1)), v = y0 + p / TW;
-            if (u < a.w && v < a.h) {
-                const long i = (long)v * a.w + u;
+            const TilePixel q = tile_pixel(j);
+            if (q.inside(a.h, a.w)) {
+                const long i = q.at(a.w);
                 a.du[i] = 0.0; a.dv[i] = 0.0; a.score[i] = 0.0f; a.valid[i] = 0;
             }
         }
         return;
     }
 
-    for (int i = t; i < L.ah * L.aw; i += FLOW_BLOCK) {
-        const int u = x0 - r + i % L.aw, v = y0 - r + i / L.aw;
-        s_a[i] = (u >= 0 && u < a.w && v >= 0 && v < a.h) ? a.a[(long)v * a.w + u] : (uint8_t)0;
-    }
-    for (int i = t; i < L.bh * L.bw; i += FLOW_BLOCK) {
-        const int u = bx0 + i % L.bw, v = by0 + i / L.bw;
-        s_b[i] = (u >= 0 && u < a.w && v >= 0 && v < a.h) ? a.b[(long)v * a.w + u] : (uint8_t)0;
-    }
+    tile_stage_bytes(s_a, a.a, a.h, a.w, r);
+    tile_stage(bx0, by0, L.bw, L.bh, a.h, a.w, [&](int i, bool inside, long g, int, int) { s_b[i] = inside ? a.b[g] : (uint8_t)0; });
     __syncthreads();
-    // the sums of b at every position a candidate can be centred on: position (px, py) is byte (px + r, py + r) of the region
-    for (int i = t; i < L.ph * L.pw; i += FLOW_BLOCK) {
-        const int px = i % L.pw, py = i / L.pw;
+    // the sums of b at every position a candidate can be centred on: position (px, py) is byte (px + r, py + r) of the region, which is
+    // byte (u - bx0, v - by0) for the position's place (u, v) in b
+    tile_stage(bx0 + r, by0 + r, L.pw, L.ph, a.h, a.w, [&](int i, bool, long, int u, int v) {
         uint2 q = make_uint2(NO_WINDOW, 0u);
-        if (flow_inside(bx0 + r + px, by0 + r + py, r, a.h, a.w)) {
+        if (window_inside(u, v, r, a.h, a.w)) {
             long long s1, s2;
-            flow_window_sums(s_b + (py + r) * L.bw + px + r, L.bw, r, s1, s2);
+            dense_window_sums(s_b + (v - by0) * L.bw + (u - bx0), L.bw, r, s1, s2);
             q = make_uint2((unsigned)s1, (unsigned)s2);
         }
         s_sb[i] = q;
-    }
+    });
 
     const long long n = (long long)side * side;
     unsigned sa[PIX], saa[PIX];
@@ -112,9 +104,9 @@ __global__ __launch_bounds__(FLOW_BLOCK) void flow_match_kernel(FlowMatchArgs a)
     int best[PIX];                          // (dy + S) << 8 | (dx + S) of the best, -1: none yet
 #pragma unroll
     for (int j = 0; j < PIX; ++j) {
-        const int p = t + FLOW_BLOCK * j, c = p & (TW - 1), row = p / TW;
+        const TilePixel q = tile_pixel(j);
         long long s1 = 0, s2 = 0;
-        if (todo >> j & 1) flow_window_sums(s_a + (row + r) * L.aw + c + r, L.aw, r, s1, s2);
+        if (todo >> j & 1) dense_window_sums(s_a + (q.row + r) * L.aw + q.c + r, L.aw, r, s1, s2);
         sa[j] = (unsigned)s1; saa[j] = (unsigned)s2;
         s0[j] = 0.0; best[j] = -1;
     }
@@ -124,7 +116,7 @@ __global__ __launch_bounds__(FLOW_BLOCK) void flow_match_kernel(FlowMatchArgs a)
     for (int k = 0; k < span * span; ++k) {
         const int dx = k % span - S, dy = k / span - S;
         // (B) rows of a * b: partial (row, c) sums a[row][c .. c + 2 r] * b[row + S + dy][c + S + dx ..] in the staged arrays
-        for (int i = t; i < L.ah * TW; i += FLOW_BLOCK) {
+        for (int i = t; i < L.ah * TW; i += TILE_BLOCK) {
             const int c = i & (TW - 1), row = i / TW;
             const uint8_t* pa = s_a + row * L.aw + c;
             const uint8_t* pb = s_b + (row + S + dy) * L.bw + c + S + dx;
@@ -137,13 +129,13 @@ __global__ __launch_bounds__(FLOW_BLOCK) void flow_match_kernel(FlowMatchArgs a)
 #pragma unroll
         for (int j = 0; j < PIX; ++j) {
             if (!(todo >> j & 1)) continue;
-            const int p = t + FLOW_BLOCK * j, c = p & (TW - 1), row = p / TW;
-            const uint2 q = s_sb[(row + S + dy) * L.pw + c + S + dx];
+            const TilePixel px = tile_pixel(j);
+            const uint2 q = s_sb[(px.row + S + dy) * L.pw + px.c + S + dx];
             if (q.x == NO_WINDOW) continue;
             unsigned ab = 0;
-            for (int e = 0; e < side; ++e) ab += s_row[(row + e) * TW + c];
+            for (int e = 0; e < side; ++e) ab += s_row[(px.row + e) * TW + px.c];
             double s;
-            if (!flow_score(n, sa[j], saa[j], q.x, q.y, ab, a.min_var, s)) continue;
+            if (!dense_score(n, sa[j], saa[j], q.x, q.y, ab, a.min_var, s, 1)) continue;
             const bool take = flow_better(best[j] >= 0, s, dx, dy, s0[j], (best[j] & 255) - S, (best[j] >> 8) - S);      // -1 decodes to anything: not read
             s0[j] = take ? s : s0[j];
             best[j] = take ? ((dy + S) << 8 | (dx + S)) : best[j];
@@ -154,8 +146,9 @@ __global__ __launch_bounds__(FLOW_BLOCK) void flow_match_kernel(FlowMatchArgs a)
     // the second phase: the four neighbours of each pixel's best, directly from the staged bytes
 #pragma unroll
     for (int j = 0; j < PIX; ++j) {
-        const int p = t + FLOW_BLOCK * j, c = p & (TW - 1), row = p / TW, u = x0 + c, v = y0 + row;
-        if (u >= a.w || v >= a.h) continue;
+        const TilePixel px = tile_pixel(j);
+        const int c = px.c, row = px.row;
+        if (!px.inside(a.h, a.w)) continue;
         double du = 0.0, dv = 0.0;
         float score = 0.0f;
         bool ok = false;
@@ -168,7 +161,7 @@ __global__ __launch_bounds__(FLOW_BLOCK) void flow_match_kernel(FlowMatchArgs a)
                 const uint2 q = s_sb[(row + S + ey) * L.pw + c + S + ex];
                 if (q.x == NO_WINDOW) return false;
                 const long long ab = flow_window_ab(ca, L.aw, s_b + (row + S + ey + r) * L.bw + c + S + ex + r, L.bw, r);
-                return flow_score(n, sa[j], saa[j], q.x, q.y, ab, a.min_var, s);
+                return dense_score(n, sa[j], saa[j], q.x, q.y, ab, a.min_var, s, 1);
             };
             double sm, sp;
             bool both = dx - 1 >= -S && dx + 1 <= S;
@@ -182,7 +175,7 @@ __global__ __launch_bounds__(FLOW_BLOCK) void flow_match_kernel(FlowMatchArgs a)
             score = (float)s0[j];
             ok = true;
         }
-        const long i = (long)v * a.w + u;
+        const long i = px.at(a.w);
         a.du[i] = du; a.dv[i] = dv; a.score[i] = score; a.valid[i] = ok ? 1 : 0;
     }
 }
@@ -223,9 +216,6 @@ __global__ __launch_bounds__(256) void flow_lift_kernel(FlowLiftArgs a) {
     a.ok[i] = ok ? 1 : 0;
 }
 
-bool bad_side(int v) { return v < 1 || v > DENSE_MAX_SIDE; }
-bool positive(double v) { return std::isfinite(v) && v > 0.0; }
-
 }  // namespace
 }  // namespace im
 
@@ -236,18 +226,18 @@ extern "C" {
 int im_flow_match(im_ctx* ctx, const uint8_t* d_a, const uint8_t* d_b, int h, int w, int r, int search, int prior_u, int prior_v, long long min_var,
                   double min_score, const uint8_t* d_ask, double* d_du, double* d_dv, float* d_score, uint8_t* d_valid, void* stream) {
     IM_CHECK_CTX(ctx);
-    if (!d_a || !d_b || !d_du || !d_dv || !d_score || !d_valid) return ctx->fail(FLOW_REFUSED, "im_flow_match: null pointer");
-    if (bad_side(h) || bad_side(w)) return ctx->fail(FLOW_REFUSED, "im_flow_match: h and w must be 1..16384");
-    if (r < 1 || r > FLOW_MAX_RADIUS) return ctx->fail(FLOW_REFUSED, "im_flow_match: r must be 1..15");
-    if (search < 0 || search > FLOW_MAX_SEARCH) return ctx->fail(FLOW_REFUSED, "im_flow_match: the search half-width must be 0..16");
+    if (!d_a || !d_b || !d_du || !d_dv || !d_score || !d_valid) return ctx->fail(DENSE_REFUSED, "im_flow_match: null pointer");
+    if (bad_side(h) || bad_side(w)) return ctx->fail(DENSE_REFUSED, "im_flow_match: h and w must be 1..16384");
+    if (r < 1 || r > FLOW_MAX_RADIUS) return ctx->fail(DENSE_REFUSED, "im_flow_match: r must be 1..15");
+    if (search < 0 || search > FLOW_MAX_SEARCH) return ctx->fail(DENSE_REFUSED, "im_flow_match: the search half-width must be 0..16");
     if (prior_u < -FLOW_MAX_PRIOR || prior_u > FLOW_MAX_PRIOR || prior_v < -FLOW_MAX_PRIOR || prior_v > FLOW_MAX_PRIOR)
-        return ctx->fail(FLOW_REFUSED, "im_flow_match: the prior must be -4096..4096");
-    if (min_var < 0 || min_var > FLOW_MAX_MIN_VAR) return ctx->fail(FLOW_REFUSED, "im_flow_match: min_var must be 0..2^26");
-    if (!std::isfinite(min_score)) return ctx->fail(FLOW_REFUSED, "im_flow_match: min_score must be finite");
+        return ctx->fail(DENSE_REFUSED, "im_flow_match: the prior must be -4096..4096");
+    if (min_var < 0 || min_var > FLOW_MAX_MIN_VAR) return ctx->fail(DENSE_REFUSED, "im_flow_match: min_var must be 0..2^26");
+    if (!std::isfinite(min_score)) return ctx->fail(DENSE_REFUSED, "im_flow_match: min_score must be finite");
     hipStream_t s = (hipStream_t)stream;
     FlowMatchArgs a{d_a, d_b, d_ask, h, w, r, search, prior_u, prior_v, min_var, min_score, d_du, d_dv, d_score, d_valid};
     const FlowLds L(r, search);             // at most 62800 bytes: below the 64 KiB a launch may ask for without an attribute
-    IM_LAUNCH(ctx, "flow_match", s, launch(flow_match_kernel, dim3((unsigned)blocks_of(w, TW), (unsigned)blocks_of(h, TH)), FLOW_BLOCK, L.bytes, s, a));
+    IM_LAUNCH(ctx, "flow_match", s, launch(flow_match_kernel, dim3((unsigned)blocks_of(w, TW), (unsigned)blocks_of(h, TH)), TILE_BLOCK, L.bytes, s, a));
     IM_GUARD_CHECK(ctx, s, "im_flow_match");
     return 0;
 }
@@ -255,9 +245,9 @@ int im_flow_match(im_ctx* ctx, const uint8_t* d_a, const uint8_t* d_b, int h, in
 int im_flow_check(im_ctx* ctx, const double* d_du, const double* d_dv, const uint8_t* d_valid, const double* d_du_b, const double* d_dv_b,
                   const uint8_t* d_valid_b, int h, int w, double tol, uint8_t* d_keep, void* stream) {
     IM_CHECK_CTX(ctx);
-    if (!d_du || !d_dv || !d_valid || !d_du_b || !d_dv_b || !d_valid_b || !d_keep) return ctx->fail(FLOW_REFUSED, "im_flow_check: null pointer");
-    if (bad_side(h) || bad_side(w)) return ctx->fail(FLOW_REFUSED, "im_flow_check: h and w must be 1..16384");
-    if (!positive(tol)) return ctx->fail(FLOW_REFUSED, "im_flow_check: tol must be finite and > 0");
+    if (!d_du || !d_dv || !d_valid || !d_du_b || !d_dv_b || !d_valid_b || !d_keep) return ctx->fail(DENSE_REFUSED, "im_flow_check: null pointer");
+    if (bad_side(h) || bad_side(w)) return ctx->fail(DENSE_REFUSED, "im_flow_check: h and w must be 1..16384");
+    if (!positive(tol)) return ctx->fail(DENSE_REFUSED, "im_flow_check: tol must be finite and > 0");
     hipStream_t s = (hipStream_t)stream;
     FlowCheckArgs a{d_du, d_dv, d_valid, d_du_b, d_dv_b, d_valid_b, h, w, tol, d_keep};
     IM_LAUNCH(ctx, "flow_check", s, launch(flow_check_kernel, blocks_of((long long)h * w, 256), 256, 0, s, a));
@@ -270,10 +260,10 @@ int im_flow_lift(im_ctx* ctx, const double* d_du, const double* d_dv, const uint
                  int wb, const double* h_cam_b, double w_step_b, double max_diff, double* d_P, double* d_D, uint8_t* d_ok, void* stream) {
     IM_CHECK_CTX(ctx);
     if (!d_du || !d_dv || !d_valid || !d_keep || !d_plane_a || !d_w_a || !h_cam_a || !d_plane_b || !d_w_b || !d_keep_b || !h_cam_b || !d_P || !d_D || !d_ok)
-        return ctx->fail(FLOW_REFUSED, "im_flow_lift: null pointer");
-    if (bad_side(h) || bad_side(w) || bad_side(hb) || bad_side(wb)) return ctx->fail(FLOW_REFUSED, "im_flow_lift: h and w must be 1..16384");
-    if (!positive(max_diff)) return ctx->fail(FLOW_REFUSED, "im_flow_lift: max_diff must be finite and > 0");
-    if (!positive(fabs(w_step_b))) return ctx->fail(FLOW_REFUSED, "im_flow_lift: w_step must be finite and not zero");
+        return ctx->fail(DENSE_REFUSED, "im_flow_lift: null pointer");
+    if (bad_side(h) || bad_side(w) || bad_side(hb) || bad_side(wb)) return ctx->fail(DENSE_REFUSED, "im_flow_lift: h and w must be 1..16384");
+    if (!positive(max_diff)) return ctx->fail(DENSE_REFUSED, "im_flow_lift: max_diff must be finite and > 0");
+    if (!positive(fabs(w_step_b))) return ctx->fail(DENSE_REFUSED, "im_flow_lift: w_step must be finite and not zero");
     hipStream_t s = (hipStream_t)stream;
     FlowLiftArgs a{d_du, d_dv, d_valid, d_keep, d_plane_a, d_w_a, h, w, d_plane_b, d_w_b, d_keep_b, hb, wb, {}, {}, max_diff * fabs(w_step_b), d_P, d_D, d_ok};
     __builtin_memcpy(&a.ca, h_cam_a, sizeof(DenseCam));

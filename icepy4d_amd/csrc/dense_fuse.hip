@@ -14,11 +14,12 @@
 #include "common.h"
 #include "ctx.h"
 #include "fuse_pixel.h"
+#include "dense_host.h"
 
 namespace im {
 namespace {
 
-constexpr int FUSE_REFUSED = -83;
+static_assert(FUSE_MAX_SIDE == DENSE_MAX_SIDE, "bad_side of dense_host.h is the limit of a fused map's side");
 constexpr int FUSE_BLOCK = 256;
 
 struct FuseLinkArgs {
@@ -51,7 +52,6 @@ __global__ __launch_bounds__(FUSE_BLOCK) void fuse_rest_kernel(FuseRestArgs a) {
     a.rest[i] = fuse_rest(a.P, (int)(i % a.wb), (int)(i / a.wb), a.keep_b[i], a.claimed[i], a.w_b[i], a.keep_a, a.w_a, a.ha, a.wa, a.tol) ? 1 : 0;
 }
 
-bool bad_side(int v) { return v < 1 || v > FUSE_MAX_SIDE; }
 bool among(const void* out, std::initializer_list<const void*> ins) {
     for (const void* p : ins)
         if (p == out) return true;
@@ -70,13 +70,13 @@ int im_dense_fuse_link(im_ctx* ctx, const uint8_t* d_keep_a, const double* d_w_a
                        float* d_score_out, uint8_t* d_views, uint8_t* d_claimed, void* stream) {
     IM_CHECK_CTX(ctx);
     if (!d_keep_a || !d_w_a || !d_score_a || !d_keep_b || !d_w_b || !d_score_b || !h_pose || !d_link || !d_w_out || !d_score_out || !d_views || !d_claimed)
-        return ctx->fail(FUSE_REFUSED, "im_dense_fuse_link: null pointer");
-    if (bad_side(ha) || bad_side(wa) || bad_side(hb) || bad_side(wb)) return ctx->fail(FUSE_REFUSED, "im_dense_fuse_link: h and w must be 1..16384");
-    if (!(tol >= 0.0)) return ctx->fail(FUSE_REFUSED, "im_dense_fuse_link: the tolerance must not be negative");
+        return ctx->fail(DENSE_REFUSED, "im_dense_fuse_link: null pointer");
+    if (bad_side(ha) || bad_side(wa) || bad_side(hb) || bad_side(wb)) return ctx->fail(DENSE_REFUSED, "im_dense_fuse_link: h and w must be 1..16384");
+    if (!(tol >= 0.0)) return ctx->fail(DENSE_REFUSED, "im_dense_fuse_link: the tolerance must not be negative");
     // another thread reads what a thread writes if an output is an input: the result would depend on the order of the threads
     for (const void* out : {(const void*)d_link, (const void*)d_w_out, (const void*)d_score_out, (const void*)d_views, (const void*)d_claimed})
         if (among(out, {d_keep_a, d_w_a, d_score_a, d_keep_b, d_w_b, d_score_b}))
-            return ctx->fail(FUSE_REFUSED, "im_dense_fuse_link: the outputs must not be the inputs");
+            return ctx->fail(DENSE_REFUSED, "im_dense_fuse_link: the outputs must not be the inputs");
     hipStream_t s = (hipStream_t)stream;
     FuseLinkArgs a{d_keep_a, d_w_a, d_score_a, ha, wa, d_keep_b, d_w_b, d_score_b, hb, wb, {}, tol, d_link, d_w_out, d_score_out, d_views, d_claimed};
     __builtin_memcpy(&a.P, h_pose, sizeof(DensePose));
@@ -89,10 +89,10 @@ int im_dense_fuse_link(im_ctx* ctx, const uint8_t* d_keep_a, const double* d_w_a
 int im_dense_fuse_rest(im_ctx* ctx, const uint8_t* d_keep_b, const double* d_w_b, int hb, int wb, const uint8_t* d_keep_a, const double* d_w_a, int ha,
                        int wa, const double* h_pose_ba, double tol_a, const uint8_t* d_claimed, uint8_t* d_rest, void* stream) {
     IM_CHECK_CTX(ctx);
-    if (!d_keep_b || !d_w_b || !d_keep_a || !d_w_a || !h_pose_ba || !d_claimed || !d_rest) return ctx->fail(FUSE_REFUSED, "im_dense_fuse_rest: null pointer");
-    if (bad_side(ha) || bad_side(wa) || bad_side(hb) || bad_side(wb)) return ctx->fail(FUSE_REFUSED, "im_dense_fuse_rest: h and w must be 1..16384");
-    if (!(tol_a >= 0.0)) return ctx->fail(FUSE_REFUSED, "im_dense_fuse_rest: the tolerance must not be negative");
-    if (among(d_rest, {d_keep_b, d_w_b, d_keep_a, d_w_a, d_claimed})) return ctx->fail(FUSE_REFUSED, "im_dense_fuse_rest: the output must not be an input");
+    if (!d_keep_b || !d_w_b || !d_keep_a || !d_w_a || !h_pose_ba || !d_claimed || !d_rest) return ctx->fail(DENSE_REFUSED, "im_dense_fuse_rest: null pointer");
+    if (bad_side(ha) || bad_side(wa) || bad_side(hb) || bad_side(wb)) return ctx->fail(DENSE_REFUSED, "im_dense_fuse_rest: h and w must be 1..16384");
+    if (!(tol_a >= 0.0)) return ctx->fail(DENSE_REFUSED, "im_dense_fuse_rest: the tolerance must not be negative");
+    if (among(d_rest, {d_keep_b, d_w_b, d_keep_a, d_w_a, d_claimed})) return ctx->fail(DENSE_REFUSED, "im_dense_fuse_rest: the output must not be an input");
     hipStream_t s = (hipStream_t)stream;
     FuseRestArgs a{d_keep_b, d_w_b, hb, wb, d_keep_a, d_w_a, ha, wa, {}, tol_a, d_claimed, d_rest};
     __builtin_memcpy(&a.P, h_pose_ba, sizeof(DensePose));

@@ -6,6 +6,9 @@
 // an integer, so the kernels may sum in any order; what is float64 uses only + - * / sqrt with contraction off, in the association
 // written here. A header of its own without the context or any launch code, like warp_pixel.h (whose fix_coord rounds the coordinates):
 // tests/dense_host_harness.cpp compiles this very text behind a stub <hip/hip_runtime.h>.
+// The later dense stages take from here what they share with the sweep, defined once: the window test and the window sums, the score (with
+// the scale of the second window's samples as a parameter), the parabola, the update of the running best and the back-projection
+// (refine_pixel.h, flow_pixel.h, fuse_pixel.h). What the kernels share beyond arithmetic is dense_tile.h's, the host checks dense_host.h's.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -50,16 +53,44 @@ __device__ __forceinline__ bool dense_sample(const uint8_t* src, int h1, int w1,
     return true;
 }
 
-// The score of a window of n = (2 r + 1)^2 samples from its integer sums. false: too little texture (or none: a zero variance would
-// divide by zero, so it is invalid whatever min_var is). n sbb <= 225^2 2^36 < 2^52: every product fits an int64.
+// does the window of radius r centred on (x, y) lie inside an image [h][w]?
+__device__ __forceinline__ bool window_inside(int x, int y, int r, int h, int w) { return x >= r && x < w - r && y >= r && y < h - r; }
+
+// Sum and sum of squares of the (2 r + 1)^2 byte window centred on *c (rows of `stride` bytes: an image itself, or a staged tile). Up to
+// r = 15 (flow_pixel.h) 961 * 255^2 < 2^26, so 32 bits would hold either sum; the accumulators are int64 all the same, because with uint32
+// the compiler gathers four bytes into a word for a dot product, and that form measured slower on the MI355X in the sweep and the costs
+// (r = 3) and in the flow match (r = 7 and 15) alike.
+__device__ __forceinline__ void dense_window_sums(const uint8_t* c, int stride, int r, long long& s1, long long& s2) {
+    s1 = s2 = 0;
+    for (int dy = -r; dy <= r; ++dy)
+        for (int dx = -r; dx <= r; ++dx) {
+            const long long p = c[dy * stride + dx];
+            s1 += p; s2 += p * p;
+        }
+}
+
+// The score of two windows of n = (2 r + 1)^2 samples each from their integer sums. false: too little texture in either window (or none: a
+// zero variance would divide by zero, so it is invalid whatever min_var is). scale_b, the last argument, is the scale of the second window's
+// samples against bytes, which its variance threshold carries: DENSE_WARPED for warped samples (sums of weights adding up to 1024, so 2^20
+// in a variance), which is what the sweep's callers get by leaving it out, and 1 for bytes. n sbb <= 225^2 2^36 < 2^52 (warped, r <= 7) and
+// 961^2 2^26 < 2^46 (bytes, r <= 15): every product fits an int64.
+constexpr long long DENSE_WARPED = 1LL << 20;
 __device__ __forceinline__ bool dense_score(long long n, long long sa, long long saa, long long sb, long long sbb, long long sab, long long min_var,
-                                            double& s) {
+                                            double& s, long long scale_b = DENSE_WARPED) {
 #pragma clang fp contract(off)
     const long long VA = n * saa - sa * sa, VB = n * sbb - sb * sb, C = n * sab - sa * sb;
     s = 0.0;
-    if (VA < n * n * min_var || VB < n * n * min_var * (1LL << 20) || VA <= 0 || VB <= 0) return false;
+    if (VA < n * n * min_var || VB < n * n * min_var * scale_b || VA <= 0 || VB <= 0) return false;
     s = (double)C / sqrt((double)VA * (double)VB);
     return true;
+}
+
+// The sub-step offset of a best score s0 between its two neighbours sm and sp: the vertex of the parabola through the three where it is a
+// maximum (a negative denominator), else 0.
+__device__ __forceinline__ double parabola_offset(double sm, double s0, double sp) {
+#pragma clang fp contract(off)
+    const double den = (sm - 2.0 * s0) + sp;
+    return den < 0.0 ? (0.5 * (sm - sp)) / den : 0.0;
 }
 
 // The running choice of one pixel over the planes in ascending order: the best valid score, its predecessor and its successor.
@@ -74,9 +105,10 @@ __device__ __forceinline__ void dense_best_init(DenseBest& b) {
     b.k = -1;
     b.flags = 0;
 }
-// plane k scored s (valid) or did not (s is ignored then). A later plane replaces the best only if strictly greater.
-__device__ __forceinline__ void dense_best_step(DenseBest& b, int k, bool valid, double s) {
-    if (valid && (b.k < 0 || s > b.s0)) {
+// Plane k scored s (valid) or did not (s is ignored then): it becomes the best (take), or it is the successor of the best, and either way
+// it is remembered as the predecessor of the next. `take` is the caller's rule; it implies valid.
+__device__ __forceinline__ void dense_best_update(DenseBest& b, int k, bool take, bool valid, double s) {
+    if (take) {
         b.s0 = s; b.k = k;
         b.sm = b.prev; b.sp = 0.0;
         b.flags = (b.flags >> 2) & 1;
@@ -86,17 +118,17 @@ __device__ __forceinline__ void dense_best_step(DenseBest& b, int k, bool valid,
     b.prev = valid ? s : 0.0;
     b.flags = (b.flags & 3) | (valid ? 4 : 0);
 }
+// The sweep's rule: a later plane replaces the best only if strictly greater.
+__device__ __forceinline__ void dense_best_step(DenseBest& b, int k, bool valid, double s) {
+    dense_best_update(b, k, valid && (b.k < 0 || s > b.s0), valid, s);
+}
 // plane = -1, w = 0, score = 0 where no plane scored or the best is below min_score
 __device__ __forceinline__ void dense_best_finish(const DenseBest& b, int D, double w_first, double w_step, double min_score, int16_t& plane,
                                                   double& w, float& score) {
 #pragma clang fp contract(off)
     plane = -1; w = 0.0; score = 0.0f;
     if (b.k < 0 || b.s0 < min_score) return;
-    double off = 0.0;
-    if (b.k >= 1 && b.k <= D - 2 && (b.flags & 3) == 3) {
-        const double den = (b.sm - 2.0 * b.s0) + b.sp;
-        if (den < 0.0) off = (0.5 * (b.sm - b.sp)) / den;
-    }
+    const double off = b.k >= 1 && b.k <= D - 2 && (b.flags & 3) == 3 ? parabola_offset(b.sm, b.s0, b.sp) : 0.0;
     plane = (int16_t)b.k;
     w = w_first + ((double)b.k + off) * w_step;
     score = (float)b.s0;
@@ -106,13 +138,15 @@ __device__ __forceinline__ void dense_best_finish(const DenseBest& b, int D, dou
 struct DensePose { double Ki[9], R[9], t[3], K1[9]; };
 static_assert(sizeof(DensePose) == 30 * sizeof(double), "h_pose of im_dense_consistency is 30 doubles");
 
-// X0 = Ki (u, v, 1) / w
-__device__ __forceinline__ void dense_backproject(const double* Ki, int u, int v, double w, double* X) {
+// X0 = Ki (x, y, 1) / w, at a position that need not be a pixel centre (flow_pixel.h), and at pixel (u, v): an int converts exactly
+__device__ __forceinline__ void dense_backproject_at(const double* Ki, double x, double y, double w, double* X) {
 #pragma clang fp contract(off)
-    const double du = (double)u, dv = (double)v;
-    X[0] = ((Ki[0] * du + Ki[1] * dv) + Ki[2]) / w;
-    X[1] = ((Ki[3] * du + Ki[4] * dv) + Ki[5]) / w;
-    X[2] = ((Ki[6] * du + Ki[7] * dv) + Ki[8]) / w;
+    X[0] = ((Ki[0] * x + Ki[1] * y) + Ki[2]) / w;
+    X[1] = ((Ki[3] * x + Ki[4] * y) + Ki[5]) / w;
+    X[2] = ((Ki[6] * x + Ki[7] * y) + Ki[8]) / w;
+}
+__device__ __forceinline__ void dense_backproject(const double* Ki, int u, int v, double w, double* X) {
+    dense_backproject_at(Ki, (double)u, (double)v, w, X);
 }
 
 // Is the depth of kept pixel (u, v) of map 0 (inverse depth w) met by map 1 [h1][w1] (plane1 < 0: dropped)? The nearest pixel of view 1

@@ -4,9 +4,10 @@
 // it is not Metashape's depth filter.
 //
 //   dense_costs_kernel       one block of 256 threads per 64 x 16 tile of ref pixels, the plane loop of dense_sweep_kernel (samples of tile
-//                            + halo into LDS, row partials, column sums, score); each score is quantised, four planes are packed into a word
-//                            per pixel and sixteen planes are staged in LDS, then stored as runs: whole words where D is a multiple of four
-//                            (a pixel's sixteen bytes from four neighbouring lanes), bytes in plane order otherwise.
+//                            + halo into LDS, row partials, column sums, score: plane_scores of dense_tile.h, defined once for the two
+//                            kernels); each score is quantised, four planes are packed into a word per pixel and sixteen planes are
+//                            staged in LDS, then stored as runs: whole words where D is a multiple of four (a pixel's sixteen bytes from
+//                            four neighbouring lanes), bytes in plane order otherwise.
 //   dense_sgm_kernel         one wave per path line (a row, a column, a diagonal or an anti-diagonal), four lines per block. Lane l holds
 //                            L(q, 4 l .. 4 l + 3) in registers; planes at or beyond D hold SGM_FAR, which never wins and is never stored.
 //                            d - 1 and d + 1 across lanes come from __shfl_up / __shfl_down, m from the xor butterfly. The wave walks its
@@ -17,20 +18,14 @@
 // Everything is an integer behind the score: the order of execution does not matter. No atomics. Enqueue only.
 #include "common.h"
 #include "ctx.h"
-#include "dense_pixel.h"
+#include "dense_tile.h"
+#include "dense_host.h"
 #include "sgm_pixel.h"
 
 namespace im {
 namespace {
 
-constexpr int SGM_REFUSED = -83;
-constexpr int TW = DENSE_TILE_W, TH = DENSE_TILE_H, COST_BLOCK = 256;
-constexpr int HW = TW + 2 * DENSE_MAX_RADIUS, HH = TH + 2 * DENSE_MAX_RADIUS;
-constexpr int PIX = TW * TH / COST_BLOCK;
 constexpr int GROUP = 16;                                // planes staged per tile before they are stored
-constexpr unsigned INV_BIT = 1u << 31;
-static_assert(TW == 64 && TW * TH % COST_BLOCK == 0, "a row of partials is one entry per lane; whole rounds of the block cover the tile");
-static_assert(15LL * 261120 < (1LL << 22) && 15LL * 255 * 261120 < (1LL << 31), "the packed row partials");
 static_assert(SGM_MAX_PLANES == 4 * IM_WAVE, "four planes per lane");
 
 struct DenseCostArgs {
@@ -41,113 +36,58 @@ struct DenseCostArgs {
     uint8_t* cost;
 };
 
-__global__ __launch_bounds__(COST_BLOCK) void dense_costs_kernel(DenseCostArgs a) {
-    __shared__ uint8_t s_a[HH * HW];                  // ref bytes of tile + halo (0 outside ref)
-    __shared__ unsigned s_b[HH * HW];                 // the plane's warped values, INV_BIT where invalid
-    __shared__ unsigned long long s_bb[HH * TW];      // row partials: sum b^2
-    __shared__ uint2 s_px[HH * TW];                   //               x = sum b | invalid count << 22, y = sum a b
+__global__ __launch_bounds__(TILE_BLOCK) void dense_costs_kernel(DenseCostArgs a) {
+    __shared__ PlaneLds L;                            // dense_tile.h: ref bytes, the plane's samples, the two rows of partials
     __shared__ double s_AB[20];                       // A, B, w_first and w_step: read per plane from LDS, 40 scalar registers less to hold
     __shared__ unsigned s_c[TW * TH * GROUP / 4];     // GROUP planes of every pixel of the tile, planes contiguous
-    const int t = threadIdx.x, r = a.r, side = 2 * r + 1, D = a.D;
-    const int x0 = blockIdx.x * TW, y0 = blockIdx.y * TH;
-    const int hw = TW + 2 * r, hh = TH + 2 * r;
+    const int t = threadIdx.x, r = a.r, D = a.D;
     uint8_t* const o_cost = a.cost;
 
     // a tile none of whose pixels has its window inside ref: every plane of every pixel is invalid. A row of the tile is one run of bytes
-    const bool any = x0 + TW > r && x0 < a.w0 - r && y0 + TH > r && y0 < a.h0 - r;
-    if (!any) {
-        const int cols = min(TW, a.w0 - x0);
-        for (int row = 0; row < TH && y0 + row < a.h0; ++row) {
-            uint8_t* const run = o_cost + ((size_t)(y0 + row) * a.w0 + x0) * D;
-            for (int i = t; i < cols * D; i += COST_BLOCK) run[i] = (uint8_t)SGM_INVALID;
+    if (!tile_any_window_inside(a.h0, a.w0, r)) {
+        const int cols = min(TW, a.w0 - tile_x0());
+        for (int row = 0; row < TH && tile_y0() + row < a.h0; ++row) {
+            uint8_t* const run = o_cost + ((size_t)(tile_y0() + row) * a.w0 + tile_x0()) * D;
+            for (int i = t; i < cols * D; i += TILE_BLOCK) run[i] = (uint8_t)SGM_INVALID;
         }
         return;
     }
 
-    for (int i = t; i < hh * hw; i += COST_BLOCK) {
-        const int u = x0 - r + i % hw, v = y0 - r + i / hw;
-        s_a[i] = (u >= 0 && u < a.w0 && v >= 0 && v < a.h0) ? a.ref[(long)v * a.w0 + u] : (uint8_t)0;
-    }
+    tile_stage_bytes(L.a, a.ref, a.h0, a.w0, r);
     if (t < 9) { s_AB[t] = a.A[t]; s_AB[9 + t] = a.B[t]; }
     if (t == 9) { s_AB[18] = a.w_first; s_AB[19] = a.w_step; }
     __syncthreads();
 
-    const long long n = (long long)side * side;
-    long long sa[PIX], saa[PIX];
-    unsigned outside[PIX], pack[PIX];
-#pragma unroll
-    for (int j = 0; j < PIX; ++j) {
-        const int p = t + COST_BLOCK * j, c = p & (TW - 1), row = p / TW, u = x0 + c, v = y0 + row;
-        outside[j] = (u >= r && u < a.w0 - r && v >= r && v < a.h0 - r) ? 0u : 1u;
-        pack[j] = 0;
-        long long s1 = 0, s2 = 0;
-        if (!outside[j])
-            for (int dy = 0; dy < side; ++dy)
-                for (int dx = 0; dx < side; ++dx) {
-                    const int av = s_a[(row + dy) * hw + c + dx];
-                    s1 += av; s2 += av * av;
-                }
-        sa[j] = s1; saa[j] = s2;
-    }
+    PlaneRef R;
+    plane_ref_sums(L, a.h0, a.w0, r, R);
+    unsigned pack[PIX] = {};
 
     for (int k = 0; k < D; ++k) {
         double H[9];
         dense_plane(s_AB, s_AB + 9, s_AB[18], s_AB[19], k, H);
-        // (A) the samples of tile + halo
-        for (int i = t; i < hh * hw; i += COST_BLOCK) {
-            const int u = x0 - r + i % hw, v = y0 - r + i / hw;
-            int b = 0;
-            const bool ok = u >= 0 && u < a.w0 && v >= 0 && v < a.h0 && dense_sample(a.src, a.h1, a.w1, H, u, v, b);
-            s_b[i] = ok ? (unsigned)b : INV_BIT;
-        }
-        __syncthreads();
-        // (B) rows: 2 r + 1 columns
-        for (int i = t; i < hh * TW; i += COST_BLOCK) {
-            const int c = i & (TW - 1), row = i / TW;
-            unsigned sb = 0, sab = 0, inv = 0;
-            unsigned long long sbb = 0;
-            for (int dx = 0; dx < side; ++dx) {
-                const unsigned q = s_b[row * hw + c + dx];
-                const unsigned b = q & ~INV_BIT;
-                inv += q >> 31;
-                sb += b; sab += b * s_a[row * hw + c + dx]; sbb += (unsigned long long)b * b;
-            }
-            s_bb[i] = sbb;
-            s_px[i] = make_uint2(sb | (inv << 22), sab);
-        }
-        __syncthreads();
-        // (C) columns: 2 r + 1 rows of partials, the score, its cost into byte k % 4 of the pixel's word
+        // the score of plane k at every pixel, its cost into byte k % 4 of the pixel's word
         const bool word_done = (k & 3) == 3 || k == D - 1;
-#pragma unroll
-        for (int j = 0; j < PIX; ++j) {
-            const int p = t + COST_BLOCK * j, c = p & (TW - 1), row = p / TW;
-            long long sb = 0, sbb = 0, sab = 0;
-            unsigned inv = outside[j];
-            for (int dy = 0; dy < side; ++dy) {
-                const uint2 q = s_px[(row + dy) * TW + c];
-                sb += q.x & ((1u << 22) - 1); inv += q.x >> 22; sab += q.y;
-                sbb += (long long)s_bb[(row + dy) * TW + c];
-            }
-            double s = 0.0;
-            const bool valid = inv == 0 && dense_score(n, sa[j], saa[j], sb, sbb, sab, a.min_var, s);
+        plane_scores(L, R, a.src, a.h0, a.w0, a.h1, a.w1, r, a.min_var, H, [&](int j, const TilePixel& q, bool valid, double s) {
             pack[j] |= (unsigned)sgm_cost(valid, s) << (8 * (k & 3));
-            if (word_done) { s_c[p * (GROUP / 4) + ((k / 4) & (GROUP / 4 - 1))] = pack[j]; pack[j] = 0; }
-        }
+            if (word_done) { s_c[q.p * (GROUP / 4) + ((k / 4) & (GROUP / 4 - 1))] = pack[j]; pack[j] = 0; }
+        });
         // the staged planes k0 .. k of every pixel, as runs. The next write into s_c lies behind the two barriers of a later plane.
         if ((k & (GROUP - 1)) == GROUP - 1 || k == D - 1) {
             __syncthreads();
             const int k0 = k & ~(GROUP - 1), cnt = k - k0 + 1;
             if ((D & 3) == 0 && (reinterpret_cast<unsigned long long>(o_cost) & 3) == 0) {      // whole aligned words
-                for (int i = t; i < TW * TH * (GROUP / 4); i += COST_BLOCK) {
-                    const int p = i / (GROUP / 4), j = i & (GROUP / 4 - 1), u = x0 + (p & (TW - 1)), v = y0 + p / TW;
-                    if (4 * j < cnt && u < a.w0 && v < a.h0)
-                        *reinterpret_cast<unsigned*>(o_cost + ((size_t)v * a.w0 + u) * D + k0 + 4 * j) = s_c[i];
+                for (int i = t; i < TW * TH * (GROUP / 4); i += TILE_BLOCK) {
+                    const TilePixel q(i / (GROUP / 4));
+                    const int j = i & (GROUP / 4 - 1);
+                    if (4 * j < cnt && q.inside(a.h0, a.w0))
+                        *reinterpret_cast<unsigned*>(o_cost + (size_t)q.at(a.w0) * D + k0 + 4 * j) = s_c[i];
                 }
             } else {
-                for (int i = t; i < TW * TH * GROUP; i += COST_BLOCK) {
-                    const int p = i / GROUP, b = i & (GROUP - 1), u = x0 + (p & (TW - 1)), v = y0 + p / TW;
-                    if (b < cnt && u < a.w0 && v < a.h0)
-                        o_cost[((size_t)v * a.w0 + u) * D + k0 + b] = (uint8_t)(s_c[i >> 2] >> (8 * (i & 3)));
+                for (int i = t; i < TW * TH * GROUP; i += TILE_BLOCK) {
+                    const TilePixel q(i / GROUP);
+                    const int b = i & (GROUP - 1);
+                    if (b < cnt && q.inside(a.h0, a.w0))
+                        o_cost[(size_t)q.at(a.w0) * D + k0 + b] = (uint8_t)(s_c[i >> 2] >> (8 * (i & 3)));
                 }
             }
         }
@@ -320,7 +260,6 @@ __global__ __launch_bounds__(CHOOSE_BLOCK) void dense_sgm_choose_kernel(SgmChoos
     a.plane[pix] = plane; a.w[pix] = w; a.score[pix] = score;
 }
 
-bool bad_side(int v) { return v < 1 || v > DENSE_MAX_SIDE; }
 bool bad_planes(int D) { return D < 1 || D > SGM_MAX_PLANES; }
 bool too_large(int h0, int w0, int D) { return (long long)h0 * w0 * D > (1LL << 32); }
 
@@ -336,28 +275,28 @@ int im_dense_sgm_max_planes(void) { return SGM_MAX_PLANES; }
 int im_dense_costs(im_ctx* ctx, const uint8_t* d_ref, int h0, int w0, const uint8_t* d_src, int h1, int w1, const double* h_A, const double* h_B,
                    double w_first, double w_step, int D, int r, long long min_var, uint8_t* d_cost, void* stream) {
     IM_CHECK_CTX(ctx);
-    if (!d_ref || !d_src || !h_A || !h_B || !d_cost) return ctx->fail(SGM_REFUSED, "im_dense_costs: null pointer");
-    if (bad_side(h0) || bad_side(w0) || bad_side(h1) || bad_side(w1)) return ctx->fail(SGM_REFUSED, "im_dense_costs: h and w must be 1..16384");
-    if (bad_planes(D)) return ctx->fail(SGM_REFUSED, "im_dense_costs: D must be 1..256");
-    if (r < 1 || r > DENSE_MAX_RADIUS) return ctx->fail(SGM_REFUSED, "im_dense_costs: r must be 1..7");
-    if (min_var < 0 || min_var > (1LL << 26)) return ctx->fail(SGM_REFUSED, "im_dense_costs: min_var must be 0..2^26");
-    if (too_large(h0, w0, D)) return ctx->fail(SGM_REFUSED, "im_dense_costs: h0 w0 D must be at most 2^32");
+    if (!d_ref || !d_src || !h_A || !h_B || !d_cost) return ctx->fail(DENSE_REFUSED, "im_dense_costs: null pointer");
+    if (bad_side(h0) || bad_side(w0) || bad_side(h1) || bad_side(w1)) return ctx->fail(DENSE_REFUSED, "im_dense_costs: h and w must be 1..16384");
+    if (bad_planes(D)) return ctx->fail(DENSE_REFUSED, "im_dense_costs: D must be 1..256");
+    if (r < 1 || r > DENSE_MAX_RADIUS) return ctx->fail(DENSE_REFUSED, "im_dense_costs: r must be 1..7");
+    if (min_var < 0 || min_var > (1LL << 26)) return ctx->fail(DENSE_REFUSED, "im_dense_costs: min_var must be 0..2^26");
+    if (too_large(h0, w0, D)) return ctx->fail(DENSE_REFUSED, "im_dense_costs: h0 w0 D must be at most 2^32");
     hipStream_t s = (hipStream_t)stream;
     DenseCostArgs a{d_ref, d_src, h0, w0, h1, w1, D, r, {}, {}, w_first, w_step, min_var, d_cost};
-    for (int i = 0; i < 9; ++i) { a.A[i] = h_A[i]; a.B[i] = h_B[i]; }
-    IM_LAUNCH(ctx, "dense_costs", s, launch(dense_costs_kernel, dim3((unsigned)blocks_of(w0, TW), (unsigned)blocks_of(h0, TH)), COST_BLOCK, 0, s, a));
+    copy_matrices(h_A, h_B, a.A, a.B);
+    IM_LAUNCH(ctx, "dense_costs", s, launch(dense_costs_kernel, dim3((unsigned)blocks_of(w0, TW), (unsigned)blocks_of(h0, TH)), TILE_BLOCK, 0, s, a));
     IM_GUARD_CHECK(ctx, s, "im_dense_costs");
     return 0;
 }
 
 int im_dense_sgm(im_ctx* ctx, const uint8_t* d_cost, int h0, int w0, int D, int P1, int P2, int paths, uint16_t* d_sum, void* stream) {
     IM_CHECK_CTX(ctx);
-    if (!d_cost || !d_sum) return ctx->fail(SGM_REFUSED, "im_dense_sgm: null pointer");
-    if (bad_side(h0) || bad_side(w0)) return ctx->fail(SGM_REFUSED, "im_dense_sgm: h and w must be 1..16384");
-    if (bad_planes(D)) return ctx->fail(SGM_REFUSED, "im_dense_sgm: D must be 1..256");
-    if (P1 < 0 || P1 > P2 || P2 > SGM_MAX_PENALTY) return ctx->fail(SGM_REFUSED, "im_dense_sgm: 0 <= P1 <= P2 <= 4095 is expected");
-    if (paths != 4 && paths != 8) return ctx->fail(SGM_REFUSED, "im_dense_sgm: paths must be 4 or 8");
-    if (too_large(h0, w0, D)) return ctx->fail(SGM_REFUSED, "im_dense_sgm: h0 w0 D must be at most 2^32");
+    if (!d_cost || !d_sum) return ctx->fail(DENSE_REFUSED, "im_dense_sgm: null pointer");
+    if (bad_side(h0) || bad_side(w0)) return ctx->fail(DENSE_REFUSED, "im_dense_sgm: h and w must be 1..16384");
+    if (bad_planes(D)) return ctx->fail(DENSE_REFUSED, "im_dense_sgm: D must be 1..256");
+    if (P1 < 0 || P1 > P2 || P2 > SGM_MAX_PENALTY) return ctx->fail(DENSE_REFUSED, "im_dense_sgm: 0 <= P1 <= P2 <= 4095 is expected");
+    if (paths != 4 && paths != 8) return ctx->fail(DENSE_REFUSED, "im_dense_sgm: paths must be 4 or 8");
+    if (too_large(h0, w0, D)) return ctx->fail(DENSE_REFUSED, "im_dense_sgm: h0 w0 D must be at most 2^32");
     hipStream_t s = (hipStream_t)stream;
     // one launch per pair of opposite directions; the stream orders them, so the adds of one launch meet the finished sums of the one before
     for (int kind = 0; kind < paths / 2; ++kind) {
@@ -372,10 +311,10 @@ int im_dense_sgm(im_ctx* ctx, const uint8_t* d_cost, int h0, int w0, int D, int 
 int im_dense_sgm_choose(im_ctx* ctx, const uint8_t* d_cost, const uint16_t* d_sum, int h0, int w0, int D, double w_first, double w_step,
                         double min_score, int16_t* d_plane, double* d_w, float* d_score, void* stream) {
     IM_CHECK_CTX(ctx);
-    if (!d_cost || !d_sum || !d_plane || !d_w || !d_score) return ctx->fail(SGM_REFUSED, "im_dense_sgm_choose: null pointer");
-    if (bad_side(h0) || bad_side(w0)) return ctx->fail(SGM_REFUSED, "im_dense_sgm_choose: h and w must be 1..16384");
-    if (bad_planes(D)) return ctx->fail(SGM_REFUSED, "im_dense_sgm_choose: D must be 1..256");
-    if (too_large(h0, w0, D)) return ctx->fail(SGM_REFUSED, "im_dense_sgm_choose: h0 w0 D must be at most 2^32");
+    if (!d_cost || !d_sum || !d_plane || !d_w || !d_score) return ctx->fail(DENSE_REFUSED, "im_dense_sgm_choose: null pointer");
+    if (bad_side(h0) || bad_side(w0)) return ctx->fail(DENSE_REFUSED, "im_dense_sgm_choose: h and w must be 1..16384");
+    if (bad_planes(D)) return ctx->fail(DENSE_REFUSED, "im_dense_sgm_choose: D must be 1..256");
+    if (too_large(h0, w0, D)) return ctx->fail(DENSE_REFUSED, "im_dense_sgm_choose: h0 w0 D must be at most 2^32");
     hipStream_t s = (hipStream_t)stream;
     SgmChooseArgs a{d_cost, d_sum, h0, w0, D, w_first, w_step, min_score, d_plane, d_w, d_score};
     IM_LAUNCH(ctx, "dense_sgm_choose", s,

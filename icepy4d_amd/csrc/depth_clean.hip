@@ -3,8 +3,9 @@
 // OpenCV's filterSpeckles and not Metashape's depth filter.
 //
 // Labelling is a union-find over the label array itself, parent[i] <= i, in separate launches on one stream:
-//   depth_tile_kernel      one block of 256 threads per 64 x 16 tile: planes, parents and counts of the tile in LDS (10 KB), every pixel linked
-//                          with its left and upper neighbour inside the tile (depth_link on LDS) and counted on its local root, then every
+//   depth_tile_kernel      one block of 256 threads per 64 x 16 tile (the sweep's tile and its map from a thread to its pixels: dense_tile.h):
+//                          planes, parents and counts of the tile in LDS (10 KB), every pixel linked with its left and upper
+//                          neighbour inside the tile (depth_link on LDS) and counted on its local root, then every
 //                          pixel's root written as a GLOBAL linear index and, on a root's slot of the scratch array, the pixels the tile
 //                          holds of it (0 elsewhere). Local and global indices order the pixels of a tile alike, so the local root is the
 //                          least global index.
@@ -24,14 +25,15 @@
 #include "ctx.h"
 #include "stage_scratch.h"
 #include "depth_pixel.h"
+#include "dense_tile.h"
+#include "dense_host.h"
 
 namespace im {
 namespace {
 
-constexpr int DEPTH_REFUSED = -83;
-constexpr int TW = DEPTH_TILE_W, TH = DEPTH_TILE_H, DEPTH_BLOCK = 256;
-constexpr int PIX = TW * TH / DEPTH_BLOCK;
-static_assert(TW == 64 && TW * TH % DEPTH_BLOCK == 0, "a row of the tile is one wave; whole rounds of the block cover the tile");
+// the labelling's tile is the sweep's (TW, TH, PIX and the map from a thread to its pixels are dense_tile.h's); so is the limit on a side
+constexpr int DEPTH_BLOCK = TILE_BLOCK;
+static_assert(DEPTH_TILE_W == TW && DEPTH_TILE_H == TH && DEPTH_MAX_SIDE == DENSE_MAX_SIDE, "im_depth_tile_w/h and bad_side speak of the shared tile");
 
 struct DepthLabelArgs {
     const int16_t* plane;
@@ -43,19 +45,19 @@ __global__ __launch_bounds__(DEPTH_BLOCK) void depth_tile_kernel(DepthLabelArgs 
     __shared__ int s_parent[TW * TH];
     __shared__ int s_count[TW * TH];
     __shared__ short s_plane[TW * TH];
-    const int t = threadIdx.x, x0 = blockIdx.x * TW, y0 = blockIdx.y * TH;
     const short outside = a.mode == DEPTH_SURFACES ? (short)-1 : (short)0;      // no member in either mode
 #pragma unroll
     for (int j = 0; j < PIX; ++j) {
-        const int p = t + DEPTH_BLOCK * j, x = x0 + (p & (TW - 1)), y = y0 + p / TW;
-        s_plane[p] = (x < a.w && y < a.h) ? a.plane[(size_t)y * a.w + x] : outside;
-        s_parent[p] = p;
-        s_count[p] = 0;
+        const TilePixel q = tile_pixel(j);
+        s_plane[q.p] = q.inside(a.h, a.w) ? a.plane[q.at(a.w)] : outside;
+        s_parent[q.p] = q.p;
+        s_count[q.p] = 0;
     }
     __syncthreads();
 #pragma unroll
     for (int j = 0; j < PIX; ++j) {
-        const int p = t + DEPTH_BLOCK * j, lx = p & (TW - 1), ly = p / TW, q = s_plane[p];
+        const TilePixel px = tile_pixel(j);
+        const int p = px.p, lx = px.c, ly = px.row, q = s_plane[p];
         if (lx > 0 && depth_joined(q, s_plane[p - 1], a.mode, a.max_diff)) depth_link(s_parent, p, p - 1);
         if (ly > 0 && depth_joined(q, s_plane[p - TW], a.mode, a.max_diff)) depth_link(s_parent, p, p - TW);
     }
@@ -63,18 +65,19 @@ __global__ __launch_bounds__(DEPTH_BLOCK) void depth_tile_kernel(DepthLabelArgs 
     int root[PIX];
 #pragma unroll
     for (int j = 0; j < PIX; ++j) {
-        const int p = t + DEPTH_BLOCK * j;
+        const int p = tile_pixel(j).p;
         root[j] = depth_member(s_plane[p], a.mode) ? depth_find(s_parent, p) : -1;      // pixels beyond the image are no members
         if (root[j] >= 0) atomicAdd(s_count + root[j], 1);
     }
     __syncthreads();
 #pragma unroll
     for (int j = 0; j < PIX; ++j) {
-        const int p = t + DEPTH_BLOCK * j, x = x0 + (p & (TW - 1)), y = y0 + p / TW, r = root[j];
-        if (x >= a.w || y >= a.h) continue;
-        const size_t i = (size_t)y * a.w + x;
-        a.label[i] = r < 0 ? -1 : (y0 + r / TW) * a.w + x0 + (r & (TW - 1));
-        a.cnt[i] = s_count[p];                       // not zero on the roots of the tile only
+        const TilePixel q = tile_pixel(j);
+        const int r = root[j];
+        if (!q.inside(a.h, a.w)) continue;
+        const long i = q.at(a.w);
+        a.label[i] = r < 0 ? -1 : (int)TilePixel(r).at(a.w);
+        a.cnt[i] = s_count[q.p];                       // not zero on the roots of the tile only
     }
 }
 
@@ -210,8 +213,6 @@ __global__ __launch_bounds__(DEPTH_BLOCK) void depth_fill_kernel(DepthFillArgs a
     depth_count(a.count, fill);
 }
 
-bool bad_side(int v) { return v < 1 || v > DEPTH_MAX_SIDE; }
-
 }  // namespace
 }  // namespace im
 
@@ -224,10 +225,10 @@ int im_depth_tile_h(void) { return DEPTH_TILE_H; }
 
 int im_depth_components(im_ctx* ctx, const int16_t* d_plane, int h, int w, int mode, int max_diff, int* d_label, int* d_size, void* stream) {
     IM_CHECK_CTX(ctx);
-    if (!d_plane || !d_label || !d_size) return ctx->fail(DEPTH_REFUSED, "im_depth_components: null pointer");
-    if (bad_side(h) || bad_side(w)) return ctx->fail(DEPTH_REFUSED, "im_depth_components: h and w must be 1..16384");
-    if (mode != DEPTH_SURFACES && mode != DEPTH_HOLES) return ctx->fail(DEPTH_REFUSED, "im_depth_components: mode must be 0 or 1");
-    if (max_diff < 0 || max_diff > DEPTH_MAX_DIFF) return ctx->fail(DEPTH_REFUSED, "im_depth_components: max_diff must be 0..4095");
+    if (!d_plane || !d_label || !d_size) return ctx->fail(DENSE_REFUSED, "im_depth_components: null pointer");
+    if (bad_side(h) || bad_side(w)) return ctx->fail(DENSE_REFUSED, "im_depth_components: h and w must be 1..16384");
+    if (mode != DEPTH_SURFACES && mode != DEPTH_HOLES) return ctx->fail(DENSE_REFUSED, "im_depth_components: mode must be 0 or 1");
+    if (max_diff < 0 || max_diff > DEPTH_MAX_DIFF) return ctx->fail(DENSE_REFUSED, "im_depth_components: max_diff must be 0..4095");
     hipStream_t s = (hipStream_t)stream;
     const long long n = (long long)h * w;
     const DepthComponentsScratch lay(n);
@@ -247,9 +248,9 @@ int im_depth_components(im_ctx* ctx, const int16_t* d_plane, int h, int w, int m
 int im_depth_drop_small(im_ctx* ctx, const int* d_size, int h, int w, int min_size, int16_t* d_plane, double* d_w, float* d_score, long long* d_count,
                         void* stream) {
     IM_CHECK_CTX(ctx);
-    if (!d_size || !d_plane || !d_w || !d_score || !d_count) return ctx->fail(DEPTH_REFUSED, "im_depth_drop_small: null pointer");
-    if (bad_side(h) || bad_side(w)) return ctx->fail(DEPTH_REFUSED, "im_depth_drop_small: h and w must be 1..16384");
-    if (min_size < 1) return ctx->fail(DEPTH_REFUSED, "im_depth_drop_small: min_size must be 1..2^31-1");
+    if (!d_size || !d_plane || !d_w || !d_score || !d_count) return ctx->fail(DENSE_REFUSED, "im_depth_drop_small: null pointer");
+    if (bad_side(h) || bad_side(w)) return ctx->fail(DENSE_REFUSED, "im_depth_drop_small: h and w must be 1..16384");
+    if (min_size < 1) return ctx->fail(DENSE_REFUSED, "im_depth_drop_small: min_size must be 1..2^31-1");
     hipStream_t s = (hipStream_t)stream;
     IM_HIP(ctx, hipMemsetAsync(d_count, 0, sizeof(long long), s));
     DepthDropArgs a{d_size, h, w, min_size, d_plane, d_w, d_score, d_count};
@@ -263,16 +264,16 @@ int im_depth_fill_holes(im_ctx* ctx, const int16_t* d_plane, const double* d_w, 
                         uint8_t* d_filled, long long* d_count, void* stream) {
     IM_CHECK_CTX(ctx);
     if (!d_plane || !d_w || !d_score || !d_label || !d_size || !d_plane_out || !d_w_out || !d_score_out || !d_filled || !d_count)
-        return ctx->fail(DEPTH_REFUSED, "im_depth_fill_holes: null pointer");
+        return ctx->fail(DENSE_REFUSED, "im_depth_fill_holes: null pointer");
     // a filled pixel must never be read as a rim pixel or an anchor by another thread
     if ((const void*)d_plane_out == (const void*)d_plane || (const void*)d_w_out == (const void*)d_w || (const void*)d_score_out == (const void*)d_score)
-        return ctx->fail(DEPTH_REFUSED, "im_depth_fill_holes: the outputs must not be the inputs");
-    if (bad_side(h) || bad_side(w)) return ctx->fail(DEPTH_REFUSED, "im_depth_fill_holes: h and w must be 1..16384");
-    if (max_hole < 1 || max_hole > DEPTH_MAX_HOLE) return ctx->fail(DEPTH_REFUSED, "im_depth_fill_holes: max_hole must be 1..4096");
-    if (max_diff < 0 || max_diff > DEPTH_MAX_DIFF) return ctx->fail(DEPTH_REFUSED, "im_depth_fill_holes: max_diff must be 0..4095");
-    if (D < 1 || D > DEPTH_MAX_PLANES) return ctx->fail(DEPTH_REFUSED, "im_depth_fill_holes: D must be 1..4096");
+        return ctx->fail(DENSE_REFUSED, "im_depth_fill_holes: the outputs must not be the inputs");
+    if (bad_side(h) || bad_side(w)) return ctx->fail(DENSE_REFUSED, "im_depth_fill_holes: h and w must be 1..16384");
+    if (max_hole < 1 || max_hole > DEPTH_MAX_HOLE) return ctx->fail(DENSE_REFUSED, "im_depth_fill_holes: max_hole must be 1..4096");
+    if (max_diff < 0 || max_diff > DEPTH_MAX_DIFF) return ctx->fail(DENSE_REFUSED, "im_depth_fill_holes: max_diff must be 0..4095");
+    if (D < 1 || D > DEPTH_MAX_PLANES) return ctx->fail(DENSE_REFUSED, "im_depth_fill_holes: D must be 1..4096");
     if (!std::isfinite(w_first) || !std::isfinite(w_step) || w_step == 0.0)
-        return ctx->fail(DEPTH_REFUSED, "im_depth_fill_holes: w_first must be finite, w_step finite and not zero");
+        return ctx->fail(DENSE_REFUSED, "im_depth_fill_holes: w_first must be finite, w_step finite and not zero");
     hipStream_t s = (hipStream_t)stream;
     const long long n = (long long)h * w;
     const DepthHolesScratch lay(n);

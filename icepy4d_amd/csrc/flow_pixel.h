@@ -24,31 +24,9 @@ constexpr long long FLOW_MAX_MIN_VAR = 1LL << 26;
 static_assert(961LL * 255 < (1LL << 18) && 961LL * 255 * 255 < (1LL << 26) && 961LL * 961 * FLOW_MAX_MIN_VAR < (1LL << 46), "the window sums");
 
 // ---- match ----------------------------------------------------------------------------------------------------------------------------------
-// The score of two windows of n bytes each from their integer sums: dense_score's rule without the 2^20 scale of warped samples.
-// false: too little texture in either window (or none: a zero variance would divide by zero, so it is invalid whatever min_var is).
-__device__ __forceinline__ bool flow_score(long long n, long long sa, long long saa, long long sb, long long sbb, long long sab, long long min_var,
-                                           double& s) {
-#pragma clang fp contract(off)
-    const long long VA = n * saa - sa * sa, VB = n * sbb - sb * sb, C = n * sab - sa * sb;
-    s = 0.0;
-    if (VA < n * n * min_var || VB < n * n * min_var || VA <= 0 || VB <= 0) return false;
-    s = (double)C / sqrt((double)VA * (double)VB);
-    return true;
-}
+// The window test, the window sums and the score are dense_pixel.h's: window_inside, dense_window_sums, and dense_score with the scale 1 of
+// bytes in either window.
 
-// does the window of radius r centred on (x, y) lie inside an image [h][w]?
-__device__ __forceinline__ bool flow_inside(int x, int y, int r, int h, int w) { return x >= r && x < w - r && y >= r && y < h - r; }
-
-// sum and sum of squares of the (2 r + 1)^2 window centred on *c (rows of `stride` bytes)
-__device__ __forceinline__ void flow_window_sums(const uint8_t* c, int stride, int r, long long& s1, long long& s2) {
-    unsigned a1 = 0, a2 = 0;
-    for (int dy = -r; dy <= r; ++dy)
-        for (int dx = -r; dx <= r; ++dx) {
-            const unsigned p = c[dy * stride + dx];
-            a1 += p; a2 += p * p;
-        }
-    s1 = a1; s2 = a2;
-}
 // sum of products of the two windows centred on *ca and *cb
 __device__ __forceinline__ long long flow_window_ab(const uint8_t* ca, int stride_a, const uint8_t* cb, int stride_b, int r) {
     unsigned ab = 0;
@@ -69,34 +47,29 @@ __device__ __forceinline__ bool flow_better(bool have, double s, int dx, int dy,
     return !have | (s > s0) | ((s == s0) & flow_before(dx, dy, dx0, dy0));
 }
 
-// The sub-pixel offset along one axis: the sweep's parabola over the best's two neighbours where both lie inside the search range and
-// scored (both: 1), the denominator is negative; else 0.
-__device__ __forceinline__ double flow_offset(bool both, double sm, double s0, double sp) {
-#pragma clang fp contract(off)
-    if (!both) return 0.0;
-    const double den = (sm - 2.0 * s0) + sp;
-    return den < 0.0 ? (0.5 * (sm - sp)) / den : 0.0;
-}
+// The sub-pixel offset along one axis: the sweep's parabola (dense_pixel.h) over the best's two neighbours where both lie inside the
+// search range and scored (both: 1); else 0.
+__device__ __forceinline__ double flow_offset(bool both, double sm, double s0, double sp) { return both ? parabola_offset(sm, s0, sp) : 0.0; }
 
 // The whole match of pixel (u, v) on the images themselves, candidate after candidate: what the kernel computes tile-wise from LDS.
 // a and b are [h][w]. false (and zeros) where no candidate scored or the best is below min_score.
 __device__ __forceinline__ bool flow_candidate(const uint8_t* a, const uint8_t* b, int h, int w, int u, int v, int r, int bx, int by, long long sa,
                                                long long saa, long long min_var, double& s) {
     s = 0.0;
-    if (!flow_inside(bx, by, r, h, w)) return false;
+    if (!window_inside(bx, by, r, h, w)) return false;
     const uint8_t* cb = b + (long)by * w + bx;
     long long sb, sbb;
-    flow_window_sums(cb, w, r, sb, sbb);
+    dense_window_sums(cb, w, r, sb, sbb);
     const long long n = (long long)(2 * r + 1) * (2 * r + 1);
-    return flow_score(n, sa, saa, sb, sbb, flow_window_ab(a + (long)v * w + u, w, cb, w, r), min_var, s);
+    return dense_score(n, sa, saa, sb, sbb, flow_window_ab(a + (long)v * w + u, w, cb, w, r), min_var, s, 1);
 }
 __device__ __forceinline__ bool flow_match_pixel(const uint8_t* a, const uint8_t* b, int h, int w, int u, int v, int r, int S, int pu, int pv,
                                                  long long min_var, double min_score, double& du, double& dv, float& score) {
 #pragma clang fp contract(off)
     du = dv = 0.0; score = 0.0f;
-    if (!flow_inside(u, v, r, h, w)) return false;
+    if (!window_inside(u, v, r, h, w)) return false;
     long long sa, saa;
-    flow_window_sums(a + (long)v * w + u, w, r, sa, saa);
+    dense_window_sums(a + (long)v * w + u, w, r, sa, saa);
     bool have = false;
     double s0 = 0.0;
     int bx = 0, by = 0;
@@ -135,14 +108,6 @@ __device__ __forceinline__ bool flow_consistent(int u, int v, double du, double 
 }
 
 // ---- lift -----------------------------------------------------------------------------------------------------------------------------------
-// the float-coordinate twin of dense_backproject: X = Ki (x, y, 1) / w
-__device__ __forceinline__ void flow_backproject(const double* Ki, double x, double y, double w, double* X) {
-#pragma clang fp contract(off)
-    X[0] = ((Ki[0] * x + Ki[1] * y) + Ki[2]) / w;
-    X[1] = ((Ki[3] * x + Ki[4] * y) + Ki[5]) / w;
-    X[2] = ((Ki[6] * x + Ki[7] * y) + Ki[8]) / w;
-}
-
 // The inverse depth of map B [hb][wb] at (x, y): all four taps floor(x) .. floor(x) + 1, floor(y) .. floor(y) + 1 inside the map (a tap of
 // weight zero included), with a plane and kept, and spanning at most `span` = max_diff |w_step_b|; then their bilinear mean, along x first.
 __device__ __forceinline__ bool flow_depth_at(const int16_t* plane_b, const double* w_b, const uint8_t* keep_b, int hb, int wb, double x, double y,
@@ -180,7 +145,7 @@ __device__ __forceinline__ bool flow_lift_pixel(const DenseCam& ca, const DenseC
     if (!flow_depth_at(plane_b, w_b, keep_b, hb, wb, x, y, span, wq)) return false;
     double X[3], Q[3];
     dense_world_point(ca, u, v, w_a, P);
-    flow_backproject(cb.Ki, x, y, wq, X);
+    dense_backproject_at(cb.Ki, x, y, wq, X);
     dense_to_world(cb, X, Q);
     for (int i = 0; i < 3; ++i) D[i] = Q[i] - P[i];
     return true;

@@ -3,7 +3,8 @@
 // few candidates around the current one, each scored over a window whose samples follow the slant instead of sharing the centre's depth.
 // Metashape's matcher is closed and is NOT reproduced: this is a definition of this project's own, restated in numpy by
 // tests/refine_oracle.py. Slants are in plane steps per pixel. Every sum is an integer, so the kernels may sum in any order; what is float64
-// uses only + - * / with contraction off, in the association written here. The sample and the score are dense_pixel.h's, defined once.
+// uses only + - * / with contraction off, in the association written here. The sample, the window sums, the score, the update of the running
+// best and the parabola are dense_pixel.h's, defined once.
 // A header of its own without the context or any launch code: tests/refine_host_harness.cpp compiles this very text behind a stub
 // <hip/hip_runtime.h>.
 #pragma once
@@ -82,18 +83,10 @@ __device__ __forceinline__ bool slant_pixel(const double* wc, const uint8_t* kc,
 // 0, -1, +1, -2, +2, ... and lets a later one replace the best only if it scores strictly more: the winner is the greatest score and, among
 // equal scores, the candidate visited first, i.e. the least |c|, and -c before +c. In ASCENDING order that is: replace on a greater score, or
 // on an equal one when |c| < |c_best| (the best so far lies below c, so an equal |c| means c = -c_best > 0, which was visited later and
-// loses). The rest is dense_best_step: the best, its predecessor and its successor.
+// loses). The rest is dense_best_update: the best, its predecessor and its successor.
 __device__ __forceinline__ void refine_best_step(DenseBest& b, int k, int c, bool valid, double s) {
     const int c_best = c - (k - b.k);                      // meaningful when b.k >= 0
-    if (valid && (b.k < 0 || s > b.s0 || (s == b.s0 && abs(c) < abs(c_best)))) {
-        b.s0 = s; b.k = k;
-        b.sm = b.prev; b.sp = 0.0;
-        b.flags = (b.flags >> 2) & 1;
-    } else if (b.k >= 0 && k == b.k + 1) {
-        b.sp = s; b.flags |= valid ? 2 : 0;
-    }
-    b.prev = valid ? s : 0.0;
-    b.flags = (b.flags & 3) | (valid ? 4 : 0);
+    dense_best_update(b, k, valid && (b.k < 0 || s > b.s0 || (s == b.s0 && abs(c) < abs(c_best))), valid, s);
 }
 
 // The refined (w, score) of a kept pixel (u, v) whose window of radius r lies inside ref. ref_c points at the pixel's ref byte in an array of
@@ -106,12 +99,8 @@ __device__ __forceinline__ bool refine_pixel(const uint8_t* ref_c, int ref_strid
 #pragma clang fp contract(off)
     const int side = 2 * r + 1, half = span * sub;
     const long long n = (long long)side * side;
-    long long sa = 0, saa = 0;
-    for (int dy = -r; dy <= r; ++dy)
-        for (int dx = -r; dx <= r; ++dx) {
-            const long long av = ref_c[dy * ref_stride + dx];
-            sa += av; saa += av * av;
-        }
+    long long sa, saa;
+    dense_window_sums(ref_c, ref_stride, r, sa, saa);
     DenseBest best;
     dense_best_init(best);
     for (int c = -half; c <= half; ++c) {
@@ -134,11 +123,7 @@ __device__ __forceinline__ bool refine_pixel(const uint8_t* ref_c, int ref_strid
     }
     w_out = w_i; score_out = score_i;
     if (best.k < 0 || !(best.s0 > (double)score_i)) return false;      // a NaN score takes nothing
-    double off = 0.0;
-    if (best.k >= 1 && best.k <= 2 * half - 1 && (best.flags & 3) == 3) {
-        const double den = (best.sm - 2.0 * best.s0) + best.sp;
-        if (den < 0.0) off = (0.5 * (best.sm - best.sp)) / den;
-    }
+    const double off = best.k >= 1 && best.k <= 2 * half - 1 && (best.flags & 3) == 3 ? parabola_offset(best.sm, best.s0, best.sp) : 0.0;
     w_out = w_i + (((double)(best.k - half) + off) / (double)sub) * w_step;
     score_out = (float)best.s0;
     return true;

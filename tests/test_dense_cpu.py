@@ -184,22 +184,6 @@ def write_records(path):
     return n
 
 
-def build_harness(tmp, sanitize):
-    if not os.path.exists(toolchain.CLANGXX):
-        pytest.skip("no clang++")
-    os.makedirs(os.path.join(tmp, "hip"), exist_ok=True)
-    with open(os.path.join(tmp, "hip", "hip_runtime.h"), "w") as f:
-        f.write(toolchain.HIP_STUB)
-    exe = os.path.join(tmp, "dense_host_harness" + ("_san" if sanitize else ""))
-    flags = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-g", "-O1"] if sanitize else ["-O2"]
-    r = subprocess.run([toolchain.CLANGXX, "-std=c++17", "-ffp-contract=off", *flags, "-I" + tmp, "-I" + toolchain.CSRC,
-                        os.path.join(ROOT, "tests", "dense_host_harness.cpp"), "-o", exe], capture_output=True, text=True)
-    if sanitize and r.returncode != 0 and "clang_rt" in r.stderr and "dense_host_harness.cpp:" not in r.stderr:
-        pytest.skip("this clang++ has no sanitizer runtimes")
-    assert r.returncode == 0, r.stderr[-2000:]
-    return exe
-
-
 @pytest.fixture(scope="module")
 def harness_dir(tmp_path_factory):
     d = str(tmp_path_factory.mktemp("dense_host"))
@@ -210,7 +194,7 @@ def harness_dir(tmp_path_factory):
 @pytest.mark.parametrize("sanitize", [False, True], ids=["plain", "asan_ubsan"])
 def test_host_build_equals_the_restatement_bit_for_bit(harness_dir, sanitize):
     d, n = harness_dir
-    exe = build_harness(d, sanitize)
+    exe = toolchain.host_program(d, "dense_host_harness.cpp", sanitize)
     r = subprocess.run([exe, os.path.join(d, "records.bin")], capture_output=True, text=True)
     print(r.stdout)
     assert r.returncode == 0 and r.stdout.strip().endswith("PASSED"), r.stdout[-3000:] + r.stderr[-3000:]
@@ -219,7 +203,7 @@ def test_host_build_equals_the_restatement_bit_for_bit(harness_dir, sanitize):
 
 
 def test_dense_cloud_scratch_is_as_carved(harness_dir):
-    exe = build_harness(harness_dir[0], False)
+    exe = toolchain.host_program(harness_dir[0], "dense_host_harness.cpp", False)
     up256 = lambda b: (b + 255) // 256 * 256  # noqa: E731
     for n in (1, 255, 256, 257, 8192, 8193, 16384 * 16384):
         r = subprocess.run([exe, "--scratch", str(n)], capture_output=True, text=True)
@@ -378,9 +362,30 @@ def test_abi_is_declared_bound_and_exported():
         assert "DENSE_MAX_SIDE = 16384, DENSE_MAX_PLANES = 4096, DENSE_MAX_RADIUS = 7" in f.read()
 
 
+def test_what_the_dense_stages_share_is_defined_once():
+    """The tile, its staging and the scoring of a plane are csrc/dense_tile.h's, the arithmetic csrc/dense_pixel.h's, the host checks
+    csrc/dense_host.h's: no kernel file restates them."""
+    text = {}
+    for name in os.listdir(toolchain.CSRC):
+        if name.endswith((".h", ".hip")):
+            with open(os.path.join(toolchain.CSRC, name)) as f:
+                text[name] = f.read()
+    calls = sorted(n for n, s in text.items() if re.search(r"(?<!bool )dense_sample\(", s))
+    assert calls == ["dense_tile.h", "refine_pixel.h"], calls                     # the sweep's plane scoring and the slanted window; no .hip file
+    assert not any("flow_score" in s for s in text.values())                      # dense_score with the scale 1 of bytes
+    parabola = sorted(n for n, s in text.items() if re.search(r"- 2\.0 \* [\w.]*s0\) \+", s))
+    assert parabola == ["dense_pixel.h"] and text["dense_pixel.h"].count("(sm - 2.0 * s0) + sp") == 1, parabola
+    assert sum(len(re.findall(r"bool bad_side\(", s)) for s in text.values()) == 1 and "bool bad_side(" in text["dense_host.h"]
+    for name in ("dense.hip", "dense_sgm.hip", "dense_refine.hip", "dense_flow.hip", "depth_clean.hip"):
+        assert '#include "dense_tile.h"' in text[name] and "blockIdx.x * TW" not in text[name] and "= -83" not in text[name], name
+    assert text["dense_tile.h"].count("static_assert(TW == 64") == 1 and not any("static_assert(TW == 64" in s for n, s in text.items() if n != "dense_tile.h")
+    with open(os.path.join(ROOT, "tests", "dense_host_harness.cpp")) as f:
+        assert "dense_tile.h" not in f.read()                                     # kernel text: threadIdx, __shared__, barriers
+
+
 def test_the_kernels_spill_nothing_and_two_blocks_fit_a_cu(tmp_path):
     """The sweep's block is 256 threads, one wave per SIMD: two blocks on a CU need at most 256 VGPRs per lane (512 per SIMD lane) and
-    80 KiB of LDS each (160 KiB per CU). Compiled: 42 576 B of LDS and 137 VGPRs, so three blocks fit by either."""
+    80 KiB of LDS each (160 KiB per CU). Compiled: 42 576 B of LDS and 136 VGPRs, so three blocks fit by either."""
     res = toolchain.kernel_resources(toolchain.device_listing("dense.hip", str(tmp_path)))
     mine = {k: v for k, v in res.items() if "dense_" in k or "DenseCloudScan" in k}
     assert len(mine) == 2 + 2, sorted(res)                                    # two kernels and the scan's two templates
@@ -391,7 +396,7 @@ def test_the_kernels_spill_nothing_and_two_blocks_fit_a_cu(tmp_path):
     lds = 30 * 78 * (1 + 4) + 30 * 64 * (8 + 8) + 18 * 8                      # a, b, the two rows of partials, A and B; plus alignment
     assert lds <= sweep[0]["group_segment_fixed_size"] <= lds + 64 and 2 * (lds + 64) <= 160 * 1024
     print("dense_sweep_kernel: vgpr", sweep[0]["vgpr_count"], "sgpr", sweep[0]["sgpr_count"], "lds", lds)
-    assert sweep[0]["vgpr_count"] <= 168                                       # 137 as compiled: three waves per SIMD of 512; two blocks need <= 256
+    assert sweep[0]["vgpr_count"] <= 168                                       # 136 as compiled: three waves per SIMD of 512; two blocks need <= 256
     assert sweep[0]["max_flat_workgroup_size"] == 256
 
 

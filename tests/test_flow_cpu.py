@@ -257,27 +257,6 @@ def write_records(path):
     return n
 
 
-def build_harness(tmp, sanitize):
-    if not os.path.exists(toolchain.CLANGXX):
-        pytest.skip("no clang++")
-    os.makedirs(os.path.join(tmp, "hip"), exist_ok=True)
-    with open(os.path.join(tmp, "hip", "hip_runtime.h"), "w") as f:
-        f.write(toolchain.HIP_STUB)
-    exe = os.path.join(tmp, "flow_host_harness" + ("_san" if sanitize else ""))
-    flags = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-g", "-O1"] if sanitize else ["-O2"]
-    if sanitize:                          # the sanitizer runtimes are asked for before the harness is built: its own failure to build is never a skip
-        probe = os.path.join(tmp, "sanitizer_probe.cpp")
-        with open(probe, "w") as f:
-            f.write("int main() { return 0; }\n")
-        r = subprocess.run([toolchain.CLANGXX, *flags, probe, "-o", os.path.join(tmp, "sanitizer_probe")], capture_output=True, text=True)
-        if r.returncode != 0:
-            pytest.skip("this clang++ has no sanitizer runtimes")
-    r = subprocess.run([toolchain.CLANGXX, "-std=c++17", "-ffp-contract=off", *flags, "-I" + tmp, "-I" + toolchain.CSRC,
-                        os.path.join(ROOT, "tests", "flow_host_harness.cpp"), "-o", exe], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    return exe
-
-
 @pytest.fixture(scope="module")
 def harness_dir(tmp_path_factory):
     d = str(tmp_path_factory.mktemp("flow_host"))
@@ -287,7 +266,7 @@ def harness_dir(tmp_path_factory):
 @pytest.mark.parametrize("sanitize", [False, True], ids=["plain", "asan_ubsan"])
 def test_host_build_equals_the_restatement_bit_for_bit(harness_dir, sanitize):
     d, n = harness_dir
-    exe = build_harness(d, sanitize)
+    exe = toolchain.host_program(d, "flow_host_harness.cpp", sanitize)
     r = subprocess.run([exe, os.path.join(d, "records.bin")], capture_output=True, text=True)
     print(r.stdout)
     assert r.returncode == 0 and r.stdout.strip().endswith("PASSED"), r.stdout[-3000:] + r.stderr[-3000:]

@@ -240,22 +240,6 @@ def write_harness_inputs(d):
     dump(d, "depth9", [M9, N9, node9, node9 * 8 + 7, 4 * N9 * 8, N9 * 4, node9, up256((N9 + 255) // 256 * 8) + 256, 2 ** 26, 2, 9, 1024], np.int64)
 
 
-def build_harness(tmp, sanitize):
-    if not os.path.exists(toolchain.CLANGXX):
-        pytest.skip("no clang++")
-    os.makedirs(os.path.join(tmp, "hip"), exist_ok=True)
-    with open(os.path.join(tmp, "hip", "hip_runtime.h"), "w") as f:
-        f.write(toolchain.HIP_STUB)
-    exe = os.path.join(tmp, "poisson_host_harness" + ("_san" if sanitize else ""))
-    flags = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-g", "-O1"] if sanitize else ["-O2"]
-    r = subprocess.run([toolchain.CLANGXX, "-std=c++17", "-ffp-contract=off", *flags, "-I" + tmp, "-I" + toolchain.CSRC,
-                        os.path.join(ROOT, "tests", "poisson_host_harness.cpp"), "-o", exe], capture_output=True, text=True)
-    if sanitize and r.returncode != 0 and "clang_rt" in r.stderr and "poisson_host_harness.cpp:" not in r.stderr:
-        pytest.skip("this clang++ has no sanitizer runtimes")
-    assert r.returncode == 0, r.stderr[-2000:]
-    return exe
-
-
 @pytest.fixture(scope="module")
 def harness_dir(tmp_path_factory):
     d = str(tmp_path_factory.mktemp("poisson_host"))
@@ -265,7 +249,7 @@ def harness_dir(tmp_path_factory):
 
 @pytest.mark.parametrize("sanitize", [False, True], ids=["plain", "asan_ubsan"])
 def test_host_build_equals_the_restatement_bit_for_bit(harness_dir, sanitize):
-    exe = build_harness(harness_dir, sanitize)
+    exe = toolchain.host_program(harness_dir, "poisson_host_harness.cpp", sanitize)
     r = subprocess.run([exe, harness_dir], capture_output=True, text=True)
     print(r.stdout)
     assert r.returncode == 0 and r.stdout.strip().endswith("PASSED"), r.stdout[-3000:] + r.stderr[-3000:]

@@ -237,22 +237,6 @@ def write_records(path):
     return len(C.cases())
 
 
-def build_harness(tmp, sanitize):
-    if not os.path.exists(toolchain.CLANGXX):
-        pytest.skip("no clang++")
-    os.makedirs(os.path.join(tmp, "hip"), exist_ok=True)
-    with open(os.path.join(tmp, "hip", "hip_runtime.h"), "w") as f:
-        f.write(toolchain.HIP_STUB)
-    exe = os.path.join(tmp, "refine_host_harness" + ("_san" if sanitize else ""))
-    flags = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-g", "-O1"] if sanitize else ["-O2"]
-    r = subprocess.run([toolchain.CLANGXX, "-std=c++17", "-ffp-contract=off", *flags, "-I" + tmp, "-I" + toolchain.CSRC,
-                        os.path.join(ROOT, "tests", "refine_host_harness.cpp"), "-o", exe], capture_output=True, text=True)
-    if sanitize and r.returncode != 0 and "clang_rt" in r.stderr and "refine_host_harness.cpp:" not in r.stderr:
-        pytest.skip("this clang++ has no sanitizer runtimes")
-    assert r.returncode == 0, r.stderr[-2000:]
-    return exe
-
-
 @pytest.fixture(scope="module")
 def harness_dir(tmp_path_factory):
     d = str(tmp_path_factory.mktemp("refine_host"))
@@ -262,7 +246,7 @@ def harness_dir(tmp_path_factory):
 @pytest.mark.parametrize("sanitize", [False, True], ids=["plain", "asan_ubsan"])
 def test_host_build_equals_the_restatement_bit_for_bit(harness_dir, sanitize):
     d, n = harness_dir
-    exe = build_harness(d, sanitize)
+    exe = toolchain.host_program(d, "refine_host_harness.cpp", sanitize)
     r = subprocess.run([exe, os.path.join(d, "records.bin")], capture_output=True, text=True)
     print(r.stdout)
     assert r.returncode == 0 and r.stdout.strip().endswith("PASSED"), r.stdout[-3000:] + r.stderr[-3000:]
@@ -289,7 +273,11 @@ def test_abi_is_declared_bound_and_exported():
     with open(os.path.join(toolchain.CSRC, "refine_pixel.h")) as f:
         text = f.read()
     assert "REFINE_MAX_FIT_RADIUS = 7, REFINE_MIN_COUNT = 3, REFINE_MAX_COUNT = 225, REFINE_MAX_SPAN = 4, REFINE_MAX_SUB = 8" in text
-    assert text.count("#pragma clang fp contract(off)") == 3 and "static_assert" in text      # every function that computes in float64; the int64 headroom
+    # every function of this header that computes in float64 switches contraction off: slant_height, slant_fit and refine_pixel, three.
+    # (refine_best_step only compares; the score, the parabola and the sample carry their own pragma in dense_pixel.h.) And the int64 headroom
+    assert text.count("#pragma clang fp contract(off)") == 3 and "static_assert" in text
+    for fn in ("slant_height", "slant_fit", "refine_pixel"):
+        assert re.search(r"bool " + fn + r"\([^{]*\{\n#pragma clang fp contract\(off\)", text), fn
     assert "sqrt" not in text and "fma" not in text and "atomic" not in text                  # + - * /; the one sqrt is dense_score's
     with open(os.path.join(toolchain.CSRC, "dense_pixel.h")) as f:
         dense = f.read()

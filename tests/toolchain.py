@@ -1,5 +1,6 @@
-"""The two compiler invocations the CPU tests share: a host build of kernel text behind a stub <hip/hip_runtime.h>, and the gfx950
-assembly listing of a .hip file with its kernels' resource fields. Neither needs a GPU; a test is skipped where the compiler is absent."""
+"""The compiler invocations the CPU tests share: a host build of kernel text behind a stub <hip/hip_runtime.h>, as a shared library or as a
+stand-alone program (plain or under the address and undefined-behaviour sanitizers), and the gfx950 assembly listing of a .hip file with its
+kernels' resource fields. None needs a GPU; a test is skipped where the compiler is absent."""
 import collections
 import ctypes
 import os
@@ -28,6 +29,31 @@ def host_library(tmp_dir, harness_cpp):
                         os.path.join(ROOT, "tests", harness_cpp), "-o", so], capture_output=True, text=True)
     assert r.returncode == 0, r.stderr[-2000:]
     return ctypes.CDLL(so)
+
+
+def host_program(tmp_dir, harness_cpp, sanitize):
+    """tests/<harness_cpp>, which has a main of its own, and the csrc headers it includes as a stand-alone program, built plain or with the
+    address and undefined-behaviour sanitizers: the path of the executable. The sanitizer runtimes are asked for with an empty program
+    before the harness is built, so the harness's own failure to build is never a skip."""
+    if not os.path.exists(CLANGXX):
+        pytest.skip("no clang++")
+    tmp_dir = str(tmp_dir)
+    os.makedirs(os.path.join(tmp_dir, "hip"), exist_ok=True)
+    with open(os.path.join(tmp_dir, "hip", "hip_runtime.h"), "w") as f:
+        f.write(HIP_STUB)
+    flags = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-g", "-O1"] if sanitize else ["-O2"]
+    if sanitize:
+        probe = os.path.join(tmp_dir, "sanitizer_probe.cpp")
+        with open(probe, "w") as f:
+            f.write("int main() { return 0; }\n")
+        r = subprocess.run([CLANGXX, *flags, probe, "-o", os.path.join(tmp_dir, "sanitizer_probe")], capture_output=True, text=True)
+        if r.returncode != 0:
+            pytest.skip("this clang++ has no sanitizer runtimes")
+    exe = os.path.join(tmp_dir, os.path.splitext(os.path.basename(harness_cpp))[0] + ("_san" if sanitize else ""))
+    r = subprocess.run([CLANGXX, "-std=c++17", "-ffp-contract=off", *flags, "-I" + tmp_dir, "-I" + CSRC, os.path.join(ROOT, "tests", harness_cpp), "-o", exe],
+                       capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-2000:]
+    return exe
 
 
 def device_listing(hip_file, tmp_dir):
