@@ -134,6 +134,8 @@ SIGNATURES = {
     "im_flow_match": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _L, _D, _P, _P, _P, _P, _P, _P],
     "im_flow_check": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _D, _P, _P],
     "im_flow_lift": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _I, _I, _P, _D, _D, _P, _P, _P, _P],
+    "im_flow_prior_up": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P],
+    "im_flow_match_field": [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _L, _D, _P, _P, _P, _P, _P, _P, _P],
     "im_depth_tile_w": [],
     "im_depth_tile_h": [],
     "im_depth_components": [_P, _P, _I, _I, _I, _I, _P, _P, _P],

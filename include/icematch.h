@@ -754,6 +754,34 @@ int im_flow_lift(im_ctx* ctx, const double* d_du, const double* d_dv, const uint
                  const double* d_w_a, int h, int w, const double* h_cam_a, const int16_t* d_plane_b, const double* d_w_b, const uint8_t* d_keep_b, int hb,
                  int wb, const double* h_cam_b, double w_step_b, double max_diff, double* d_P, double* d_D, uint8_t* d_ok, void* stream);
 
+/* ---- coarse-to-fine dense displacement (csrc/dense_flow_field.hip, csrc/flow_field_pixel.h): a prior per pixel in place of im_flow_match's
+ * one global prior, and the prior of a level from the field of the level above. Level l + 1 of the pyramid is im_pyr_down of level l with
+ * one channel, so coarse pixel (x, y) sits on fine pixel (2 x, 2 y) and a displacement halves per level. A definition of this project's own
+ * (DESIGN §4), restated in tests/pyrflow_oracle.py: bit-identical. All arrays in DEVICE memory.
+ * im_flow_prior_up: d_du_c, d_dv_c float64 and d_valid_c uint8 [hc][wc] are a field of the coarse level, hc = (h + 1) / 2, wc = (w + 1) / 2.
+ * For fine pixel (u, v): the coarse pixels of the (2 median_radius + 1)^2 neighbourhood of (u >> 1, v >> 1) inside the coarse image that are
+ * valid and whose du and dv are both finite, n of them. n < min_count: have = 0, pu = pv = 0. Else pu = (int) rint(2.0 * med_u) with med_u
+ * element (n - 1) / 2 of the ascending du values (the lower median, no averaging), pv likewise from the dv values, independently; if
+ * |pu| > 4096 or |pv| > 4096, have = 0 and both are zero. d_pu, d_pv int16 [h][w], d_have uint8 [h][w].
+ * im_flow_match_field: im_flow_match with the prior (d_pu, d_pv) of each pixel in place of (prior_u, prior_v). A pixel is matched when
+ * d_have is not 0 there, d_ask (NULL = every pixel) is not 0 there and both components of its prior lie in -4096..4096; its candidates are
+ * its own prior + (dx, dy), |dx|, |dy| <= search, exact ties go to the smallest displacement from its own prior, and the parabola takes
+ * neighbours inside its own range only. Every other pixel gets zeros and d_valid = 0. With a constant field this is im_flow_match with that
+ * prior, bit for bit. Safe for any content of d_pu, d_pv, d_have, d_ask: neither image is read outside its bounds. One block per
+ * im_dense_tile_w() x im_dense_tile_h() pixels; d_tile_path (NULL, or uint8 [blocks_y][blocks_x]) receives the path each tile took, a pure
+ * function of its inputs: 0 = no pixel of the tile is to be matched with its window inside a, else with the box [lo_u, hi_u] x [lo_v, hi_v]
+ * of those pixels' priors, 1 (tiled, from LDS) where hi_u - lo_u <= E and hi_v - lo_v <= E, 2 (direct, from global memory) otherwise;
+ * E = the greatest value <= 8 at which the tiled path's LDS for a box of E x E fits 64512 bytes at this r and search. Both paths give the
+ * same bits.
+ * Both write every element of every output, and return -83, without launching and with the outputs untouched, for a null pointer other
+ * than d_ask and d_tile_path, a side outside 1..16384, hc != (h + 1) / 2 or wc != (w + 1) / 2, median_radius outside 0..2, min_count outside
+ * 1..(2 median_radius + 1)^2, r outside 1..15, search outside 0..16, min_var outside 0..2^26 or a min_score that is not finite. Enqueue only. */
+int im_flow_prior_up(im_ctx* ctx, const double* d_du_c, const double* d_dv_c, const uint8_t* d_valid_c, int hc, int wc, int h, int w,
+                     int median_radius, int min_count, int16_t* d_pu, int16_t* d_pv, uint8_t* d_have, void* stream);
+int im_flow_match_field(im_ctx* ctx, const uint8_t* d_a, const uint8_t* d_b, int h, int w, int r, int search, const int16_t* d_pu,
+                        const int16_t* d_pv, const uint8_t* d_have, long long min_var, double min_score, const uint8_t* d_ask, double* d_du,
+                        double* d_dv, float* d_score, uint8_t* d_valid, uint8_t* d_tile_path, void* stream);
+
 /* ---- volume variations (`scripts/pcd_postprocessing/volume_variations.py`; `post_processing/cloudcompare_fun.py`:
  * `DemOfDifference.compute_volume` over CloudCompare's `ComputeVolume25D`; `post_processing/open3d_fun.py`: `filter_pcd_by_polyline`);
  * csrc/dod.hip, csrc/dod_cell.h. The DEM of difference of P pairs (ground, ceil) over E clouds that lie one behind the other in d_pts
